@@ -23,11 +23,25 @@ ranks are already there and WORLD_SIZE decides.
 Other BASELINE configs with the same script: --env Ant4Rooms-v0 (configs[3], with --gpus 8),
 --env AntPush-v0 --envs 2048 (configs[4]), --env PointUMaze-v0 (configs[1]).
 
-Prints ONE JSON line (rank 0) with the fields the driver expects plus
+A plain run does only what the headline figure needs: set up, settle, warm up, time the
+--steps, write the outputs (--dump-outputs) and print ONE JSON line (rank 0) with metric,
+value, unit, higher_is_better, dtype and ms_per_step (wall milliseconds of one timed step).
+
+--dump-outputs DIR: after the timed window, what its last step returned to the caller
+(obs, reward, done, info arrays) is written as DIR/<name>.npy in float32; the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
+Above 64 MB in all, a fixed seeded sample of rows is written (DIR/<name>_rows.npy: indices).
+
+--full adds, as separate fields of the same line:
   roofline     : algorithmic HBM bytes per launch / average kernel duration (HIP events on
-                 the launch stream, recorded inside the timed region)
+                 the launch stream, recorded inside the timed region) and the HBM traffic of
+                 rocprofv3 --pmc child passes (--no-live-pmc: the committed profiles/ instead)
+  roofline_valu: VALU figures from the committed profiles/ counters
+  sustained    : the same loop over --sustained more launches after the timed window
+  without_allgather (N > 1): the timed steps once more with the collective off
   cpu_baseline : the CPU oracle (a restatement — MuJoCo itself is not available) timed on
-                 this box's host cores on a bounded sample of the same workload.
+                 this box's host cores on a bounded sample of the same workload
+                 (--no-cpu-baseline: skipped).
 """
 import argparse
 import json
@@ -48,6 +62,7 @@ FP64_VECTOR_PEAK_TFLOPS = 78.6   # AMD's MI355X spec sheet: FP64 vector = half t
 N_SIMD = 256 * 4                 # 256 CUs x 4 SIMDs
 PMC_PASS_TIMEOUT_S = 240         # each of the two live rocprofv3 --pmc child passes (about 20 s each on a fresh box)
 SUSTAINED_STEPS = 1000           # the untimed-by-the-metric leg behind the timed window: the settled kernel over a long rollout
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: at most 64 MB in all
 # tools/fetch_calib.hip under `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` on 1 GiB (past the 256 MiB Infinity Cache), profiles/r05/fetch_calibration.txt
 FETCH_CALIBRATION = "FETCH_SIZE = 0.50 x bytes for 4 / 8 / 16-byte-per-lane and 192-byte-record data streams, 1.0 x per XCD for instruction fetch; WRITE_SIZE = 1.00 x (profiles/r05/fetch_calibration.txt)"
 
@@ -96,7 +111,7 @@ def live_pmc_traffic(args):
     workload is stepped twice more in child processes under `rocprofv3 --pmc FETCH_SIZE` and `--pmc WRITE_SIZE` (separate
     passes, counters only — no tracing domain — as MI355X_MICROARCH.md prescribes: the two do not fit one pass), 100 settle +
     64 profiled launches each; returns ({"FETCH_SIZE": KB, "WRITE_SIZE": KB} per-launch averages over the launches after the
-    settle steps, note) or (None, why).  The children run with --no-live-pmc / --no-cpu-baseline and print nothing we use."""
+    settle steps, note) or (None, why).  The children are plain runs (no --full) and print nothing we use."""
     import csv
     import glob
     import shutil
@@ -112,7 +127,7 @@ def live_pmc_traffic(args):
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             out = os.path.join(tmp, counter)
             cmd = [exe, "--pmc", counter, "--output-format", "csv", "-d", out, "--", sys.executable, os.path.abspath(__file__), "--env", args.env,
-                   "--envs", str(args.envs), "--settle", str(settle), "--warmup", "0", "--steps", str(steps), "--no-cpu-baseline", "--no-live-pmc", "--sustained", "0"]
+                   "--envs", str(args.envs), "--settle", str(settle), "--warmup", "0", "--steps", str(steps)]
             if args.lanes:
                 cmd += ["--lanes", str(args.lanes)]
             for kv in args.opt:
@@ -220,6 +235,38 @@ def cpu_baseline(model, env_id, n, lo, hi, seconds_target=12.0):
                       "(oracle/libmzo_fast.so; the strict-fp libmzo.so is the parity checker, not timed), OpenMP over envs"}
 
 
+def step_outputs(result, gatherer=None):
+    """Host copies (float32) of what one MazeEnv.step returned: obs, reward, done, every info array (final_observation only in
+    the rows it is valid in, done != 0, zero elsewhere) and, for N > 1, the all-gathered record of all ranks."""
+    obs, reward, done, info = result
+    out = {"obs": obs, "reward": reward, "done": done}
+    for k, v in info.items():
+        out[k] = v.where((done != 0).unsqueeze(1), 0.0) if k == "final_observation" else v
+    if gatherer is not None:
+        out["record_gathered"] = gatherer.gathered
+    return {k: v.detach().float().cpu().numpy() for k, v in out.items()}
+
+
+def dump_outputs(outputs, out_dir, limit_bytes=DUMP_LIMIT_BYTES):
+    """DIR/<name>.npy for each array.  Above `limit_bytes` in all, every array keeps the same fraction of its rows, chosen by a fixed
+    seed (the same rows from run to run), and DIR/<name>_rows.npy holds their indices."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    budget = limit_bytes - 2 * 256 * len(outputs)  # .npy headers (128 bytes each) of the arrays and their row files
+    total = sum(a.nbytes for a in outputs.values())
+    frac = 1.0
+    if total > budget:  # a sampled row costs its bytes plus its float64 index
+        frac = budget / (total + 8 * sum(a.shape[0] for a in outputs.values()))
+    for name, a in outputs.items():
+        if frac < 1.0:
+            k = max(1, int(a.shape[0] * frac))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], k, replace=False))
+            a = a[rows]
+            np.save(os.path.join(out_dir, f"{name}_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
+
+
 def _capi_path():
     from mujoco_maze_amd import _capi
     return _capi.LIB_PATH
@@ -285,15 +332,19 @@ def main():
     ap.add_argument("--lanes", type=int, default=0, help="lanes per env (8/16/32/64); 0 = library default")
     ap.add_argument("--wpb", type=int, default=0, help="wavefronts per workgroup (1/2/4); 0 = library default")
     ap.add_argument("--no-gather", action="store_true", help="skip the RCCL obs all-gather for N > 1")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--sustained", type=int, default=SUSTAINED_STEPS, help="steps of the extra, separately reported leg behind the timed window (0 = off)")
-    ap.add_argument("--no-live-pmc", action="store_true", help="do not spawn the rocprofv3 --pmc child passes for roofline.traffic (fall back to profiles/)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy (float32, <= 64 MB)")
+    ap.add_argument("--full", action="store_true", help="also measure roofline, roofline_valu, sustained, without_allgather and cpu_baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
+    ap.add_argument("--sustained", type=int, default=SUSTAINED_STEPS, help="--full: steps of the extra, separately reported leg behind the timed window (0 = off)")
+    ap.add_argument("--no-live-pmc", action="store_true", help="--full: do not spawn the rocprofv3 --pmc child passes for roofline.traffic (fall back to profiles/)")
     ap.add_argument("--dry-run", action="store_true", help="launcher / process-group plumbing only, no GPU work (CPU test of --gpus N)")
     ap.add_argument("--opt", action="append", default=[], help="extra library option key=value (tuning experiments)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args))
     if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) != args.gpus:
@@ -354,10 +405,11 @@ def main():
         g = gatherer if gather else None
         if g is not None:
             env.bind_record(g.flip())
-        env.step(pool[i % len(pool)])
+        result = env.step(pool[i % len(pool)])
         if g is not None:
             g.wait()       # previous step's gather (its receive buffer is reused)
             g.start()      # async RCCL all-gather of this step's record
+        return result
 
     def timed(steps, gather=True):
         torch.cuda.synchronize(dev)
@@ -366,7 +418,7 @@ def main():
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
         for i in range(steps):
-            one_step(i, gather)
+            last = one_step(i, gather)
         if gatherer is not None and gather:
             gatherer.wait()
         torch.cuda.synchronize(dev)
@@ -378,7 +430,7 @@ def main():
             tmax = torch.tensor([el], dtype=torch.float64, device=dev)
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             el = float(tmax.item())
-        return el
+        return el, last
 
     for i in range(args.settle):
         one_step(i)
@@ -393,43 +445,36 @@ def main():
         env.set_option("time_kernels_stride", stride)
         return stride
 
-    ev_stride = time_every(args.steps)
-    dt = timed(args.steps)
-    kernel_ms = env.kernel_ms()
+    ev_stride = time_every(args.steps) if args.full else None
+    dt, last = timed(args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(step_outputs(last, gatherer), args.dump_outputs)
     status = env.status()
     bad = int(((status & 3) != 0).sum().item())
-    kernel_ms_ranks, no_gather = [kernel_ms], None
-    # the sustained number: the driver's short window sits a few hundred launches into the rollout; the same
-    # loop once more over SUSTAINED_STEPS launches, NOT part of `value` / `ms_per_step`
-    sustained = None
-    if world == 1 and args.sustained > 0:
-        time_every(args.sustained)
-        dt_s = timed(args.sustained)
-        sustained = {"value": n * args.sustained / dt_s, "kernel_ms": env.kernel_ms(), "ms_per_step": dt_s / args.sustained * 1e3, "steps": args.sustained,
-                     "note": "same loop, run after the timed window; not part of value"}
-    if world > 1:
-        km = torch.zeros(world, dtype=torch.float64, device=dev)
-        km[rank] = kernel_ms
-        dist.all_reduce(km)
-        kernel_ms_ranks = [float(x) for x in km.tolist()]
-        if gatherer is not None:  # the same K steps once more without the collective
-            env.bind_record(None)
-            dt_ng = timed(args.steps, gather=False)
-            no_gather = {"value": n * world * args.steps / dt_ng, "ms_per_step": dt_ng / args.steps * 1e3}
+    if args.full:
+        kernel_ms = env.kernel_ms()
+        kernel_ms_ranks, sustained, no_gather = [kernel_ms], None, None
+        # the sustained number: the driver's short window sits a few hundred launches into the rollout; the same
+        # loop once more over SUSTAINED_STEPS launches, NOT part of `value` / `ms_per_step`
+        if world == 1 and args.sustained > 0:
+            time_every(args.sustained)
+            dt_s, _ = timed(args.sustained)
+            sustained = {"value": n * args.sustained / dt_s, "kernel_ms": env.kernel_ms(), "ms_per_step": dt_s / args.sustained * 1e3, "steps": args.sustained,
+                         "note": "same loop, run after the timed window; not part of value"}
+        if world > 1:
+            km = torch.zeros(world, dtype=torch.float64, device=dev)
+            km[rank] = kernel_ms
+            dist.all_reduce(km)
+            kernel_ms_ranks = [float(x) for x in km.tolist()]
+            if gatherer is not None:  # the same K steps once more without the collective
+                env.bind_record(None)
+                dt_ng, _ = timed(args.steps, gather=False)
+                no_gather = {"value": n * world * args.steps / dt_ng, "ms_per_step": dt_ng / args.steps * 1e3}
 
     if rank == 0:
         total_env_steps = n * world * args.steps
         value = total_env_steps / dt
-        per_env = algo_bytes_per_env_step(env.model.c)
-        algo_bytes = per_env * n
-        achieved = algo_bytes / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else None
-        pmc = pmc_counters(env_id, n)
-        live, live_note = (None, "disabled (--no-live-pmc)") if (args.no_live_pmc or world > 1) else live_pmc_traffic(args)
-        traffic = pmc_traffic(live) if live else pmc_traffic(pmc)
-        traffic_source = live_note if live else (f"fallback ({live_note}): " + pmc.get("_file", "none committed for this workload") +
-                                                 ": FETCH_SIZE + WRITE_SIZE (KB) of the committed rocprofv3 --pmc passes of this command, bytes per launch")
         robot = env.model.c.robot
-        kernel = {1: "ant_step_kernel", 0: "planar_step_kernel", 2: "swimmer_step_kernel"}[robot]
         out = {
             "metric": f"env-steps/sec (whole node), {env_id}, {n} envs/GPU",
             "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -443,23 +488,33 @@ def main():
                        "launch": env.launch_info(),  # the instantiation this batch size / device selected (mz_get_info)
                        **({"rehearsal": "all ranks on one GPU over gloo (MZ_BENCH_SINGLE_GPU=1): not a scaling measurement"}
                           if os.environ.get("MZ_BENCH_SINGLE_GPU") == "1" else {})},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": (achieved / HBM_PEAK_GBS) if achieved else None, "traffic": traffic,
-                         "kernel": kernel, "kernel_ms": kernel_ms, "kernel_ms_per_rank": kernel_ms_ranks,
-                         "kernel_ms_source": "HIP event pairs on the kernel's stream around every %d-th launch of the timed region (mz_last_kernel_ms)" % ev_stride,
-                         "algorithmic_bytes_per_launch": algo_bytes,
-                         "algorithmic_bytes_per_env_step": per_env,
-                         "traffic_source": traffic_source,
-                         "traffic_over_algorithmic": (traffic / algo_bytes) if traffic else None,
-                         "traffic_lower": pmc_traffic(live or pmc, corrected=False) if traffic else None,
-                         "traffic_definition": "v2 (since round 5): 2 x FETCH_SIZE + WRITE_SIZE, the guide's gfx950 correction; the lines of rounds 1-4 carried "
-                                               "v1 = FETCH_SIZE + WRITE_SIZE, which is this line's traffic_lower — compare like with like",
-                         "traffic_note": "traffic = 2 x FETCH_SIZE + WRITE_SIZE (gfx950: FETCH_SIZE counts data reads at half their bytes — calibrated for this "
-                                         "kernel's access widths, tools/fetch_calib.hip — but instruction fetch in full: an upper bound); traffic_lower = FETCH_SIZE + WRITE_SIZE",
-                         "traffic_fetch_bytes": ((live or pmc).get("FETCH_SIZE", 0.0) * 1024.0) if traffic else None,
-                         "traffic_write_bytes": ((live or pmc).get("WRITE_SIZE", 0.0) * 1024.0) if traffic else None,
-                         "note": "latency/VALU-bound path (SURVEY 8d): ~0.5 KB of HBM traffic per 20 forward-dynamics evaluations; HBM fraction reported because north_star asks for it"},
         }
+    if rank == 0 and args.full:
+        per_env = algo_bytes_per_env_step(env.model.c)
+        algo_bytes = per_env * n
+        achieved = algo_bytes / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else None
+        pmc = pmc_counters(env_id, n)
+        live, live_note = (None, "disabled (--no-live-pmc)") if (args.no_live_pmc or world > 1) else live_pmc_traffic(args)
+        traffic = pmc_traffic(live) if live else pmc_traffic(pmc)
+        traffic_source = live_note if live else (f"fallback ({live_note}): " + pmc.get("_file", "none committed for this workload") +
+                                                 ": FETCH_SIZE + WRITE_SIZE (KB) of the committed rocprofv3 --pmc passes of this command, bytes per launch")
+        kernel = {1: "ant_step_kernel", 0: "planar_step_kernel", 2: "swimmer_step_kernel"}[robot]
+        out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                          "frac": (achieved / HBM_PEAK_GBS) if achieved else None, "traffic": traffic,
+                          "kernel": kernel, "kernel_ms": kernel_ms, "kernel_ms_per_rank": kernel_ms_ranks,
+                          "kernel_ms_source": "HIP event pairs on the kernel's stream around every %d-th launch of the timed region (mz_last_kernel_ms)" % ev_stride,
+                          "algorithmic_bytes_per_launch": algo_bytes,
+                          "algorithmic_bytes_per_env_step": per_env,
+                          "traffic_source": traffic_source,
+                          "traffic_over_algorithmic": (traffic / algo_bytes) if traffic else None,
+                          "traffic_lower": pmc_traffic(live or pmc, corrected=False) if traffic else None,
+                          "traffic_definition": "v2 (since round 5): 2 x FETCH_SIZE + WRITE_SIZE, the guide's gfx950 correction; the lines of rounds 1-4 carried "
+                                                "v1 = FETCH_SIZE + WRITE_SIZE, which is this line's traffic_lower — compare like with like",
+                          "traffic_note": "traffic = 2 x FETCH_SIZE + WRITE_SIZE (gfx950: FETCH_SIZE counts data reads at half their bytes — calibrated for this "
+                                          "kernel's access widths, tools/fetch_calib.hip — but instruction fetch in full: an upper bound); traffic_lower = FETCH_SIZE + WRITE_SIZE",
+                          "traffic_fetch_bytes": ((live or pmc).get("FETCH_SIZE", 0.0) * 1024.0) if traffic else None,
+                          "traffic_write_bytes": ((live or pmc).get("WRITE_SIZE", 0.0) * 1024.0) if traffic else None,
+                          "note": "latency/VALU-bound path (SURVEY 8d): ~0.5 KB of HBM traffic per 20 forward-dynamics evaluations; HBM fraction reported because north_star asks for it"}
         rv = valu_roofline(pmc, kernel_ms, n * args.steps / (kernel_ms * 1e-3 * args.steps) if kernel_ms > 0 else 0.0, env_id, f64=robot != 1)
         if rv is not None:
             out["roofline_valu"] = rv
@@ -469,6 +524,7 @@ def main():
             out["without_allgather"] = no_gather  # same ranks, same steps, collective off (with / without)
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(env.model, env_id, n, env.action_space.low.astype("float64"), env.action_space.high.astype("float64"))
+    if rank == 0:
         print(json.dumps(out), flush=True)
     env.close()
     if world > 1:

@@ -107,7 +107,7 @@ if rank == 0:
 """
 
 
-def test_two_ranks_nccl():
+def test_two_ranks_nccl(tmp_path):
     """the first time TWO GPUs are visible this runs instead of skipping — two processes, one per GPU, backend "nccl"
     (RCCL over xGMI): rank-local records arrive in every rank's gathered tensor, and the sharded run equals the unsharded one bit for
     bit; then `bench.py --gpus 2` itself (real nccl, gather on / off pair in its JSON line).  One-GPU boxes skip (the same code path
@@ -124,8 +124,7 @@ def test_two_ranks_nccl():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     if not two:
         env["MZ_TEST_SINGLE_GPU"] = "1"  # rehearse the very script on the one GPU (gloo), so that its first real run is not its first run
-    script = os.path.join(ROOT, "gpurun_out", "_two_ranks_nccl.py")
-    os.makedirs(os.path.dirname(script), exist_ok=True)
+    script = str(tmp_path / "_two_ranks_nccl.py")
     with open(script, "w") as f:
         f.write(TWO_RANK_SCRIPT % dict(root=ROOT))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", str(port), script]
@@ -133,8 +132,9 @@ def test_two_ranks_nccl():
     assert out.returncode == 0 and "TWO_RANKS_NCCL_OK" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
     if not two:
         pytest.skip("the nccl leg needs two visible GPUs (the two-rank script itself was rehearsed on this GPU over gloo: passed)")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "50", "--warmup", "10", "--no-cpu-baseline", "--no-live-pmc",
-                          "--sustained", "0"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "50", "--warmup", "10", "--full", "--no-cpu-baseline",
+                          "--no-live-pmc", "--sustained", "0"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["value"] > 0 and line["scaling"] == "weak"
+    assert line["without_allgather"]["value"] > 0

@@ -9,14 +9,14 @@ cd $GRAFT_REPO_ROOT
 out=gpurun_out/evidence_$tag
 mkdir -p $out
 if [[ $part == *a* ]]; then
-  python bench.py > $out/bench_line.json 2> $out/bench_line.err
+  python bench.py --full > $out/bench_line.json 2> $out/bench_line.err
   python bench.py --steps 20 --warmup 5 > $out/bench_line_driver_like.json 2>/dev/null
   for w in "AntUMaze-v0 4096" "PointUMaze-v0 4096" "AntPush-v0 2048" "Ant4Rooms-v0 4096" "SwimmerUMaze-v0 4096" "AntUMaze-v0 8192"; do
     set -- $w
     tools/profile.sh $tag $1 $2 > $out/profile_$1_$2.log 2>&1
     python tools/pmc_summary.py $tag $1 $2 > $out/pmc_summary_$1_$2.log 2>&1
     rm -rf gpurun_out/prof_${tag}_$1_$2  # the raw rocprofv3 output (tens of MiB per workload): only what pmc_summary.py kept travels back
-    [ "$w" != "AntUMaze-v0 4096" ] && python bench.py --no-cpu-baseline --env $1 --envs $2 > $out/bench_line_$1_$2.json 2>/dev/null
+    [ "$w" != "AntUMaze-v0 4096" ] && python bench.py --full --no-cpu-baseline --env $1 --envs $2 > $out/bench_line_$1_$2.json 2>/dev/null
   done
   cp -r profiles/$tag $out/profiles_$tag
   python tools/phase_profile.py 16 2>/dev/null > $out/phase_cycles.txt
@@ -31,7 +31,7 @@ if [[ $part == *b* ]]; then
   bash tools/gpu_other_configs.sh > /dev/null 2>&1; cp gpurun_out/other_configs.txt $out/
   python tools/general_engine_bench.py 2048 100 2>/dev/null | grep -v Warning > $out/general_engine.txt
   for a in "--envs 8192" "--envs 16384" "--envs 32768" "--env PointUMaze-v0 --envs 8192" "--env PointUMaze-v0 --envs 16384" "--env AntPush-v0 --envs 4096" "--env AntPush-v0 --envs 8192"; do
-    python bench.py --steps 300 --warmup 10 --no-cpu-baseline --no-live-pmc --sustained 0 $a 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%-62s %8.3f M env-steps/s   kernel %.4f ms   flagged envs %d' % (d['metric'][34:], d['value']/1e6, d['roofline']['kernel_ms'], d['config']['bad_envs']))"
+    python bench.py --full --steps 300 --warmup 10 --no-cpu-baseline --no-live-pmc --sustained 0 $a 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%-62s %8.3f M env-steps/s   kernel %.4f ms   flagged envs %d' % (d['metric'][34:], d['value']/1e6, d['roofline']['kernel_ms'], d['config']['bad_envs']))"
   done > $out/batch_sweep.txt
   cat $out/soak.txt $out/other_configs.txt $out/batch_sweep.txt
 fi
