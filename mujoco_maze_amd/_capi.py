@@ -11,7 +11,7 @@ from mujoco_maze_amd.model import MzModel
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB_PATH = os.path.join(_HERE, "csrc", "libmazestep.so")
-# A/B timing of experiment builds (tools/exp_*.sh) only: the override is announced on stderr when the library is loaded and
+# A/B timing of a developer library (`make dev` / `make dev1`) or of a library built from another commit only: the override is announced on stderr when the library is loaded and
 # recorded in bench.py's JSON line (config.library), so a stale variable cannot swap the stepper silently
 # — and it is honoured only together with MZ_DEBUG=1 (a developer's shell), never on its own
 LIB_PATH = (os.environ.get("MZ_LIBMAZESTEP_EXPERIMENT") if os.environ.get("MZ_DEBUG") == "1" else None) or DEFAULT_LIB_PATH

@@ -88,7 +88,7 @@ struct AntDims {
   // NB = 1: 32 since round 5 (40 before) — the block's own contacts are merged entries now (a block on the floor against two walls: 3,
   // not 12), and 32 slots make an env's LDS block 9.9 KB: FOUR 16-lane waves (16 envs) fit a CU's 160 KB, so that batches beyond
   // 2048 envs run the one-block ant at 16 lanes per env in one round (ant_kernels.hip ant_lanes; AntPush 4096 envs 5.4 -> 8.6 M
-  // env-steps/s).  Soak at 32 slots: 2 x (61 M + 15 M) env-steps of AntPush / AntFall, no CONTACT_OVERFLOW (tools/exp_push_nc.sh).
+  // env-steps/s).  Soak at 32 slots: 2 x (61 M + 15 M) env-steps of AntPush / AntFall, no CONTACT_OVERFLOW.
   static constexpr int NGEOM = 13 + NMOV;  // contact enumerators: movable bodies first, then the 13 robot geoms
   static constexpr int NHESS = NH * NH + 8 * NH + 12;
   static constexpr int NTRI = NH * (NH + 1) / 2;
@@ -863,9 +863,6 @@ MZ_HD void capsule_box_search(const float* cl, const float* h, float hl, const f
 // sphere / capsule (centre ctr, axis ax = the capsule's from -> to direction, half length hl, radius r; torso-relative) against an
 // axis-aligned box (centre bc torso-relative, half sizes bs): up to two sphere-box contacts (mjc_CapsuleBox), normal from the
 // robot geom to the box
-#if defined(MZ_EXP_STAMPS) && defined(__HIPCC__)
-__device__ unsigned mz_exp_general_runs;  // (experiment build) capsule-box tests that did not qualify for the face case
-#endif
 template <class Emit>
 MZ_HD void round_vs_box(bool sphere, const float* ctr, const float* ax, float hl, float r, const float* bc, const float* bs,
                         float margin, int kind, int blk, Emit&& emit) {
@@ -874,9 +871,6 @@ MZ_HD void round_vs_box(bool sphere, const float* ctr, const float* ax, float hl
   ContactGeo cg;
   cg.kind = kind; cg.blk = blk; cg.other = 0;
   cg.hint[0] = cg.hint[1] = cg.hint[2] = 0.f;
-#ifdef MZ_EXP_SPHEREONLY  // timing experiment (wrong physics): a capsule is tested as a sphere at its centre
-  sphere = true;
-#endif
   if (sphere) {
     if (sphere_aabb(cl, r, bs, margin, &dist, pos, n) && dist < margin) {
       cg.dist = dist;
@@ -893,14 +887,13 @@ MZ_HD void round_vs_box(bool sphere, const float* ctr, const float* ax, float hl
     em[k] = cl[k] - hh[k]; ep[k] = cl[k] + hh[k];
     in_m = in_m && fabsf(em[k]) <= bs[k]; in_p = in_p && fabsf(ep[k]) <= bs[k];
   }
-#ifndef MZ_EXP_NOFACEPATH
   // The FACE case, written out (round 5): both ends of the axis segment beyond the same face of the box and inside its other two
   // slabs — a leg against a wall, which is nearly every wall test an ant ever causes (maze cells are metres wide, capsules
   // centimetres; a concave corner is two boxes, one face each).  Then everything the general code below works out is known: the closest
   // point of the segment is the end nearer to the face (the first end on a tie), the feature is that face, the second support point is
   // the other end (it stays over the face: frac = 1), and each of the two sphere tests sees a centre outside along that one axis —
   // depth = |coordinate| - half size - radius, normal = minus the axis.  Same contacts, same order; ~60 instructions instead of
-  // ~1000.  Why it matters: per-wave start / end stamps of the product kernel (tools/exp_launch_stamps.py) put ONE wall test at 1.9 us
+  // ~1000.  Why it matters: per-wave start / end stamps of the product kernel put ONE wall test at 1.9 us
   // of its wave — 4 650 cycles — and the slowest wave of a launch at 24 of them per step: 46 of the 61 us it runs longer than the
   // mean wave.  (Round 4 tried a fast path for the closest-point search alone and lost 1 %: the rest of the test still ran.)
   {
@@ -936,11 +929,7 @@ MZ_HD void round_vs_box(bool sphere, const float* ctr, const float* ax, float hl
       return;
     }
   }
-#endif
-#if defined(MZ_EXP_STAMPS) && defined(__HIP_DEVICE_COMPILE__)
-  atomicAdd(&mz_exp_general_runs, 1u);
-#endif
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(MZ_EXP_NOLAUNDER)
+#if defined(__HIP_DEVICE_COMPILE__)
   // Keep the general case's arithmetic BEHIND its branch (round 5): the wall loop of the forward pass calls this once per candidate
   // cell, and everything below that does not depend on the cell — reciprocals of the axis, its products, two dozen comparison masks —
   // was hoisted in front of that loop by the compiler, i.e. executed by every geom that reached the loop at all, 98.6 % of which
@@ -973,11 +962,7 @@ MZ_HD void round_vs_box(bool sphere, const float* ctr, const float* ax, float hl
     clface = nout == 1 ? lastout : -1;
     cledge = inaxis; boxpos = pin;
     // the segment runs through the box with both ends outside: MuJoCo's answer is its search order's
-#ifdef MZ_EXP_NOSEARCH  // timing experiment (wrong physics): never run the twelve-edge search
-    if (false) {
-#else
     if (nout == 0) {
-#endif
       corner = 0;
       float clb[3] = {cl[0], cl[1], cl[2]}, hb[3] = {h[0], h[1], h[2]};
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -990,11 +975,7 @@ MZ_HD void round_vs_box(bool sphere, const float* ctr, const float* ax, float hl
       capsule_box_search(clb, hb, hl, bs, &t, &type, &clface, &cledge, &corner, &boxpos);
     }
   }
-#ifdef MZ_EXP_NOSECOND  // timing experiment (wrong physics): no second support point
-  const float second = 0.f;
-#else
   const float second = capsule_box_second(cl, h, bs, t, type, clface, cledge, corner, boxpos);
-#endif
   for (int pass = 0; pass < 2; pass++) {
     if (pass == 1 && !(fabsf(second) > 1e-12f)) break;
     const float tt = t + (pass ? second : 0.f);

@@ -33,12 +33,6 @@
 #pragma once
 #include "ant_newton_rows.h"
 
-// experiment build -DMZ_EXP_SUBTICK2: the forward pass's timers all book on slot 3, slots 0 .. 2 time the solver's set-up (ant_newton_rows.h)
-#ifdef MZ_EXP_SUBTICK2
-#define MZ_FT(k) 3
-#else
-#define MZ_FT(k) (k)
-#endif
 namespace rows {
 
 template <int J>
@@ -152,9 +146,6 @@ __device__ __forceinline__ void robot_geom_contacts(const AntDev& K, const AntU&
     const uint32_t cols2 = ((j0 >= 0 && j0 < z.cols) ? 1u << j0 : 0u) | ((j1 != j0 && j1 >= 0 && j1 < z.cols) ? 1u << j1 : 0u);
     if (!(rows2 & cols2)) return;
   }
-#ifdef MZ_EXP_STAMPS  // cycles the wave spends between here and the end of the narrow phase (booked by the first active lane, on its env)
-  const unsigned long long exp_t0 = __builtin_amdgcn_s_memtime();
-#endif
   // the surviving boxes as bit sets (bit 4 (i - i0) + (j - j0): up to 8 x 4 cells, row-major = MuJoCo's geom order of the maze's
   // boxes; per cell the platform before the wall), then one cell per pass — lanes with one candidate each meet in the same pass
   // instead of each waiting for the other's position in a loop nest
@@ -201,34 +192,13 @@ __device__ __forceinline__ void robot_geom_contacts(const AntDev& K, const AntU&
       if (candidate(i, j, 1)) candw |= 1u << (4 * (i - i0) + (j - j0));
       if (elevated && candidate(i, j, 0)) candp |= 1u << (4 * (i - i0) + (j - j0));
     }
-#ifdef MZ_EXP_NOWALL  // timing experiment (wrong physics): no wall narrow phase at all
-  candw = 0u; candp = 0u;
-#endif
-#ifdef MZ_EXP_STAMPS  // cycles of the candidate scan alone (same booking as below)
-  {
-    const unsigned long long act = __ballot(1);
-    if ((int)(threadIdx.x & 63) == __ffsll((long long)act) - 1) atomicAdd(const_cast<int*>(&s.bkey[3]), (int)(__builtin_amdgcn_s_memtime() - exp_t0));
-  }
-#endif
   while (candw | candp) {
-#ifdef MZ_EXP_STAMPS  // (NB = 0 only: bkey is free there) narrow-phase runs of this env over the step
-    atomicAdd(const_cast<int*>(&s.bkey[0]), 1);
-#endif
     const int b = __ffs((int)(candw | candp)) - 1;
     const unsigned bit = 1u << b;
     if (candp & bit) test(i0 + (b >> 2), j0 + (b & 3), 0);
     if (candw & bit) test(i0 + (b >> 2), j0 + (b & 3), 1);
     candw &= ~bit; candp &= ~bit;
-#ifdef MZ_EXP_ONECAND  // timing experiment (wrong physics): at most one narrow-phase run per geom — what would dealing the candidates to idle lanes save?
-    candw = 0u; candp = 0u;
-#endif
   }
-#ifdef MZ_EXP_STAMPS
-  {
-    const unsigned long long act = __ballot(1);
-    if ((int)(threadIdx.x & 63) == __ffsll((long long)act) - 1) atomicAdd(const_cast<int*>(&s.bkey[2]), (int)(__builtin_amdgcn_s_memtime() - exp_t0));
-  }
-#endif
 }
 
 }  // namespace rows
@@ -270,11 +240,7 @@ __device__ __forceinline__ float ant_forward_rows(const DevCtx<G, PROF>& cx_step
   // scratch, stored by every wave and re-read per evaluation (PMC, 8192 envs: WRITE_SIZE 14.5 MB per launch against 2.8 MB of
   // algorithmic writes).  The opaque lane index keeps the loads inside the evaluation (they are loop-invariant otherwise).
   DevCtx<G, PROF> cx = cx_step;
-#ifdef MZ_EXP_LCRELOAD  // A / B build: the one-wave kernel as well
-  if (true) {
-#else
   if (cx_step.mfma) {
-#endif
     int ll = cx_step.l;
     asm volatile("" : "+v"(ll));
     cx.l = ll;
@@ -342,7 +308,7 @@ __device__ __forceinline__ float ant_forward_rows(const DevCtx<G, PROF>& cx_step
   for (int k = 0; k < 3; k++) { com[k] = role(com1[k], com2[k], com0[k], 0.f); w[k] = role(w1[k], w2[k], w0[k], 0.f); }
   const int cls = j == 0 ? 2 : (j == 1 ? 3 : (j == 2 ? 1 : 0));
   const float hlen = cx.lc[LC_HLEN], rad = cx.lc[LC_RAD];
-  cx.tick(s, MZ_FT(0));
+  cx.tick(s, 0);
   if constexpr (NB == 1) { if (p == 0) { s.cz = cz; s.con_over = 0; } }  // (the block's enumerators below read them)
   // ---- C: contacts of the own geom, staged in registers (the first three; more: the env takes the fall-back below).  Right after the
   // kinematics: the narrow phase is the branchiest code of the evaluation, and here little else is live across it
@@ -359,9 +325,6 @@ __device__ __forceinline__ float ant_forward_rows(const DevCtx<G, PROF>& cx_step
       nfound++;
     });
   }
-#ifdef MZ_EXP_SUBTICK  // experiment build: the robot geoms' narrow phase is booked on slot 0, the block's enumerators on slot 3
-  cx.tick(s, MZ_FT(0));
-#endif
   // the movable block's own enumerators (floor corners | the 3 x 3 cells under it, platform and wall each | slide limits), one per
   // lane of the group's first eleven, staged in the cY block as in the lane-group path; their contacts take the first slots
   int nblk = 0, nrep = 0;  // nrep: contact points folded into merged entries (for the count MuJoCo would report)
@@ -375,13 +338,8 @@ __device__ __forceinline__ float ant_forward_rows(const DevCtx<G, PROF>& cx_step
     // reads nothing else — is a function of the block's position and the maze alone; the rows' velocity terms are rebuilt from the
     // staged geometry at every evaluation as before.  An env that took the lane-group fall-back (its staging was overwritten) or whose
     // enumeration overflowed re-enumerates.
-#ifndef MZ_EXP_NOBLOCKCACHE
     const int k0 = __float_as_int(s.qpos[15]), k1 = __float_as_int(s.qpos[16]), k2 = __float_as_int(s.qlo[2]), k3 = __float_as_int(s.qlo[3]);
     const bool staged = s.bkey[4] != 0 && s.bkey[0] == k0 && s.bkey[1] == k1 && s.bkey[2] == k2 && s.bkey[3] == k3;
-#else
-    const int k0 = 0, k1 = 0, k2 = 0, k3 = 0;
-    const bool staged = false;
-#endif
     if (cx.any(!staged)) {
       cx.sync();  // (every lane has read the key)
       if (!staged) { MZ_FOR(e, D::NMOV) con_enum_item<NB, true>(K, s, e); }
@@ -399,16 +357,13 @@ __device__ __forceinline__ float ant_forward_rows(const DevCtx<G, PROF>& cx_step
       for (int i = 0; i < mine; i++) { const int slot = before + i; if (slot < NC) { s.csrc[slot] = MZ_STAGE_OF(NB) * cx.l + i; s.cleg[slot] = -1; s.ccls[slot] = -1; } }
     if (nblk > NC) nblk = NC;
   }
-#ifdef MZ_EXP_SUBTICK
-  cx.tick(s, 3);
-#endif
   const bool over = cx.gany(nfound > 3) || bover;
   // compact slots in geom order (torso, then per leg: welded capsule, aux, ankle): one packed-count butterfly
   const int rank = j == 3 ? 0 : 1 + 3 * l + (j == 2 ? 0 : j + 1);
   const unsigned word = rsum_u((unsigned)(nfound > 3 ? 3 : nfound) << (2 * rank));
   const int off = nblk + (int)sum2bit(word & ((1u << (2 * rank)) - 1u));
   int ncon = nblk + (int)sum2bit(word);
-  cx.tick(s, MZ_FT(2));
+  cx.tick(s, 2);
 
   // ---- I: spatial inertia of the own body about the torso origin (inertia_item); composites
   float cin[10];
@@ -513,7 +468,7 @@ __device__ __forceinline__ float ant_forward_rows(const DevCtx<G, PROF>& cx_step
       if (p >= 14) qfs = ax == 2 ? K.block_mass * K.gz : 0.f;
     }
   }
-  cx.tick(s, MZ_FT(1));
+  cx.tick(s, 1);
   if (!over) {
     if (ncon > NC) { ncon = NC; if (p == 0) s.status |= MZ_STATUS_CONTACT_OVERFLOW; }
     if (p == 0) { s.ncon = ncon; s.nblkcon = nblk; s.ncon_true = ncon + nrep; }
@@ -533,9 +488,6 @@ __device__ __forceinline__ float ant_forward_rows(const DevCtx<G, PROF>& cx_step
     }
     cx.sync();
   }
-#ifdef MZ_EXP_STAMPS
-  if (over && p == 0) s.bkey[1] += 1;
-#endif
   if (cx.any(over)) {  // (compiled out as a timing experiment, round 5: no faster — nothing of this block is paid by the waves that skip it)
     // Fall-back (rare: some geom of some env of this wave found more than three contacts): publish the kinematics the lane-group
     // contact code of ant_dyn.h reads, and let the envs concerned enumerate the two-pass way.
@@ -629,22 +581,10 @@ __device__ __forceinline__ void ant_mj_step_rows(const DevCtx<G, PROF>& cx, cons
       integrate(aw * qvel);
       qvel = x0v + h * aw * qacc;
       if (isdof) s.qvel[i] = qvel;
-#ifdef MZ_EXP_RK4TICK  // (tools/tail_phases.py: what the "rk4" timer slot of the slowest waves is made of)
-      cx.tick(s, 13);
-#endif
       cx.sync();
-#ifdef MZ_EXP_RK4TICK
-      cx.tick(s, 14);
-#endif
     }
   }
   integrate(accv);
   if (isdof) s.qvel[i] = x0v + h * accf;
-#ifdef MZ_EXP_RK4TICK
-  cx.tick(s, 13);
-#endif
   cx.sync();
-#ifdef MZ_EXP_RK4TICK
-  cx.tick(s, 14);
-#endif
 }

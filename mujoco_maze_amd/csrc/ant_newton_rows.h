@@ -532,13 +532,8 @@ __device__ __forceinline__ void block_rows_direct(const AntDev& K, const AntScra
 // u = v = 0; a dof without an active limit row holds lsign = lD = 0; a row without contact C holds zero columns): as `if`s they are
 // exec-mask regions — two scalar instructions, a branch and the exec hazards, per region — around a handful of vector instructions
 // that the wave executes anyway as long as ONE of its lanes needs them.  With one wave per SIMD nobody fills those bubbles: the
-// conditions are gone (the arithmetic adds its zeros), round 4: 0.2941 -> 0.2813 ms.  MZ_IF_OWNER marks the places (-DMZ_EXP_BRANCHY
-// brings the `if`s back for an A / B run).
-#ifdef MZ_EXP_BRANCHY
-#define MZ_IF_OWNER(c) if (c)
-#else
+// conditions are gone (the arithmetic adds its zeros), round 4: 0.2941 -> 0.2813 ms.  MZ_IF_OWNER marks the places.
 #define MZ_IF_OWNER(c) if (true)
-#endif
 template <int NB, int G, bool PROF, bool WR = false, class SCR>
 __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, const AntDev& K, SCR& s, bool compare,
                                                     const float (&Mrow)[14 + 2 * NB], const float qfs, const float (&Sax)[6], const float hq, const float hv) {
@@ -561,11 +556,7 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
   constexpr int BW = WR ? 16 : G;                 // lanes the block's entries are dealt over
   constexpr int MB = NB ? (WR ? 1 : (D::NC + G - 1) / G) : 0;
   constexpr int MA = NB ? 2 : 1;                   // robot contacts per lane of the row (16 MA in all; an ant on its back next to the block: > 16)
-#ifdef MZ_EXP_NOREFINE
-  constexpr bool REFINE = false;
-#else
   constexpr bool REFINE = NB == 1;                 // iterative refinement of an accepted unit step (below): the stiff (solimp .995) mazes
-#endif
   const int r = cx.l & 15;                       // position of this lane (rows::pos2dof); beyond NR: spare lanes (zero rows, never pivots)
   const bool isdof = r < NR, ishinge = (r & 3) < 2 && r < 14;
   const int leg = r >> 2, d = r & 1;              // hinge lanes: own leg, 0 hip / 1 ankle
@@ -614,9 +605,6 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
     if (isdof) s.qas[ri] = qas;
   }
   const float warm = isdof ? s.warm[ri] : 0.f;  // later evaluations start from the previous evaluation's solution
-#ifdef MZ_EXP_SUBTICK2
-  cx.tick(s, 0);  // limit row, qacc_smooth where needed
-#endif
   // own robot contact: 3 x (NHC + 2) Jacobian rows stay in LDS (row-major, read as needed); constants in registers
   float cD[MA], ar[MA][3];
   float wr[MA][3][6];  // WR: the own contacts' three wrenches each
@@ -661,9 +649,6 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
       for (int a = 0; a < 3; a++) ar[m][a] = iscon[m] ? s.caref[cr[m]][a] : 0.f;
     }
   }
-#ifdef MZ_EXP_SUBTICK2
-  cx.tick(s, 1);  // the slots' records
-#endif
   // own block contacts (NB = 1): slots cx.l + m G < nB
   float bj[MB ? MB : 1][3][2], bar[MB ? MB : 1][3], bD[MB ? MB : 1], bu[MB ? MB : 1][3], bv[MB ? MB : 1][3];
   if constexpr (NB == 1) {
@@ -805,9 +790,6 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
       for (int a = 0; a < 3; a++) o[m][a] = bj[m][a][0] * b0 + bj[m][a][1] * b1;
   };
 
-#ifdef MZ_EXP_SUBTICK2
-  cx.tick(s, 2);  // block rows, own columns / rows of the contacts
-#endif
   // ---- initial guess
   float qacc = warm;
   if (compare) {  // MuJoCo's rule on the first evaluation of a step: the better of warm start and qacc_smooth, by cost
@@ -1077,7 +1059,7 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
     // taken as exact when the active set does not change — true of the arithmetic, not of an fp32 elimination: with every geom at
     // solimp .995 (maze_env.py:108-112) H = M + J^T D J has a condition number of 1e3 .. 1e4, and the step's error is relative to
     // the WHOLE step — hinge accelerations of thousands of rad/s^2 — so the torso's angular entries (tens of rad/s^2) came out 3e-4
-    // off, 4e-6 in their velocity per evaluation: the whole of AntPush's error tail (tools/exp_forward_err.py; the float64 oracle,
+    // off, 4e-6 in their velocity per evaluation: the whole of AntPush's error tail (the float64 oracle,
     // fed inputs perturbed at fp32 round-off, moves by 1e-5 at most).  The residual gradient at qacc + search (same active set, the
     // affine quantities follow the step) goes through the SAME elimination — its multipliers were kept (resolve_rows) — and the
     // correction is added: ~120 instructions, no second Hessian.
@@ -1125,12 +1107,6 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
         if (exact && !done) qacc += corr;
       }
     }
-#ifdef MZ_EXP_TRACE  // developer aid (tools/replay_trace.py): one line per Newton iteration of the first env of a wave
-    {
-      const float g14 = NR > 14 ? bcast<14>(g) : 0.f, g15 = NR > 14 ? bcast<15>(g) : 0.f, s14 = NR > 14 ? bcast<14>(search) : 0.f, s15 = NR > 14 ? bcast<15>(search) : 0.f;
-      if (cx.l == 0) printf("TRACE it %d ncon %d nB %d gnorm %g anorm %g gblk %g %g sblk %g %g changed %d alpha %g sn %g qn %g exact %d done %d u %g %g %g v %g %g %g D %g\n", it, ncon, nB, gnorm, anorm, g14, g15, s14, s15, (int)changed, alpha, sn, qn, (int)exact, (int)done, u[0][0], u[0][1], u[0][2], v[0][0], v[0][1], v[0][2], cD[0]);
-    }
-#endif
     if (exact && ant_u(cx, K).trust_exact) done = true;
     if (changed && alpha * alpha * sn <= MZ_NEWTON_STALL * MZ_NEWTON_STALL * qn) done = true;  // stationary at fp32 resolution (ant_dyn.h ant_solve)
     cx.tick(s, 7);
@@ -1141,9 +1117,6 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
     s.iters = it;
     if (it >= ant_u(cx, K).max_iter && !done) s.status |= MZ_STATUS_SOLVER_MAXITER;
     if constexpr (PROF) s.prof[15] += (unsigned)it;  // (part 2 of the scratch block: instrumented builds only)
-#ifdef MZ_EXP_STAMPS  // (tools/exp_launch_stamps.py) lock-step iterations of the wave | contact-evaluations of this env, over the step
-    s.red[2] += (float)it; s.red[3] += (float)ncon;
-#endif
   }
   cx.sync();
   cx.tick(s, 8);

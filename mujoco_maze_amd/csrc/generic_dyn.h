@@ -238,20 +238,12 @@ struct alignas(16) GenScratch {
   double lsign[GN_NL], lD[GN_NL], laref[GN_NL], ljar[GN_NL], ljv[GN_NL];
   double grad[GN_NV], search[GN_NV], Mx[GN_NV], Ms[GN_NV], red[8];
   double ctmp[GN_NV], cdinv[GN_NV];  // gen_chol_solve: the column in flight, reciprocals of the factor's diagonal
-#ifdef MZ_EXP_GENPROF
-  unsigned long long prof[20], prof_t0;  // phase timers of the instrumented build (tools/exp_general_prof.sh)
-#endif
   // LAST: the contacts' Jacobian rows [contact][normal, mu t1, mu t2] at a row stride of the MODEL's nv (gen_cj).  The step kernel
   // allocates the block only as far as 3 nv GN_NC doubles of it (gen_scratch_bytes): 30 KB for a 20-dof model instead of 37 — what
   // keeps two envs per CU up to 22 dofs (generic_kernels.hip)
   double cJf[GN_NC * 3 * GN_NV];
 };
 MZ_HD size_t gen_scratch_bytes(int nv) { return (offsetof(GenScratch, cJf) + sizeof(double) * 3 * (size_t)nv * GN_NC + 15) / 16 * 16; }
-#if defined(MZ_EXP_GENPROF) && defined(__HIP_DEVICE_COMPILE__)
-#define GEN_TICK(id) do { if (cx.lane0() == 0) { unsigned long long now_ = __builtin_amdgcn_s_memtime(); s.prof[id] += now_ - s.prof_t0; s.prof_t0 = now_; } } while (0)
-#else
-#define GEN_TICK(id) do {} while (0)
-#endif
 
 MZ_HD double* gen_cj(GenScratch& s, int nv, int k, int a) { return s.cJf + (size_t)(3 * k + a) * nv; }
 MZ_HD const double* gen_cj(const GenScratch& s, int nv, int k, int a) { return s.cJf + (size_t)(3 * k + a) * nv; }
@@ -1352,7 +1344,6 @@ MZ_HD void gen_solve(const C& cx, const GenDev& K, GenScratch& s) {
   bool done = false;
   int it = 0;
   double prev_cost = cw < cs ? cw : cs;
-  GEN_TICK(7);
   while (!done && it < K.max_iter) {
     MZ_FOR(i, nv) s.Mx[i] = gd_dotn_diff(s.M[i], s.qacc, s.qas, nv);
     MZ_FOR(k, ncon) {  // a contact's three residuals, and from them its gradient and Hessian weights — once, not once per entry that uses them
@@ -1363,7 +1354,6 @@ MZ_HD void gen_solve(const C& cx, const GenDev& K, GenScratch& s) {
     }
     MZ_FOR(l, nlim) s.ljar[l] = s.lsign[l] * s.qacc[s.ldof[l]] - s.laref[l];
     cx.sync();
-    GEN_TICK(8);
     double gpart = 0.0;
     MZ_FOR(i, nv) {
       double g = s.Mx[i];
@@ -1373,7 +1363,6 @@ MZ_HD void gen_solve(const C& cx, const GenDev& K, GenScratch& s) {
       s.grad[i] = g; gpart += g * g;
     }
     const double gn = sqrt(cx.gsum(gpart));
-    GEN_TICK(9);
     if (K.inv_scale * gn < K.tol) break;
     // H = M + J^T W J: the lower triangle only (all the factorisation reads).  Rows r and nv - 1 - r together hold nv + 1 entries:
     // (nv + 1) * ceil(nv / 2) items cover the triangle (nv odd: the middle row twice, same values)
@@ -1392,11 +1381,9 @@ MZ_HD void gen_solve(const C& cx, const GenDev& K, GenScratch& s) {
       s.H[i][j] = acc;
     }
     cx.sync();
-    GEN_TICK(10);
     MZ_FOR(i, nv) s.search[i] = -s.grad[i];
     cx.sync();
     const bool posdef = gen_chol_solve(cx, s, s.H, s.H, nv, s.search);
-    GEN_TICK(11);
     if (!posdef) { MZ_FOR(one, 1) s.status |= MZ_STATUS_BAD_STATE; break; }
     // line search on phi(alpha) = cost(qacc + alpha search): unit step when no row changes state, else safeguarded Newton on phi'
     MZ_FOR(i, nv) s.Ms[i] = gd_dotn(s.M[i], s.search, nv);
@@ -1430,14 +1417,12 @@ MZ_HD void gen_solve(const C& cx, const GenDev& K, GenScratch& s) {
       }
     }
     cx.sync();
-    GEN_TICK(12);
     if (!(alpha > 0.0)) break;
     MZ_FOR(i, nv) s.qacc[i] += alpha * s.search[i];
     cx.sync();
     it++;
     if (!changed) break;  // the unit Newton step stayed inside one active set: exact minimiser
     const double cnow = cost_at(s.qacc);
-    GEN_TICK(13);
     if (!(K.inv_scale * (prev_cost - cnow) > 0.0)) break;  // round-off floor
     prev_cost = cnow;
     if (it >= K.max_iter) { MZ_FOR(one, 1) s.status |= MZ_STATUS_SOLVER_MAXITER; }
@@ -1450,19 +1435,14 @@ MZ_HD void gen_solve(const C& cx, const GenDev& K, GenScratch& s) {
 template <class C>
 MZ_HD void gen_forward(const C& cx, const GenDev& K, GenScratch& s) {
   const mz_model& m = K.m;
-  GEN_TICK(15);
   MZ_FOR(one, 1) s.npool = 0;
   gen_kinematics(cx, K, s);
-  GEN_TICK(0);
   MZ_FOR(g, m.ngeom) gen_geom_item(K, s, g);
   MZ_FOR(j, m.njnt) gen_axis_item(K, s, j);
   MZ_FOR(b, m.nbody) if (b > 0) gen_inertia_item(K, s, b);
   cx.sync();
-  GEN_TICK(1);
   MZ_FOR(it, K.nitem) gen_collide_item(K, s, it);
-  GEN_TICK(2);
   gen_tree_passes(cx, K, s);
-  GEN_TICK(3);
   MZ_FOR(i, m.nv) gen_mass_item(K, s, i);
   MZ_FOR(b, m.nbody) gen_fluid_item(K, s, b);
   {
@@ -1480,20 +1460,16 @@ MZ_HD void gen_forward(const C& cx, const GenDev& K, GenScratch& s) {
     }
   }
   cx.sync();
-  GEN_TICK(4);
   MZ_FOR(i, m.nv) gen_force_item(K, s, i);
   MZ_FOR(e, m.nv * m.nv) { const int i = e / m.nv, j = e - m.nv * i; if (i < j) s.M[i][j] = s.M[j][i]; }  // gen_mass_item wrote the lower triangle
   MZ_FOR(item, 3 * s.ncon) gen_contact_row_item(K, s, item);
   cx.sync();
-  GEN_TICK(5);
   // qacc_smooth = M^-1 qfrc_smooth (H is free until the solver assembles the Hessian)
   MZ_FOR(i, m.nv) s.qas[i] = s.qfs[i];
   cx.sync();
   if (!gen_chol_solve(cx, s, s.M, s.H, m.nv, s.qas)) { MZ_FOR(one, 1) s.status |= MZ_STATUS_BAD_STATE; }
   cx.sync();
-  GEN_TICK(6);
   gen_solve(cx, K, s);
-  GEN_TICK(14);
 }
 
 // mj_integratePos of joint j (the joints are independent of each other: one lane each)

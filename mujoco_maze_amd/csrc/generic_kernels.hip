@@ -45,21 +45,9 @@ __global__ __launch_bounds__(64) void generic_step_kernel(const GenDev* __restri
   }
   for (int i = cx.l; i < nu; i += 64) L.io.act[i] = actions[(size_t)env * nu + i];
   if (cx.l == 0) { L.io.iout[2] = ((const int*)rec)[rec_t]; L.io.iout[3] = ((const int*)rec)[rec_t + 1]; }
-#ifdef MZ_EXP_GENPROF
-  if (cx.l == 0) { for (int k = 0; k < 20; k++) s.prof[k] = 0; s.prof_t0 = __builtin_amdgcn_s_memtime(); }
-#endif
   cx.sync();
   gen_env_step(cx, K, s, L.io.act, L.io.obs, &L.io.out[0], (uint8_t*)&L.io.iout[0], &L.io.iout[1], &L.io.out[1], &L.io.iout[2], env);
   cx.sync();
-#ifdef MZ_EXP_GENPROF
-  if (cx.l == 0 && blockIdx.x % 97 == 5) {
-    unsigned long long tot = 0;
-    for (int k = 0; k < 16; k++) tot += s.prof[k];
-    printf("GENPROF %d total %llu kin %llu items %llu collide %llu crb+rne %llu mass/compact/limits %llu force/rows %llu qas %llu | warmcost %llu Mx/cu %llu grad %llu H %llu chol %llu ls %llu cost %llu tail %llu | rk4/io %llu iters %d ncon %d\n",
-           (int)blockIdx.x, tot, s.prof[0], s.prof[1], s.prof[2], s.prof[3], s.prof[4], s.prof[5], s.prof[6], s.prof[7], s.prof[8], s.prof[9], s.prof[10], s.prof[11], s.prof[12],
-           s.prof[13], s.prof[14], s.prof[15], s.iters, s.ncon);
-  }
-#endif
   const uint8_t d = *(const uint8_t*)&L.io.iout[0];
   const int t_new = L.io.iout[2];
   uint32_t episode = (uint32_t)L.io.iout[3];

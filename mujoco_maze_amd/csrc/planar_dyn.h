@@ -20,12 +20,6 @@
 #pragma once
 #include "ant_dyn.h"    // MZ_FOR, HostCtx, maze_row
 #include "point_dyn.h"  // PointDev, point_detect, pt_impedance
-// Newton iterations of a solve that take the unit step before the exact line search takes over (round 5; measured on PointUMaze /
-// PointPush, tools/gpu_point.sh)
-#ifndef MZ_PL_UNIT_STEPS
-#define MZ_PL_UNIT_STEPS 5
-#endif
-
 template <int NB, int NS>
 struct PlanarDims {
   static_assert(NB == 0 || NS == 0, "no registered maze mixes movable blocks and object balls");
@@ -39,14 +33,6 @@ struct PlanarDims {
   static constexpr int NE = 18 + EPB * NB + NB * (NB - 1) / 2 + 11 * NS;
   static constexpr int NOBS = 7 + 3 * NB + 3 * NS;
 };
-
-// developer aid (tools/exp_build.sh PROF, tools/exp_point_prof.py): -DMZ_EXP_PROF builds an experiment library whose bare-Point kernel (point_bare.h) times its phases
-// with s_memtime (lane 0 of a group; planar_kernels.hip prints one workgroup's totals) — compiled out otherwise
-#if defined(MZ_EXP_PROF) && defined(__HIP_DEVICE_COMPILE__)
-#define MZB_TICK(id) do { if (cx.lane0() == 0) { unsigned long long now_ = __builtin_amdgcn_s_memtime(); s.prof[id] += now_ - s.prof_t0; s.prof_t0 = now_; } } while (0)
-#else
-#define MZB_TICK(id) do { } while (0)
-#endif
 
 template <int NB, int NS>
 struct alignas(16) PlanarScratch {  // (the bare Point, <0, 0>: point_bare.h)
@@ -465,9 +451,6 @@ MZP_HD void planar_contacts(const PointDev& P, const PlanarScratch<NB, NS>& s, i
       ct.b1 = 0; ct.b2 = -1; ct.cls = 0;
       emit(ct);
     } else {      // wall (geom1) vs arrow (geom2)
-#ifdef MZ_EXP_NOARROW
-      return;
-#endif
       // the arrow lies within its circumscribed circle: a cell farther than that from its centre cannot touch it
       const double ex = fmax(fabs(arrow[0] - wc[0]) - wh[0], 0.0), ey = fmax(fabs(arrow[1] - wc[1]) - wh[1], 0.0), rr = P.arr_rxy + pr.margin;
       if (ex * ex + ey * ey > rr * rr) return;
@@ -678,9 +661,6 @@ MZP_HD void planar_forward(const C& cx, const PointDev& P, PlanarScratch<NB, NS>
   cx.sync();
   MZ_FOR(i, NV) s.qacc[i] = s.qas[i];
   bool maybe = NB + NS > 0 || s.robot_near != 0;  // group-uniform
-#ifdef MZ_EXP_NOCOLLISION
-  maybe = false;
-#endif
   if (!cx.any(maybe)) { cx.sync(); return; }
   // ---- collision: count, prefix, fill
   MZ_FOR(e, NE) {
@@ -821,7 +801,7 @@ MZP_HD void planar_forward(const C& cx, const PointDev& P, PlanarScratch<NB, NS>
     changed = cx.gany(changed);
     double lo = 0.0, hi = -1.0, alpha = 1.0, prev_d2 = -1.0;
     double p1 = 0.0, p2 = 0.0;
-    const bool fast_now = it < P.unit_steps;  // (option "ls_fast_iterations"; default MZ_PL_UNIT_STEPS; custom tasks: 0, maze_env.py)
+    const bool fast_now = it < P.unit_steps;  // (option "ls_fast_iterations"; default 5, point_dyn.h; custom tasks: 0, maze_env.py)
     if (changed && !fast_now) { p1 = cx.gsum(p1p); p2 = cx.gsum(p2p); }
     for (int ls = 0; ls < 30 && changed && !fast_now; ls++) {  // (unit steps first: point_bare.h / ant_newton_rows.h)
       double d1 = 0.0, d2 = 0.0;
@@ -947,7 +927,6 @@ MZP_HD void planar_env_step(const C& cx, const PointDev& P, PlanarScratch<NB, NS
     cx.sync();
   }
   // maze_env.py:454-464: manual wall bounce on the robot's xy
-#ifndef MZ_EXP_NODETECT
   if (P.nseg > 0) {
     const double old_xy[2] = {s.old_xy[0], s.old_xy[1]}, new_xy[2] = {s.q[0], s.q[1]};
     double fin[2];
@@ -959,7 +938,6 @@ MZP_HD void planar_env_step(const C& cx, const PointDev& P, PlanarScratch<NB, NS
     }
     cx.sync();
   }
-#endif
   }
 }
 

@@ -65,9 +65,6 @@ struct alignas(16) PlanarScratch<0, 0> {
   int nstage, njobs, status;
   unsigned jmask;
   double wds[3];                  // qacc - qacc_smooth of the step's last evaluation: the next step's first solve starts from it (MuJoCo's qacc_warmstart; round 6: +1.7 %)
-#ifdef MZ_EXP_PROF
-  unsigned long long prof[12], prof_t0;
-#endif
   MZP_HD double* detect_buf() { return &stage[0].dist; }
   static constexpr int detect_buf_doubles = CAP * 8;
 };
@@ -173,10 +170,6 @@ MZP_HD void point_forward_bare(const C& cx, const PointDev& P, PlanarScratch<0, 
   // state that has moved by more than the slack sends the env to the exact per-stage test; everybody else is done
   bool near = maybe || fabs(q[0] - s.x0[0]) > MZ_PB_SLACK || fabs(q[1] - s.x0[1]) > MZ_PB_SLACK;
   if (cx.any(near)) near = near && point_near_wall3(P, q[0], q[1], P.reach);
-#ifdef MZ_EXP_NOCOLLISION
-  near = false;
-#endif
-  MZB_TICK(0);
   if (!cx.any(near)) return;
   // ---- collision, one pass: 9 arrow-cell enumerators first (they share their code), then 9 sphere-cell ones
   MZ_FOR(one, 1) { s.nstage = 0; s.njobs = 0; s.jmask = 0u; }
@@ -193,7 +186,6 @@ MZP_HD void point_forward_bare(const C& cx, const PointDev& P, PlanarScratch<0, 
         if (pl_sphere_box(c, P.sph_r, wh, margin, &dd, nrm) && dd < margin)
           pb_stage<C>(s, dd, q[0] + nrm[0] * (P.sph_r + 0.5 * dd), q[1] + nrm[1] * (P.sph_r + 0.5 * dd), nrm[0], nrm[1], nrm[2], -1.0);
       } else {       // wall cell (geom1) vs arrow (geom2, rotated about z by the heading)
-#ifndef MZ_EXP_NOARROW
         const double ex = fmax(fabs(ax - wcx) - wh[0], 0.0), ey = fmax(fabs(ay - wcy) - wh[1], 0.0), rr = P.arr_rxy + margin;
         if (ex * ex + ey * ey <= rr * rr) {
           const double wc[3] = {wcx, wcy, (double)z.center_z}, ac[3] = {ax, ay, P.arr_z}, ah[3] = {P.arr_hx, P.arr_hy, P.arr_hz};
@@ -210,7 +202,6 @@ MZP_HD void point_forward_bare(const C& cx, const PointDev& P, PlanarScratch<0, 
               }
             });
         }
-#endif
       }
     }
   }
@@ -293,7 +284,6 @@ MZP_HD void point_forward_bare(const C& cx, const PointDev& P, PlanarScratch<0, 
       }
     }
   }
-  MZB_TICK(1);
   int ncon = s.nstage;
   if (s.nstage > S::CAP || s.njobs > 4) { ncon = ncon > S::CAP ? S::CAP : ncon; MZ_FOR(one, 1) s.status |= MZ_STATUS_CONTACT_OVERFLOW; }
   if (!near) ncon = 0;
@@ -315,13 +305,9 @@ MZP_HD void point_forward_bare(const C& cx, const PointDev& P, PlanarScratch<0, 
     }
     cx.sync();
   }
-  MZB_TICK(3);
   // ---- Newton on the primal problem, exact line search (planar_forward's iteration; M = [m 0 -mcs; 0 m mcc; -mcs mcc izz])
   double a[3] = {qas[0] + wd[0], qas[1] + wd[1], qas[2] + wd[2]};
   bool done = ncon == 0;
-#ifdef MZ_EXP_NONEWTON
-  done = true;
-#endif
   int it = 0;
   while (cx.any(!done) && it < 50) {
     const double d0 = a[0] - qas[0], d1 = a[1] - qas[1], d2 = a[2] - qas[2];
@@ -401,10 +387,10 @@ MZP_HD void point_forward_bare(const C& cx, const PointDev& P, PlanarScratch<0, 
     }
     changed = cx.gany(changed);
     double lo = 0.0, hi = -1.0, alpha = 1.0, prev_d2 = -1.0;
-    // (round 5, as in the Ant's solvers — ant_newton_rows.h: the first MZ_PL_UNIT_STEPS iterations of a solve take the unit step when
+    // (round 5, as in the Ant's solvers — ant_newton_rows.h: the first "ls_fast_iterations" iterations of a solve take the unit step when
     // the active set changes, the exact search comes behind them: it buys global convergence, not accuracy, and Newton with an exact
     // search converges from wherever the unit steps leave it)
-    const bool fast_now = it < P.unit_steps;  // (option "ls_fast_iterations"; default MZ_PL_UNIT_STEPS; custom tasks: 0, maze_env.py)
+    const bool fast_now = it < P.unit_steps;  // (option "ls_fast_iterations"; default 5, point_dyn.h; custom tasks: 0, maze_env.py)
     for (int ls = 0; ls < 30 && changed && !fast_now; ls++) {
       double e1 = 0.0, e2 = 0.0;
 #pragma unroll
@@ -435,7 +421,6 @@ MZP_HD void point_forward_bare(const C& cx, const PointDev& P, PlanarScratch<0, 
     it++;
   }
   if (ncon > 0) { qacc[0] = a[0]; qacc[1] = a[1]; qacc[2] = a[2]; }
-  MZB_TICK(4);
 }
 
 template <int NB, int NS, class C>
@@ -459,7 +444,6 @@ MZP_HD void point_env_step_bare(const C& cx, const PointDev& P, PlanarScratch<0,
 #pragma unroll
     for (int i = 0; i < 3; i++) v[i] = fmin(fmax(v[i], -P.vel_limit), P.vel_limit);
   }
-  MZB_TICK(5);
   for (int f = 0; f < P.frame_skip; f++) {  // mj_step, RK4 (point.xml:3)
     const double h = P.h;
     MZ_FOR(one, 1) { for (int i = 0; i < 3; i++) { s.x0[i] = q[i]; s.v0[i] = v[i]; s.accv[i] = 0.0; s.accf[i] = 0.0; } }
@@ -471,7 +455,6 @@ MZP_HD void point_env_step_bare(const C& cx, const PointDev& P, PlanarScratch<0,
     for (int st = 0; st < 4; st++) {
       point_forward_bare(cx, P, s, q, v, qacc, qas, st > 0 || f == 0, maybe);
       if (st == 3) { cx.sync(); MZ_FOR(one, 1) { s.wds[0] = qacc[0] - qas[0]; s.wds[1] = qacc[1] - qas[1]; s.wds[2] = qacc[2] - qas[2]; } }
-      MZB_TICK(8);
       const double bw = (st == 0 || st == 3) ? 1.0 / 6 : 1.0 / 3, aw = st == 2 ? 1.0 : 0.5;
       MZ_FOR(one, 1) { for (int i = 0; i < 3; i++) { s.accv[i] += bw * v[i]; s.accf[i] += bw * qacc[i]; } }
       cx.sync();
@@ -484,10 +467,8 @@ MZP_HD void point_env_step_bare(const C& cx, const PointDev& P, PlanarScratch<0,
 #pragma unroll
     for (int i = 0; i < 3; i++) { q[i] = s.x0[i] + h * s.accv[i]; v[i] = s.v0[i] + h * s.accf[i]; }
     cx.sync();  // (the next frame's lane 0 overwrites x0 ... accf)
-    MZB_TICK(6);
   }
   // maze_env.py:454-464: manual wall bounce on the robot's xy
-#ifndef MZ_EXP_NODETECT
   if (P.nseg > 0) {
     const double new_xy[2] = {q[0], q[1]}, old_xy[2] = {s.old_xy[0], s.old_xy[1]};
     double fin[2];
@@ -495,9 +476,7 @@ MZP_HD void point_env_step_bare(const C& cx, const PointDev& P, PlanarScratch<0,
     const int r = point_bounce_group<0, 0>(cx, P, s, old_xy, new_xy, fin);
     if (r < 0) { MZ_FOR(one, 1) s.status |= MZ_STATUS_COLLINEAR; }
     q[0] = fin[0]; q[1] = fin[1];
-    MZB_TICK(7);
   }
-#endif
   cx.sync();
   MZ_FOR(one, 1) {
     for (int i = 0; i < 3; i++) { s.q[i] = q[i]; s.v[i] = v[i]; }

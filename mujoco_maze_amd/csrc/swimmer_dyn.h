@@ -200,14 +200,12 @@ struct SwimmerOneLane {
   MZS_HD int lane0() const { return 0; }
   MZS_HD double gsum(double x) const { return x; }
   MZS_HD double from_lane(double x, int) const { return x; }
-  MZS_HD void stamp(int) const {}  // phase timers of experiment builds (planar_kernels.hip, MZ_EXP_SWPROF)
 };
 
 // forward dynamics: qacc from (q, v, motor torques tau[NL - 1]); returns status bits
 template <int NL, class C>
 MZS_HD int swimmer_forward(const C& cx, const SwimmerDev& P, const double* q, const double* v, const double* tau, double* qacc) {
   constexpr int NV = NL + 2, NH = NL - 1;
-  cx.stamp(5);
   // link orientation angles and rates
   double phi[NL], om[NL], c[NL], s[NL];
   phi[0] = q[2]; om[0] = v[2];
@@ -224,7 +222,6 @@ MZS_HD int swimmer_forward(const C& cx, const SwimmerDev& P, const double* q, co
 #pragma unroll
     for (int b = 0; b < NL; b++) { c[b] = cx.from_lane(cm, b); s[b] = cx.from_lane(sm, b); }
   }
-  cx.stamp(0);
   double M[NV][NV], frc[NV], L[NV][NV], inv[NV];
   if constexpr (C::nlanes > 1) {
     // Lane-group path: ONE instruction stream for every link — lane b holds link b's constants and chain length in registers
@@ -270,7 +267,6 @@ MZS_HD int swimmer_forward(const C& cx, const SwimmerDev& P, const double* q, co
       tz -= P.density * bx2 * (bx0 * bx0 * bx0 * bx0 + bx1 * bx1 * bx1 * bx1) * fabs(w) * w / 64.0;
     }
     const double Gx = (co * fx - so * fy) - m * ax, Gy = (so * fx + co * fy) - m * ay;
-    cx.stamp(1);
     // shares -> group sums; the slides' corner of M is constant (SwimmerDev::mtot)
     frc[0] = cx.gsum(Gx); frc[1] = cx.gsum(Gy);
     M[0][0] = P.mtot[0]; M[1][1] = P.mtot[1]; M[1][0] = 0.0; M[0][1] = 0.0;
@@ -288,7 +284,6 @@ MZS_HD int swimmer_forward(const C& cx, const SwimmerDev& P, const double* q, co
       }
     }
     for (int k = 0; k < NH; k++) frc[3 + k] += tau[k];
-    cx.stamp(2);
     if constexpr (NL > 3) sw_factor_slides<NV>(M, P.inv_l[0], P.inv_l[1], L, inv);
   } else {
   // position Jacobians of the link centres: p_b = p0 + sum_{k<b} off[k+1] e(phi_k) + com[b] e(phi_b)
@@ -373,7 +368,6 @@ MZS_HD int swimmer_forward(const C& cx, const SwimmerDev& P, const double* q, co
     sw_subst<NV>(L, inv, frc, qas);
   }
   for (int i = 0; i < NV; i++) qacc[i] = qas[i];
-  cx.stamp(3);
   // joint limits on the inner hinges
   double sg[NH], D[NH], aref[NH];
   for (int k = 0; k < NH; k++) { sg[k] = 0.0; D[k] = 0.0; aref[k] = 0.0; }
@@ -389,7 +383,6 @@ MZS_HD int swimmer_forward(const C& cx, const SwimmerDev& P, const double* q, co
       any = true;
     }
   }
-  cx.stamp(4);
   if (!any) return 0;
   if constexpr (NH <= 2) {
     // One or two limit rows, each on a single dof (J_k = sg_k e_{3+k}): the minimiser of
@@ -433,7 +426,6 @@ MZS_HD int swimmer_forward(const C& cx, const SwimmerDev& P, const double* q, co
       }
       for (int i = 0; i < NV; i++) qacc[i] = qas[i] + (sg[0] * l0) * X0[i] + (sg[1] * l1) * X1[i];
     }
-    cx.stamp(4);
     return 0;
   }
   int status = 0;
@@ -482,7 +474,6 @@ MZS_HD int swimmer_forward(const C& cx, const SwimmerDev& P, const double* q, co
     }
     for (int i = 0; i < NV; i++) qacc[i] += alpha * sr[i];
   }
-  cx.stamp(4);
   return status;
 }
 

@@ -243,7 +243,6 @@ struct SwimmerLanesEmu {
     pthread_barrier_wait(&sh->bar);
     return r;
   }
-  void stamp(int) const {}
 };
 template <int NL, int NB, int G>
 struct SwimmerLaneJob {
