@@ -376,6 +376,23 @@ int32_t mz_read_wave_cycles(mz_handle* h, uint64_t* out_host, int32_t n_host);
  * read) — which phase makes the slowest waves slow (Ant kernels). */
 int32_t mz_read_wave_phase_cycles(mz_handle* h, uint64_t* out_host, int32_t n_host);
 
+/* Top view of env states as images: render.render_top_down (mujoco_maze_amd/render.py; the reference's MazeEnv.render with
+ * image_shape, mujoco_maze/maze_env.py:389-420, draws a 3-D camera image instead) for `count` envs in one launch, pixel for pixel
+ * what the Python rasteriser draws (csrc/mz_render.h; the device's sin / cos / atan2 of state angles may differ from the host's by
+ * an ulp, which can move an edge pixel).
+ *  qpos_dev    [count, nq] fp32 states to draw, row i for image i; NULL: the batch's current state, row env_idx[i] of what
+ *              mz_get_state returns (the handle's engine copies it into a scratch buffer on `stream` first)
+ *  env_idx_dev [count] i32 env of image i (any order, repeats allowed: it picks the state row without qpos_dev and the env's row
+ *              of the per-env goal table of mz_bind_env_goals); NULL: 0 .. count - 1.  An index outside 0 .. num_envs - 1
+ *              gives an all-zero image
+ *  ngoal_style must equal the goal table's count; goal_rgb [ngoal][3] u8 and goal_size [ngoal] float64 are HOST arrays (the
+ *              task's colours after Python's round() and marker radii, render.goal_style), read before the call returns
+ *  rgb_dev     [count, height, width, 3] u8, row 0 at the top; width, height 2 .. 16384
+ * Asynchronous on `stream`, no synchronisation.  Returns MZ_OK, MZ_ERR_ARG, MZ_ERR_HIP, or MZ_ERR_UNSUPPORTED for a user robot
+ * (mz_model.robot = MZ_ROBOT_GENERIC: render.py does not draw a user's geoms). */
+int32_t mz_render(mz_handle* h, const float* qpos_dev, const int32_t* env_idx_dev, int32_t count, int32_t width, int32_t height,
+                  int32_t ngoal_style, const uint8_t* goal_rgb, const double* goal_size, uint8_t* rgb_dev, void* stream);
+
 /* Average duration (ms) of the step kernel over the launches recorded since "time_kernels" was set (HIP events on
  * the stream each mz_step was given; synchronises on them); returns < 0 if not available. */
 double mz_last_kernel_ms(const mz_handle* h);

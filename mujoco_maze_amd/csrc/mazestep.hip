@@ -9,6 +9,7 @@
 #include <new>
 
 #include "mz_internal.h"
+#include "mz_render.h"
 
 __global__ void fetch_clear_status_kernel(int n, int* status, int* out) {
   int env = blockIdx.x * blockDim.x + threadIdx.x;
@@ -160,6 +161,7 @@ void mz_destroy(mz_handle* h) {
   mzk_generic_destroy(h);
   if (h->status) (void)hipFree(h->status);
   if (h->prof) (void)hipFree(h->prof);
+  if (h->render_qpos) (void)hipFree(h->render_qpos);
   if (h->ev) { for (int i = 0; i < 2 * h->ntime; i++) (void)hipEventDestroy(h->ev[i]); free(h->ev); }
   delete h;
 }
@@ -380,6 +382,40 @@ int32_t mz_step(mz_handle* h, const float* actions_dev, float* obs_dev, float* r
   HIPCHK(h, hipGetLastError());
   if (slot >= 0) { HIPCHK(h, hipEventRecord(h->ev[2 * slot + 1], st)); h->itime++; }
   h->nsteps++;
+  return MZ_OK;
+}
+
+// render.render_top_down for `count` env states (include/mazestep.h).  Without a caller's qpos the engine's own get-state kernel
+// first copies the batch's qpos into the handle's scratch on the same stream: the images show what mz_get_state would return.
+int32_t mz_render(mz_handle* h, const float* qpos_dev, const int32_t* env_idx_dev, int32_t count, int32_t width, int32_t height,
+                  int32_t ngoal_style, const uint8_t* goal_rgb, const double* goal_size, uint8_t* rgb_dev, void* stream) {
+  if (!h) return MZ_ERR_ARG;
+  RenderDev R;
+  const char* why = nullptr;
+  if (ngoal_style != h->model.ngoal || (ngoal_style > 0 && (!goal_rgb || !goal_size)))
+    return set_err(h, MZ_ERR_ARG, "mz_render: ngoal_style must equal the goal table's count, with that many goal_rgb / goal_size rows", hipSuccess);
+  const int rc = render_dev_from_model(&h->model, goal_rgb, goal_size, &R, &why);
+  if (rc != MZ_OK) {
+    snprintf(h->err, sizeof(h->err), "mz_render: %s", why ? why : "unsupported model");
+    return rc;
+  }
+  if (width < 2 || height < 2 || width > 16384 || height > 16384)
+    return set_err(h, MZ_ERR_ARG, "mz_render: width and height must be 2 .. 16384 (render.py divides by width - 1 and height - 1)", hipSuccess);
+  if (count < 0 || (!env_idx_dev && count > h->n))
+    return set_err(h, MZ_ERR_ARG, "mz_render: count must be >= 0, and <= num_envs without env_idx", hipSuccess);
+  if (count == 0) return MZ_OK;
+  if (!rgb_dev) return set_err(h, MZ_ERR_ARG, "mz_render: null rgb_dev", hipSuccess);
+  DeviceScope scope(h->device);
+  hipStream_t st = (hipStream_t)stream;
+  const float* q = qpos_dev;
+  if (!q) {
+    if (!h->render_qpos) HIPCHK(h, hipMalloc(&h->render_qpos, (size_t)h->n * h->model.nq * sizeof(float)));
+    if (h->robot == MZ_ROBOT_ANT) HIPCHK(h, mzk_ant_get_state(h, st, h->render_qpos, NULL, NULL, NULL));
+    else if (h->robot == MZ_ROBOT_GENERIC) HIPCHK(h, mzk_generic_get_state(h, st, h->render_qpos, NULL, NULL, NULL));
+    else HIPCHK(h, mzk_planar_get_state(h, st, h->render_qpos, NULL, NULL, NULL));
+    q = h->render_qpos;
+  }
+  HIPCHK(h, mzk_render(h, st, &R, q, qpos_dev ? 0 : 1, env_idx_dev, count, width, height, rgb_dev));
   return MZ_OK;
 }
 

@@ -3,6 +3,7 @@
 //   ant_kernels.hip     Ant kernels (fp32, built with the relaxed floating-point flags of csrc/Makefile)
 //   planar_kernels.hip  Point / Swimmer / Reacher kernels (fp64, built with strict IEEE flags: the Point's manual wall
 //                       detector and every task predicate must reproduce the reference's float64 decisions bit for bit)
+//   render_kernels.hip  the top view of render.py for a batch of env states (fp64, no relaxed flags: mz_render.h)
 // Kernels never call across translation units, so no relocatable device code is needed.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -13,6 +14,7 @@
 #include "point_dyn.h"
 #include "swimmer_dyn.h"
 
+struct RenderDev;  // mz_render.h (only mazestep.hip and render_kernels.hip see the renderer)
 struct GenDev;  // generic_dyn.h (the generic-robot path keeps its float64 constant block out of the other translation units)
 
 struct AntLayout { int nq, nv, rec, rec_t, obs_dim, nblock3, ostride; };  // record layout of the instantiated block count; obs_dim: without the
@@ -52,6 +54,7 @@ struct mz_handle {
   int time_stride, time_phase;  // option "time_kernels_stride": every k-th launch carries the event pair
   hipEvent_t* ev;  // 2 * ntime
   long nsteps;
+  float* render_qpos;  // [n][nq] scratch of mz_render without a caller's qpos (allocated on first use, freed by mz_destroy)
 };
 
 // ---- ant_kernels.hip
@@ -90,3 +93,9 @@ hipError_t mzk_generic_set_state(mz_handle* h, hipStream_t st, const float* qpos
 hipError_t mzk_generic_get_state(mz_handle* h, hipStream_t st, float* qpos, float* qvel, float* warm, int* t);
 hipError_t mzk_generic_set_task(mz_handle* h, const TaskDev* task);  // replaces the task block of the device constants (mz_set_goals)
 hipError_t mzk_generic_task_eval(mz_handle* h, hipStream_t st, int n, const float* obs, float* reward, uint8_t* done, int* goal_idx);
+
+// ---- render_kernels.hip (render.render_top_down for a batch: mz_render)
+// images i < count of R's model: qpos row i (qpos_by_env = 0) or row env_idx[i] (qpos_by_env = 1) of qpos, [nq] floats each;
+// env_idx NULL = 0 .. count - 1; an env index outside 0 .. n - 1 gives an all-zero image.  rgb: uint8 [count][height][width][3]
+hipError_t mzk_render(mz_handle* h, hipStream_t st, const RenderDev* R, const float* qpos, int qpos_by_env, const int* env_idx, int count,
+                      int width, int height, uint8_t* rgb);

@@ -18,7 +18,7 @@ import numpy as np
 from mujoco_maze_amd import _capi
 from mujoco_maze_amd.agent_model import AgentModel
 from mujoco_maze_amd.maze_task import MazeTask
-from mujoco_maze_amd.model import CompiledModel, compile_model
+from mujoco_maze_amd.model import ROBOT_ID, CompiledModel, compile_model
 
 
 class Box:
@@ -534,6 +534,65 @@ class VecMazeEnv:
 
         qpos = self.get_state()[0][env_index].double().cpu().numpy()
         return R.render_top_down(self.model, qpos, image_shape)
+
+    def render_batch(self, env_indices=None, image_shape: Tuple[int, int] = (600, 480), qpos=None, out=None):
+        """Top views of many envs at once, drawn on the device (mz_render): uint8 [k, H, W, 3] on `self.device` with, for every
+        env, the pixels render.render_top_down draws for its state (image_shape = (width, height), row 0 at the top).
+
+        env_indices: the envs to draw (a sequence of ints or an int tensor; any order, repeats allowed), default all.  qpos:
+        float32 [k, nq] states to draw instead of the envs' current ones (the envs then only pick the per-env goals).  out: a
+        contiguous uint8 [k, H, W, 3] tensor on the device to draw into.  Enqueued on the current stream without a host
+        synchronisation: called right after step() it draws the post-step state — under auto-reset the new episode's first
+        state, like the observation.  Indices in a device tensor are not checked on the host: an index outside the batch gives an
+        all-zero image."""
+        from mujoco_maze_amd import render as R
+
+        torch, n = self._torch, self.num_envs
+        if self.model.c.robot == ROBOT_ID["generic"]:
+            raise NotImplementedError("render_batch: render.py does not draw a user robot's geoms (ROBOT = \"generic\")")
+        w, h = (int(v) for v in image_shape)
+        if w < 2 or h < 2 or w > 16384 or h > 16384:
+            raise ValueError(f"image_shape must be (width, height) with 2 <= width, height <= 16384, got {tuple(image_shape)}")
+        idx = None
+        if env_indices is not None:
+            if torch.is_tensor(env_indices):
+                if env_indices.dim() != 1 or env_indices.dtype not in (torch.int32, torch.int64):
+                    raise ValueError("env_indices must be a 1-D integer tensor")
+                idx = env_indices.to(device=self.device, dtype=torch.int32).contiguous()
+            else:
+                a = np.asarray(env_indices)
+                if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+                    raise ValueError("env_indices must be a 1-D sequence of ints")
+                if a.size and (a.min() < 0 or a.max() >= n):
+                    raise ValueError(f"env_indices must lie in 0 .. {n - 1}")
+                idx = torch.from_numpy(a.astype(np.int32)).pin_memory().to(self.device, non_blocking=True)
+            k = idx.shape[0]
+        q = None
+        if qpos is not None:
+            q = qpos if torch.is_tensor(qpos) else torch.as_tensor(np.asarray(qpos, np.float32))
+            if q.dim() != 2 or q.shape[1] != self.nq or not q.is_floating_point():
+                raise ValueError(f"qpos must be a float tensor of shape [k, nq = {self.nq}], got {tuple(q.shape)} {q.dtype}")
+            q = q.to(device=self.device, dtype=torch.float32).contiguous()
+            if idx is not None and q.shape[0] != k:
+                raise ValueError(f"qpos has {q.shape[0]} rows for {k} env_indices")
+            if idx is None:
+                k = q.shape[0]
+                if k > n:
+                    raise ValueError(f"qpos has {k} rows, more than the {n} envs: pass env_indices")
+        if idx is None and q is None:
+            k = n
+        shape = (k, h, w, 3)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        elif not torch.is_tensor(out) or tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous() \
+                or out.device != self.device:
+            raise ValueError(f"out must be a contiguous uint8 tensor of shape {shape} on {self.device}")
+        rgb, size = R.goal_style(self.model)
+        rgb, size = np.ascontiguousarray(rgb, np.uint8), np.ascontiguousarray(size, np.float64)
+        rc = self._lib.mz_render(self._h, _ptr(q), _ptr(idx), k, w, h, len(size), rgb.ctypes.data_as(C.c_void_p),
+                                 size.ctypes.data_as(C.c_void_p), _ptr(out), self._stream())
+        _capi.check(self._lib, self._h, rc, "mz_render")
+        return out
 
     def state_for_viewer(self, env_index: int = 0) -> dict:
         """MJCF of the model + the env's qpos / qvel (plain lists) for replay in an external MuJoCo viewer."""

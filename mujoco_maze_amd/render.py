@@ -8,6 +8,8 @@ websocket.  Neither mujoco-py nor a GL context exists next to a batch of device-
   the robot (ant: torso + four legs from its joint angles; point: disc + heading arrow; swimmer / reacher: the link chain).
   It returns an `uint8 [H, W, 3]` array like the reference's `_render_image` (maze_env.py:389-393) — not the same pixels: a
   different camera, flat shading.
+* `goal_style(cm)` — the goals' colours and marker sizes, shared with the device renderer (`VecMazeEnv.render_batch`,
+  csrc/mz_render.h), which draws the same image for a whole batch on the GPU.
 * `state_for_viewer(cm, qpos, qvel)` — the env's MJCF (`mjcf.world_to_mjcf`, the model this repository steps) plus its
   qpos / qvel as plain lists, for anyone who wants to replay device states in a real MuJoCo viewer.
 
@@ -66,6 +68,16 @@ def _rgb(c) -> Tuple[int, int, int]:
     return int(round(255 * c.red)), int(round(255 * c.green)), int(round(255 * c.blue))
 
 
+def goal_style(cm: CompiledModel) -> Tuple[np.ndarray, np.ndarray]:
+    """Colour (uint8 [ngoal, 3], Python's round() of the task's rgb) and marker radius (float64 [ngoal]: custom_size, or
+    scale * 0.1, maze_env.py:203-216) of every goal of the task, in list order: what render_top_down draws, and what
+    VecMazeEnv.render_batch hands to the device renderer (mz_render)."""
+    goals, s = cm.task.goals, cm.world.scale
+    rgb = np.array([_rgb(g.rgb) for g in goals], np.uint8).reshape(len(goals), 3)
+    size = np.array([g.custom_size if g.custom_size is not None else s * 0.1 for g in goals], np.float64)
+    return rgb, size
+
+
 def _yaw_from_quat(q: Sequence[float]) -> float:
     w, x, y, z = q
     return math.atan2(2.0 * (w * z + x * y), 1.0 - 2.0 * (y * y + z * z))
@@ -99,10 +111,11 @@ def render_top_down(cm: CompiledModel, qpos: Sequence[float], image_shape: Tuple
             cell = world.structure[i][j]
             if cell.is_block() or cell.is_chasm():
                 cv.rect(j * s - m.torso_x, i * s - m.torso_y, 0.5 * s, 0.5 * s, WALL if cell.is_block() else CHASM)
-    for g in task.goals:  # sites: spheres of radius custom_size or scale * 0.1 (maze_env.py:203-216)
-        size = g.custom_size if g.custom_size is not None else s * 0.1
-        cv.disc(g.pos[0], g.pos[1], size, _rgb(g.rgb))
-        cv.ring(g.pos[0], g.pos[1], g.threshold, _rgb(g.rgb))
+    rgb, size = goal_style(cm)
+    for g, c, r in zip(task.goals, rgb, size):  # sites: spheres of radius custom_size or scale * 0.1 (maze_env.py:203-216)
+        c = tuple(int(v) for v in c)
+        cv.disc(g.pos[0], g.pos[1], float(r), c)
+        cv.ring(g.pos[0], g.pos[1], g.threshold, c)
     for k in range(m.nblock):
         b, gid = m.block_bodyid[k], m.block_geomid[k]
         x, y = _block_xy(cm, qpos, b)
