@@ -350,7 +350,7 @@ int32_t mz_debug_forward(mz_handle* h, const float* actions_dev, float* qacc_dev
 
 /* Parity-test entries for the two places where the reference's float64 DECISIONS must be reproduced bit for bit.
  * mz_debug_task_eval: MazeTask.reward / termination / first matching goal (maze_task.py:43-47,77-81,110-111,403-407) on
- *   n_rows observation rows [n_rows, obs_dim] fp32 — the very task_eval_dev instance the handle's step kernel runs:
+ *   n_rows observation rows [n_rows, obs_dim] fp32 — the very task_eval_dev (csrc/mz_task.h) instance the handle's step kernel runs:
  *   reward_dev[n_rows] = task reward only (no inner reward), done_dev[n_rows] u8 = termination, goal_idx_dev (nullable).
  *   With per-env goals bound (mz_bind_env_goals) row r < num_envs is judged with env r's goals, later rows with the shared table.
  * mz_debug_detect: CollisionDetector.detect + the bounce / give-up rule of MazeEnv.step (maze_env_utils.py:96-123,186-206;

@@ -24,44 +24,14 @@
 // Template parameter NB = number of movable XY blocks of the maze (0 for AntUMaze / Ant4Rooms,
 // 1 for AntPush / AntBlockMaze / AntBlockCarry; mujoco_maze/maze_env.py:563-660).
 //
-// Execution contexts (template parameter C):
-//   * device: csrc/mazestep.hip — G lanes per env, cx.sync() = wavefront-scope fence,
-//     cx.gsum() = DPP/shuffle butterfly inside the group;
-//   * host emulation (tests/emu, CPU tests of the kernel logic only — never a
-//     product path): nlanes = 1, so every MZ_FOR runs all its items in order.
-// Rule that makes both valid: inside one phase (between two cx.sync()) the
-// iterations of an MZ_FOR are independent, and nothing but LDS scratch carries
-// values from one phase to the next (group-uniform scalars may live in registers).
+// Programming model (MZ_FOR, the execution contexts C, the rule that makes device and host emulation both valid): mz_lanes.h.
 #pragma once
 #include <cstddef>
 
 #include "ant_model.h"
-
-#if defined(__HIPCC__)
-#define MZ_HD __host__ __device__ __forceinline__
-#else
-#define MZ_HD inline
-#endif
-
-#define MZ_FOR(i, n) for (int i = cx.lane0(); i < (n); i += C::nlanes)
-// items 0..n-1 on the lanes base, base+1, ... (mod group size): lets unrelated work share one phase
-#define MZ_FOR_AT(i, n, base) for (int i = mz_first_item(cx.lane0(), (base), C::nlanes); i < (n); i += C::nlanes)
-
-MZ_HD int mz_first_item(int lane, int base, int nl) { return (lane - base) & (nl - 1); }  // group sizes are powers of two
-
-struct HostCtx {
-  static constexpr int nlanes = 1;
-  static constexpr bool row_solver = false;  // the DPP-row Newton solver (ant_newton_rows.h) exists on the device only
-  MZ_HD int lane0() const { return 0; }
-  MZ_HD void sync() const {}
-  MZ_HD float gsum(float x) const { return x; }
-  MZ_HD double gsum(double x) const { return x; }
-  MZ_HD double rowsum(double x) const { return x; }
-  MZ_HD bool any(bool p) const { return p; }
-  MZ_HD bool gany(bool p) const { return p; }
-  MZ_HD unsigned long long gballot(bool p) const { return p ? 1ULL : 0ULL; }
-  template <class S> MZ_HD void tick(S&, int) const {}
-};
+#include "mz_lanes.h"
+#include "mz_maze.h"
+#include "mz_task.h"
 
 // ------------------------------------------------------------------ sizes
 // The template parameter NB of everything below is a CONFIGURATION of movable bodies: 0-3 = that many movable blocks with two
@@ -263,32 +233,8 @@ MZ_HD float impedance_pair(const float* si, float x, float* one_minus) {
   *one_minus = od0 - y * (od0 - odm);
   return d0 + y * (dmax - d0);
 }
-MZ_HD float impedancef(const float* si, float x) {
-  float d0 = si[0], dmax = si[1], width = si[2], mid = si[3], power = si[4];
-  if (d0 == dmax || width <= 1e-15f) return 0.5f * (d0 + dmax);
-  float xn = x / width;
-  if (xn >= 1.0f) return dmax;
-  if (xn <= 0.0f) return d0;
-  float y;
-  if (power <= 1.0f) y = xn;
-  else if (power == 2.0f) y = xn <= mid ? xn * xn / mid : 1.0f - (1.0f - xn) * (1.0f - xn) / (1.0f - mid);  // MuJoCo default
-  else if (xn <= mid) y = powf(xn, power) / powf(mid, power - 1.0f);
-  else y = 1.0f - powf(1.0f - xn, power) / powf(1.0f - mid, power - 1.0f);
-  return d0 + y * (dmax - d0);
-}
 
-
-// Row bitmask of the cell grid for a per-lane row index.  The grid lives in the kernel-argument block
-// (scalar registers); a select chain keeps it there — indexing the array with a vector index would make the
-// compiler spill it to scratch memory.
-MZ_HD uint32_t maze_row(const MazeDev& z, int i) {
-  uint32_t m = 0u;
-#pragma unroll
-  for (int r = 0; r < MZ_MAX_GRID; r++) m = (r == i) ? z.rowmask[r] : m;
-  return m;
-}
-
-// the same lookup from the env's LDS copy of the grid (ant_fill_tables): one read instead of a 12-way select
+// maze_row's lookup (mz_maze.h) from the env's LDS copy of the grid (ant_fill_tables): one read instead of a 12-way select
 template <class S>
 MZ_HD uint32_t maze_row_lds(const S& s, int i) { return (i >= 0 && i < MZ_MAX_GRID) ? s.rowmask[i] : 0u; }
 template <class S>
@@ -986,39 +932,6 @@ MZ_HD void round_vs_box(bool sphere, const float* ctr, const float* ax, float hl
       emit(cg);
     }
   }
-}
-
-// Two axis-aligned boxes (movable blocks never rotate, maze cells are grid-aligned): MuJoCo's mjc_BoxBox as restated in
-// oracle/mzo_physics.c box_box, specialised to parallel axes, in float64 on WORLD coordinates (grid-aligned boxes sit on exact
-// ties — a block at its spawn position shares border lines with the diagonal wall cells, its z extent equals the walls' —
-// which fp32 torso-relative coordinates would decide at random).  Separating axis = the face axis of least penetration
-// (first of x, y, z on ties; an edge-edge axis never wins between parallel boxes), dist = -penetration; contact points = the
-// corners of the intersection of the two facing faces (inclusive border tests); an intersection without area — boxes that share
-// only a border line: a block at its spawn position and the diagonal wall cells — makes no contact [ASSUME-12].
-// Box 1 = geom1: the normal points from box 1 to box 2.
-#define MZ_BOX_MINOVERLAP 1e-6
-struct AlignedBB { int ax, nu, nv; double dist, sg, pa, pu[2], pv[2]; };  // (pu / pv: read through selects, never by a run-time index — an indexed read put the struct into scratch memory)
-MZ_HD bool aligned_box_box(const double* c1, const double* h1, const double* c2, const double* h2, double margin, AlignedBB& o) {
-  double pen[3];
-  for (int k = 0; k < 3; k++) { pen[k] = h1[k] + h2[k] - fabs(c2[k] - c1[k]); if (pen[k] < -margin) return false; }
-  int ax = 0;
-  if (pen[1] < pen[ax]) ax = 1;
-  if (pen[2] < pen[ax]) ax = 2;
-  const int u = ax == 2 ? 0 : ax + 1, v = ax == 0 ? 2 : ax - 1;
-  double lo[3], hi[3];
-  for (int k = 0; k < 3; k++) { lo[k] = fmax(c1[k] - h1[k], c2[k] - h2[k]); hi[k] = fmin(c1[k] + h1[k], c2[k] + h2[k]); }
-  const double h1u = u == 0 ? h1[0] : (u == 1 ? h1[1] : h1[2]), h1v = v == 0 ? h1[0] : (v == 1 ? h1[1] : h1[2]);
-  const double dtol = 1e-9 * (1.0 + h1u + h1v);  // coincident candidates (oracle: same)
-  const double lou = u == 0 ? lo[0] : (u == 1 ? lo[1] : lo[2]), hiu = u == 0 ? hi[0] : (u == 1 ? hi[1] : hi[2]);
-  const double lov = v == 0 ? lo[0] : (v == 1 ? lo[1] : lo[2]), hiv = v == 0 ? hi[0] : (v == 1 ? hi[1] : hi[2]);
-  if (hiu - lou <= MZ_BOX_MINOVERLAP || hiv - lov <= MZ_BOX_MINOVERLAP) return false;  // the faces must overlap by a positive area (oracle: MZO_BOX_MINOVERLAP)
-  const double c1a = ax == 0 ? c1[0] : (ax == 1 ? c1[1] : c1[2]), c2a = ax == 0 ? c2[0] : (ax == 1 ? c2[1] : c2[2]);
-  const double h1a = ax == 0 ? h1[0] : (ax == 1 ? h1[1] : h1[2]), pa = ax == 0 ? pen[0] : (ax == 1 ? pen[1] : pen[2]);
-  o.ax = ax; o.sg = c2a >= c1a ? 1.0 : -1.0; o.dist = -pa;
-  o.pa = c1a + o.sg * (h1a + 0.5 * o.dist);
-  o.nu = hiu - lou > dtol ? 2 : 1; o.nv = hiv - lov > dtol ? 2 : 1;
-  o.pu[0] = lou; o.pu[1] = hiu; o.pv[0] = lov; o.pv[1] = hiv;
-  return true;
 }
 
 // torso-relative centre of movable block k
@@ -1976,43 +1889,6 @@ MZ_HD void ant_mj_step(const C& cx, const AntDev& K, S& s, bool first_frame) {
   MZ_FOR(i, D::NV) s.qvel[i] = s.x0v[i] + h * s.accf[i];
   cx.sync();
   }
-}
-
-// ------------------------------------------------------------------ MazeTask reward / termination on the fp32 observation
-// that is returned to the caller (obs[0:3] agent slot, obs[3:6] object slot).  Flags and goal index are the reference's
-// float64 predicate (maze_task.py:43-44 `np.linalg.norm(obs[:dim] - pos) <= threshold`, :77-81 any goal, :403-407 first
-// match) evaluated on float64(obs): differences and squares in fp64, summed in index order without contraction, compared
-// with the squared-threshold bound of TaskDev (bit-exact whatever the build flags of the translation unit).
-// `env`: the env slot whose row of TaskDev::env_goals holds its own goal positions (per-episode resampling); -1 or no table bound:
-// the batch's shared goal table.
-MZ_HD void task_eval_dev(const TaskDev& T, const float* obs, float* reward, int* term, int* goal_idx, int env = -1) {
-#pragma clang fp contract(off) reciprocal(off) reassociate(off)
-  // (two loads, not one pointer select: the shared table stays a scalar load of the constant block)
-  const double* eg = (T.env_goals && env >= 0) ? T.env_goals + (size_t)env * (3 * MZ_MAX_GOAL) : nullptr;
-  const double slot_a[3] = {(double)obs[0], (double)obs[1], (double)obs[2]}, slot_o[3] = {(double)obs[3], (double)obs[4], (double)obs[5]};
-  int tm = 0, first = -1, first_t = -1;
-  for (int g = 0; g < T.ngoal; g++) {
-    double a = 0.0, b = 0.0;
-    for (int k = 0; k < 3; k++)
-      if (k < T.goal_dim[g]) {
-        const double gk = eg ? eg[3 * g + k] : T.goal_pos[g][k];
-        double e = (T.term_slot == MZ_SLOT_OBJECT ? slot_o[k] : slot_a[k]) - gk; a += e * e;
-        double f = (T.reward_slot == MZ_SLOT_OBJECT ? slot_o[k] : slot_a[k]) - gk; b += f * f;
-      }
-    if (!tm && a <= T.thr_sq[g]) { tm = 1; first_t = g; }
-    if (first < 0 && b <= T.thr_sq[g]) first = g;
-  }
-  double r = 0.0;
-  if (T.reward_kind == MZ_REWARD_FIRST_MATCH) r = T.reward_binary ? (tm ? 1.0 : T.penalty) : (first >= 0 ? T.rscale[first] : T.penalty);
-  else if (T.reward_kind == MZ_REWARD_NEG_DIST && T.ngoal > 0) {
-    double a = 0.0;
-    for (int k = 0; k < 3; k++)
-      if (k < T.goal_dim[0]) { double e = (T.reward_slot == MZ_SLOT_OBJECT ? slot_o[k] : slot_a[k]) - (eg ? eg[k] : T.goal_pos[0][k]); a += e * e; }
-    r = -sqrt(a) / T.task_scale;
-  }
-  // goal index: the goal that set the reward where the reward is a goal's (first match on the reward's slot, maze_task.py:403-407);
-  // for the other reward kinds (zero, distance) the first goal that ends the episode (termination's slot, maze_task.py:77-81,599,653)
-  *reward = (float)r; *term = tm; *goal_idx = T.reward_kind == MZ_REWARD_FIRST_MATCH ? first : first_t;
 }
 
 // coordinate c of movable block k's body origin (get_body_com, maze_env.py:364-368): spawn position + its slides

@@ -46,7 +46,6 @@ __device__ __forceinline__ unsigned rsum_u(unsigned x) {  // integer all-reduce 
   x += (unsigned)__builtin_amdgcn_mov_dpp((int)x, 0x140, 0xF, 0xF, true);
   return x;
 }
-__device__ __forceinline__ float sel4(const float (&v)[4], int i) { return i == 0 ? v[0] : (i == 1 ? v[1] : (i == 2 ? v[2] : v[3])); }
 __device__ __forceinline__ unsigned sum2bit(unsigned w) { return (unsigned)__popc(w & 0x55555555u) + 2u * (unsigned)__popc(w & 0xAAAAAAAAu); }
 
 struct GeomHit { float pos[3], n[3], dist; int kind; };  // one staged contact of a geom lane (registers)

@@ -7,14 +7,18 @@
 // checks that the compiled model really has that shape and refuses anything
 // else (MZ_ERR_UNSUPPORTED) instead of silently computing the wrong robot.
 //
-// Plain C++ (no HIP): shared by csrc/mazestep.hip and the CPU emulation of the
-// kernel logic in tests/emu/.
+// Ant only: the task and maze blocks AntDev embeds (TaskDev, MazeDev) and the refusal helper are every robot's, mz_task.h / mz_maze.h.
+//
+// Plain C++ (no HIP): shared by the translation units of libmazestep.so (mz_internal.h: mz_handle embeds AntDev) and the
+// CPU emulation of the kernel logic in tests/emu/.
 #pragma once
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
 
 #include "../../include/mazestep.h"
+#include "mz_maze.h"
+#include "mz_task.h"
 
 #define ANT_NBODY 13  // moving bodies: torso + 4 x (leg, aux, ankle)
 #define ANT_NV 14
@@ -24,31 +28,6 @@
 
 struct PairDev {  // mixed contact parameters of one geom-pair class
   float margin, mu, K, B, solimp[7];  // d0 dmax width midpoint power | 1 - d0, 1 - dmax rounded from float64 (impedance_pair, ant_dyn.h)
-};
-
-// Task constants.  Everything a flag depends on is float64, exactly the reference's values (maze_task.py:26-47): the
-// goal predicate `np.linalg.norm(obs[:dim] - pos) <= threshold` is evaluated in fp64 on the returned observation.
-// thr_sq[g] = the largest double s with sqrt(s) <= threshold (sqrt correctly rounded, as numpy's): `s <= thr_sq` is
-// then the same predicate without a square root, so no floating-point build flag can change a flag.
-struct TaskDev {
-  int ngoal, reward_kind, reward_slot, reward_binary, term_slot, max_steps;
-  int goal_dim[MZ_MAX_GOAL];
-  double goal_pos[MZ_MAX_GOAL][3], thr[MZ_MAX_GOAL], thr_sq[MZ_MAX_GOAL], rscale[MZ_MAX_GOAL];
-  double penalty, task_scale, inner_scale, fwd_w, ctrl_w;
-  // per-env goal POSITIONS (mz_bind_env_goals; device pointer, [N][MZ_MAX_GOAL][3] float64, or NULL: the batch shares goal_pos).  The
-  // reference resamples a task's goals at EVERY episode reset (maze_env.py:374-376: one task object per env); thresholds, reward
-  // scales and dims stay the task class's
-  const double* env_goals;
-};
-
-struct MazeDev {
-  int rows, cols;
-  uint32_t rowmask[MZ_MAX_GRID];  // bit j set <=> cell (i, j) is a BLOCK
-  float scale, tx, ty, half_xy, half_z, center_z;
-  // elevated mazes (Fall / MultiFall): a platform box (same footprint, z from 0 to 2 half_z, centre half_z) under every cell
-  // of the grid that is not a CHASM; the walls stand on top (center_z = half_z + height offset)
-  int elevated;
-  uint32_t platmask[MZ_MAX_GRID];  // bit j set <=> cell (i, j) carries a platform
 };
 
 struct AntDev {
@@ -92,11 +71,6 @@ struct AntDev {
   float tol, rtol, inv_scale;  // inv_scale = 1 / (meaninertia * nv)
 };
 
-static inline int ant_fail(char* err, int n, const char* msg) {
-  if (err && n > 0) { strncpy(err, msg, (size_t)n - 1); err[n - 1] = 0; }
-  return MZ_ERR_UNSUPPORTED;
-}
-
 static inline void pair_from(PairDev* p, const mz_model* m, const double* f1, const double* sr1, const double* si1, double mg1,
                              const double* f2, const double* sr2, const double* si2, double mg2) {
   double sr[2], si[5];
@@ -111,55 +85,16 @@ static inline void pair_from(PairDev* p, const mz_model* m, const double* f1, co
   p->solimp[5] = (float)(1.0 - si[0]); p->solimp[6] = (float)(1.0 - si[1]);
 }
 
-// largest double s with sqrt(s) <= thr (host libm sqrt is correctly rounded); -1 for a negative threshold (never matches)
-static inline double mz_sqrt_le_bound(double thr) {
-  if (!(thr >= 0.0)) return -1.0;
-  if (isinf(thr)) return thr;
-  double s = thr * thr;
-  while (sqrt(s) > thr) s = nextafter(s, 0.0);
-  while (sqrt(nextafter(s, INFINITY)) <= thr) s = nextafter(s, INFINITY);
-  return s;
-}
-
-static inline void task_dev_from_model(TaskDev* t, const mz_model* m) {
-  memset(t, 0, sizeof(*t));
-  t->ngoal = m->ngoal; t->reward_kind = m->reward_kind; t->reward_slot = m->reward_slot;
-  t->reward_binary = m->reward_binary; t->term_slot = m->term_slot; t->max_steps = m->max_episode_steps;
-  for (int g = 0; g < m->ngoal; g++) {
-    t->goal_dim[g] = m->goal_dim[g];
-    for (int k = 0; k < 3; k++) t->goal_pos[g][k] = m->goal_pos[g][k];
-    t->thr[g] = m->goal_threshold[g];
-    t->thr_sq[g] = mz_sqrt_le_bound(m->goal_threshold[g]);
-    t->rscale[g] = m->goal_reward_scale[g];
-  }
-  t->penalty = m->penalty; t->task_scale = m->task_scale; t->inner_scale = m->inner_reward_scaling;
-  t->fwd_w = m->forward_reward_weight; t->ctrl_w = m->ctrl_cost_weight;
-}
-
-static inline void maze_dev_from_model(MazeDev* z, const mz_model* m) {
-  memset(z, 0, sizeof(*z));
-  z->rows = m->grid_rows; z->cols = m->grid_cols;
-  for (int i = 0; i < m->grid_rows; i++)
-    for (int j = 0; j < m->grid_cols; j++)
-      if (m->grid[i][j] == MZ_CELL_BLOCK) z->rowmask[i] |= (1u << j);
-  z->elevated = m->elevated;
-  for (int i = 0; i < m->grid_rows && m->elevated; i++)
-    for (int j = 0; j < m->grid_cols; j++)
-      if (m->grid[i][j] != MZ_CELL_CHASM) z->platmask[i] |= (1u << j);
-  z->scale = (float)m->maze_scale; z->tx = (float)m->torso_x; z->ty = (float)m->torso_y;
-  z->half_xy = (float)m->wall_half_xy; z->half_z = (float)m->wall_half_z; z->center_z = (float)m->wall_center_z;
-}
-
 static inline int ant_dev_from_model(AntDev* a, const mz_model* m, char* err, int errlen) {
   memset(a, 0, sizeof(*a));
   const int nb = m->nblock, nball = m->nball;
-  if (nb < 0 || nb > 4) return ant_fail(err, errlen, "ant kernel: at most 4 movable blocks");
-  if (nball < 0 || nball > 1 || (nball && nb)) return ant_fail(err, errlen, "ant kernel: at most one object ball, and not together with movable blocks");
+  if (nb < 0 || nb > 4) return mz_refuse(err, errlen, "ant kernel: at most 4 movable blocks");
+  if (nball < 0 || nball > 1 || (nball && nb)) return mz_refuse(err, errlen, "ant kernel: at most one object ball, and not together with movable blocks");
   int nbdof = 0;
   for (int k = 0; k < nb; k++) nbdof += m->body_jntnum[m->block_bodyid[k]];
   if (m->robot != MZ_ROBOT_ANT || m->nbody != 14 + nb + nball || m->nv != ANT_NV + nbdof + 6 * nball || m->nq != ANT_NQ + nbdof + 7 * nball ||
       m->nu != ANT_NU || m->ngeom != 14 + nb + nball)
-    return ant_fail(err, errlen, "ant kernel: model is not the 14-body / 14-dof ant (+ movable blocks or one free-joint ball)");
+    return mz_refuse(err, errlen, "ant kernel: model is not the 14-body / 14-dof ant (+ movable blocks or one free-joint ball)");
   a->nblock = nb; a->observe_blocks = m->observe_blocks;
   a->nball = nball; a->observe_balls = m->observe_balls;
   if (nball) {
@@ -169,7 +104,7 @@ static inline int ant_dev_from_model(AntDev* a, const mz_model* m, char* err, in
         m->jnt_qposadr[j] != ANT_NQ || m->jnt_dofadr[j] != ANT_NV || fabs(I[0] - I[1]) > 1e-12 * I[0] || fabs(I[0] - I[2]) > 1e-12 * I[0] ||
         fabs(I[3]) + fabs(I[4]) + fabs(I[5]) > 1e-12 * I[0] || fabs(m->body_ipos[b][0]) + fabs(m->body_ipos[b][1]) > 1e-12 ||
         fabs(m->geom_pos[g][2] - m->body_ipos[b][2]) > 1e-12)
-      return ant_fail(err, errlen, "ant kernel: the object ball is one sphere on a free joint, centred above its body origin");
+      return mz_refuse(err, errlen, "ant kernel: the object ball is one sphere on a free joint, centred above its body origin");
     a->ball_mass = (float)m->body_mass[b]; a->ball_inertia = (float)I[0]; a->ball_r = (float)m->geom_size[g][0];
     a->ball_h = (float)m->body_ipos[b][2]; a->ball_bw_tran = (float)m->body_invweight0[b][0];
     pair_from(&a->ball_floor, m, m->geom_friction[0], m->geom_solref[0], m->geom_solimp[0], m->geom_margin[0], m->geom_friction[g],
@@ -179,7 +114,7 @@ static inline int ant_dev_from_model(AntDev* a, const mz_model* m, char* err, in
     pair_from(&a->ball_robot, m, m->geom_friction[1], m->geom_solref[1], m->geom_solimp[1], m->geom_margin[1], m->geom_friction[g],
               m->geom_solref[g], m->geom_solimp[g], m->geom_margin[g]);
   }
-  if (m->elevated && nb == 0) return ant_fail(err, errlen, "ant kernel: an elevated maze needs a movable block (the platform code lives in the block instantiations)");
+  if (m->elevated && nb == 0) return mz_refuse(err, errlen, "ant kernel: an elevated maze needs a movable block (the platform code lives in the block instantiations)");
   a->block_axis[0] = 0; a->block_axis[1] = 1; a->block_axis[2] = 2; a->block_nax = 2;
   for (int k = 0; k < nb; k++) {
     int b = m->block_bodyid[k], g = m->block_geomid[k], j0 = m->body_jntadr[b];
@@ -192,7 +127,7 @@ static inline int ant_dev_from_model(AntDev* a, const mz_model* m, char* err, in
     }
     if (ok && k > 0) ok = nax == a->block_nax && ax[0] == a->block_axis[0] && ax[1] == a->block_axis[1] && m->jnt_limited[j0] == a->block_limited;
     if (!ok)
-      return ant_fail(err, errlen, "ant kernel: a movable block is a box body with two slides along increasing coordinate axes (x y, y z or x z), "
+      return mz_refuse(err, errlen, "ant kernel: a movable block is a box body with two slides along increasing coordinate axes (x y, y z or x z), "
                                    "or — a single block — with three (x y z)");
     a->block_nax = nax; a->block_limited = m->jnt_limited[j0];
     for (int q = 0; q < nax; q++) { a->block_axis[q] = ax[q]; a->block_lo[q] = (float)m->jnt_range[j0 + q][0]; a->block_hi[q] = (float)m->jnt_range[j0 + q][1]; }
@@ -212,11 +147,11 @@ static inline int ant_dev_from_model(AntDev* a, const mz_model* m, char* err, in
     {  // the enumeration gives a block 3 x 3 grid cells (geom_contacts): its bounding sphere + margin must stay inside that
       const double* hb = m->geom_size[g];
       if (sqrt(hb[0] * hb[0] + hb[1] * hb[1] + hb[2] * hb[2]) + fmax(m->geom_margin[g], m->wall_margin) >= m->maze_scale)
-        return ant_fail(err, errlen, "ant kernel: a movable block must be smaller than a maze cell's reach (its bounding sphere < one cell size)");
+        return mz_refuse(err, errlen, "ant kernel: a movable block must be smaller than a maze cell's reach (its bounding sphere < one cell size)");
     }
   }
   if (m->jnt_type[0] != MZ_JNT_FREE || m->geom_type[0] != MZ_GEOM_PLANE || m->geom_type[1] != MZ_GEOM_SPHERE)
-    return ant_fail(err, errlen, "ant kernel: expected free root joint, floor plane, torso sphere");
+    return mz_refuse(err, errlen, "ant kernel: expected free root joint, floor plane, torso sphere");
   a->h = (float)m->timestep; a->gz = (float)m->gravity[2]; a->frame_skip = m->frame_skip;
   // classes from leg 0 (bodies 2,3,4 / geoms 2,3,4), torso = body 1 / geom 1
   const int cb[4] = {1, 2, 3, 4};
@@ -235,15 +170,15 @@ static inline int ant_dev_from_model(AntDev* a, const mz_model* m, char* err, in
     if (m->body_parent[b_leg] != 1 || m->body_parent[b_aux] != b_leg || m->body_parent[b_ank] != b_aux ||
         m->body_jntnum[b_leg] != 0 || m->jnt_type[j_hip] != MZ_JNT_HINGE || m->jnt_type[j_ank] != MZ_JNT_HINGE ||
         m->jnt_dofadr[j_hip] != 6 + 2 * l || m->geom_type[b_leg] != MZ_GEOM_CAPSULE || fabs(m->jnt_axis[j_hip][2] - 1.0) > 1e-12)
-      return ant_fail(err, errlen, "ant kernel: leg topology differs from ant.xml");
+      return mz_refuse(err, errlen, "ant kernel: leg topology differs from ant.xml");
     a->sx[l] = m->body_pos[b_aux][0] > 0 ? 1.f : -1.f;
     a->sy[l] = m->body_pos[b_aux][1] > 0 ? 1.f : -1.f;
     if (fabs(fabs(m->body_pos[b_aux][0]) - a->legoff) > 1e-6 || fabs(fabs(m->body_pos[b_ank][1]) - a->legoff) > 1e-6 ||
         fabs(m->body_mass[b_leg] - m->body_mass[2]) > 1e-12 || fabs(m->body_mass[b_ank] - m->body_mass[4]) > 1e-12)
-      return ant_fail(err, errlen, "ant kernel: legs are not mirror images");
+      return mz_refuse(err, errlen, "ant kernel: legs are not mirror images");
     for (int k = 0; k < 3; k++) a->ank_axis[l][k] = (float)m->jnt_axis[j_ank][k];
     a->ank_lo[l] = (float)m->jnt_range[j_ank][0]; a->ank_hi[l] = (float)m->jnt_range[j_ank][1];
-    if (!m->jnt_limited[j_hip] || !m->jnt_limited[j_ank]) return ant_fail(err, errlen, "ant kernel: hinges must be limited");
+    if (!m->jnt_limited[j_hip] || !m->jnt_limited[j_ank]) return mz_refuse(err, errlen, "ant kernel: hinges must be limited");
   }
   a->hip_lo = (float)m->jnt_range[1][0]; a->hip_hi = (float)m->jnt_range[1][1];
   a->armature = (float)m->dof_armature[6]; a->damping = (float)m->dof_damping[6];

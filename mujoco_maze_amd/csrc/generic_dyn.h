@@ -22,10 +22,12 @@
 // Then MazeEnv.step's own part (maze_env.py:448-481): the Point's manual wall bounce (the bit-exact detector of point_dyn.h),
 // the observation with the object balls' / movable blocks' body positions (maze_env.py:351-369), reward and termination.
 // One env per lane group; its working set (GenScratch) lives in LDS for the whole step.  Serial tree walks run on the group's
-// first lane, everything indexed by body / dof / geom / collision item / constraint row is an MZ_FOR over the lanes.
+// first lane, everything indexed by body / dof / geom / collision item / constraint row is an MZ_FOR over the lanes (mz_lanes.h).
 #pragma once
 #include <stddef.h>
-#include "ant_dyn.h"    // MZ_FOR, MZ_HD, HostCtx, TaskDev / MazeDev, task_eval_dev
+#include "mz_lanes.h"  // MZ_FOR, MZ_HD, HostCtx
+#include "mz_maze.h"   // MazeDev, maze_dev_from_model
+#include "mz_task.h"   // TaskDev, task_eval_dev, mz_refuse
 #include "point_dyn.h"  // point_bounce: CollisionDetector.detect + the bounce rule, operation by operation (Point step shape)
 
 #define GN_NB MZ_MAX_BODY  // bodies, world included
@@ -69,11 +71,6 @@ struct GenDev {
   double seg[MZ_MAX_SEG][4], restitution;
 };
 
-static inline int gen_fail(char* err, int n, const char* msg) {
-  if (err && n > 0) { strncpy(err, msg, (size_t)n - 1); err[n - 1] = 0; }
-  return MZ_ERR_UNSUPPORTED;
-}
-
 static inline void gen_pair(GenPair* p, const mz_model* m, const double* f1, const double* sr1, const double* si1, double mg1, double gp1, int cd1,
                             const double* f2, const double* sr2, const double* si2, double mg2, double gp2, int cd2, double tran) {
   double sr[2], si[5];
@@ -103,18 +100,18 @@ static inline int gen_model_needs_general_engine(const mz_model* m) {
 static inline int gen_dev_from_model(GenDev* g, const mz_model* m, char* err, int errlen) {
   memset(g, 0, sizeof(*g));
   if (m->nbody > GN_NB || m->njnt > GN_NJ || m->nv > GN_NV || m->nq > GN_NQ || m->ngeom > GN_NG || m->nbody < 2)
-    return gen_fail(err, errlen, "general engine: at most 23 bodies, 24 joints / dofs, 28 coordinates, 24 geoms");
-  if (m->geom_type[0] != MZ_GEOM_PLANE || m->geom_bodyid[0] != 0) return gen_fail(err, errlen, "general engine: geom 0 must be the floor plane on the world body");
+    return mz_refuse(err, errlen, "general engine: at most 23 bodies, 24 joints / dofs, 28 coordinates, 24 geoms");
+  if (m->geom_type[0] != MZ_GEOM_PLANE || m->geom_bodyid[0] != 0) return mz_refuse(err, errlen, "general engine: geom 0 must be the floor plane on the world body");
   for (int b = 1; b < m->nbody; b++)
-    if (m->body_parent[b] >= b) return gen_fail(err, errlen, "general engine: bodies must be listed parents first");
+    if (m->body_parent[b] >= b) return mz_refuse(err, errlen, "general engine: bodies must be listed parents first");
   for (int j = 0; j < m->njnt; j++) {
-    if (m->jnt_type[j] == MZ_JNT_BALL && m->jnt_limited[j]) return gen_fail(err, errlen, "general engine: limited ball joints are not implemented");
-    if (m->jnt_type[j] == MZ_JNT_FREE && m->body_jntnum[m->jnt_bodyid[j]] != 1) return gen_fail(err, errlen, "general engine: a free joint must be its body's only joint");
+    if (m->jnt_type[j] == MZ_JNT_BALL && m->jnt_limited[j]) return mz_refuse(err, errlen, "general engine: limited ball joints are not implemented");
+    if (m->jnt_type[j] == MZ_JNT_FREE && m->body_jntnum[m->jnt_bodyid[j]] != 1) return mz_refuse(err, errlen, "general engine: a free joint must be its body's only joint");
   }
   g->step_kind = m->step_kind ? m->step_kind : (m->robot == MZ_ROBOT_POINT ? GN_STEP_POINT : GN_STEP_MOTORS);
   if (g->step_kind == GN_STEP_POINT && (m->nq < 3 || m->jnt_type[0] != MZ_JNT_SLIDE || m->jnt_type[1] != MZ_JNT_SLIDE || m->jnt_type[2] != MZ_JNT_HINGE || m->nu < 2))
-    return gen_fail(err, errlen, "general engine: the Point's step shape needs a slide-x, slide-y, hinge-z root and two action entries (point.py:44-61)");
-  if (m->manual_collision && m->nseg <= 0) return gen_fail(err, errlen, "general engine: MANUAL_COLLISION without wall segments");
+    return mz_refuse(err, errlen, "general engine: the Point's step shape needs a slide-x, slide-y, hinge-z root and two action entries (point.py:44-61)");
+  if (m->manual_collision && m->nseg <= 0) return mz_refuse(err, errlen, "general engine: MANUAL_COLLISION without wall segments");
   g->m = *m;
   task_dev_from_model(&g->task, m);
   maze_dev_from_model(&g->maze, m);
@@ -135,21 +132,21 @@ static inline int gen_dev_from_model(GenDev* g, const mz_model* m, char* err, in
       else if (t1 == MZ_GEOM_SPHERE) kind = t2 == MZ_GEOM_SPHERE ? GK_SPHERE_SPHERE : t2 == MZ_GEOM_CAPSULE ? GK_SPHERE_CAPSULE : t2 == MZ_GEOM_BOX ? GK_SPHERE_BOX : -1;
       else if (t1 == MZ_GEOM_CAPSULE) kind = t2 == MZ_GEOM_BOX ? GK_CAPSULE_BOX : t2 == MZ_GEOM_CAPSULE ? GK_CAPSULE_CAPSULE : -1;
       else if (t1 == MZ_GEOM_BOX) kind = t2 == MZ_GEOM_BOX ? GK_BOX_BOX : -1;
-      if (kind < 0) return gen_fail(err, errlen, "general engine: a geom pair that can collide has no narrow phase here (geom types: plane, sphere, capsule, box)");
-      if (n >= GN_NI) return gen_fail(err, errlen, "general engine: too many geom pairs");
+      if (kind < 0) return mz_refuse(err, errlen, "general engine: a geom pair that can collide has no narrow phase here (geom types: plane, sphere, capsule, box)");
+      if (n >= GN_NI) return mz_refuse(err, errlen, "general engine: too many geom pairs");
       GenItem& it = g->item[n++];
       it.kind = kind; it.g1 = g1; it.g2 = g2; it.b1 = m->geom_bodyid[g1]; it.b2 = m->geom_bodyid[g2]; it.pad = 0;
       gen_pair(&it.P, m, m->geom_friction[g1], m->geom_solref[g1], m->geom_solimp[g1], m->geom_margin[g1], m->geom_gap[g1], m->geom_condim[g1],
                m->geom_friction[g2], m->geom_solref[g2], m->geom_solimp[g2], m->geom_margin[g2], m->geom_gap[g2], m->geom_condim[g2],
                m->body_invweight0[it.b1][0] + m->body_invweight0[it.b2][0]);
-      if (it.P.condim != 1 && it.P.condim != 3) return gen_fail(err, errlen, "general engine: condim must be 1 or 3");
+      if (it.P.condim != 1 && it.P.condim != 3) return mz_refuse(err, errlen, "general engine: condim must be 1 or 3");
     }
   for (int a = 1; a < m->ngeom && !m->collision_predefined; a++) {
     if (m->geom_bodyid[a] == 0) continue;
     if (!((m->geom_contype[a] & m->wall_conaffinity) || (m->wall_contype & m->geom_conaffinity[a]))) continue;
     const int t = m->geom_type[a];
-    if (t != MZ_GEOM_SPHERE && t != MZ_GEOM_CAPSULE && t != MZ_GEOM_BOX) return gen_fail(err, errlen, "general engine: geom types are plane, sphere, capsule, box");
-    if (n >= GN_NI) return gen_fail(err, errlen, "general engine: too many geom pairs");
+    if (t != MZ_GEOM_SPHERE && t != MZ_GEOM_CAPSULE && t != MZ_GEOM_BOX) return mz_refuse(err, errlen, "general engine: geom types are plane, sphere, capsule, box");
+    if (n >= GN_NI) return mz_refuse(err, errlen, "general engine: too many geom pairs");
     GenItem& it = g->item[n++];
     const bool box = t == MZ_GEOM_BOX;  // a maze box is geom1 against another box (same type, lower id), geom2 against spheres / capsules
     it.kind = t == MZ_GEOM_SPHERE ? GK_SPHERE_WALL : t == MZ_GEOM_CAPSULE ? GK_CAPSULE_WALL : GK_WALL_BOX;
@@ -157,7 +154,7 @@ static inline int gen_dev_from_model(GenDev* g, const mz_model* m, char* err, in
     gen_pair(&it.P, m, m->geom_friction[a], m->geom_solref[a], m->geom_solimp[a], m->geom_margin[a], m->geom_gap[a], m->geom_condim[a],
              m->wall_friction, m->wall_solref, m->wall_solimp, m->wall_margin, m->wall_gap, m->wall_condim,
              m->body_invweight0[m->geom_bodyid[a]][0] + m->body_invweight0[0][0]);
-    if (it.P.condim != 1 && it.P.condim != 3) return gen_fail(err, errlen, "general engine: condim must be 1 or 3");
+    if (it.P.condim != 1 && it.P.condim != 3) return mz_refuse(err, errlen, "general engine: condim must be 1 or 3");
   }
   g->nitem = n;
   for (int j = 0; j < m->njnt; j++) {
@@ -184,7 +181,7 @@ static inline int gen_dev_from_model(GenDev* g, const mz_model* m, char* err, in
   for (int b = 0; b < GN_NB; b++) g->subtree[b] = 0u;
   for (int b = 1; b < m->nbody; b++) for (int a = b; a > 0; a = m->body_parent[a]) g->subtree[a] |= 1u << b;
   for (int b = 1; b < m->nbody; b++) {  // (a parent's index is below its children's: mjcf.py / MuJoCo body order)
-    if (m->body_parent[b] >= b) return gen_fail(err, errlen, "general engine: bodies must be ordered parents first");
+    if (m->body_parent[b] >= b) return mz_refuse(err, errlen, "general engine: bodies must be ordered parents first");
     g->body_depth[b] = g->body_depth[m->body_parent[b]] + 1;
     if (g->body_depth[b] > g->max_depth) g->max_depth = g->body_depth[b];
   }
@@ -195,8 +192,8 @@ static inline int gen_dev_from_model(GenDev* g, const mz_model* m, char* err, in
   g->restitution = m->restitution;
   g->obs_extra = 3 * ((m->observe_balls ? m->nball : 0) + (m->observe_blocks ? m->nblock : 0));
   if (m->nq_robot < 3 || m->obs_dim != m->nq_robot + m->nv_robot + 1 + g->obs_extra + (m->top_down_view ? MZ_VIEW_DIM : 0))
-    return gen_fail(err, errlen, "general engine: obs_dim must be nq_robot + nv_robot + 1 + 3 per observed ball / block (+ the top-down view)");
-  if (m->nq_robot + m->nv_robot + 1 + g->obs_extra > MZ_MAX_OBS) return gen_fail(err, errlen, "general engine: observation wider than MZ_MAX_OBS");
+    return mz_refuse(err, errlen, "general engine: obs_dim must be nq_robot + nv_robot + 1 + 3 per observed ball / block (+ the top-down view)");
+  if (m->nq_robot + m->nv_robot + 1 + g->obs_extra > MZ_MAX_OBS) return mz_refuse(err, errlen, "general engine: observation wider than MZ_MAX_OBS");
   return MZ_OK;
 }
 

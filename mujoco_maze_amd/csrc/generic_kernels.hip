@@ -143,7 +143,7 @@ int mzk_generic_create(mz_handle* h, char* err, int errlen) {
   int rc = gen_dev_from_model(g, &h->model, err, errlen);
   if (rc == MZ_OK) {
     if (hipMalloc(&h->gen_dev, sizeof(GenDev)) != hipSuccess || hipMemcpy(h->gen_dev, g, sizeof(GenDev), hipMemcpyHostToDevice) != hipSuccess)
-      rc = gen_fail(err, errlen, "general engine: device allocation failed") == MZ_ERR_UNSUPPORTED ? MZ_ERR_HIP : MZ_ERR_HIP;
+      rc = mz_refuse(err, errlen, "general engine: device allocation failed") == MZ_ERR_UNSUPPORTED ? MZ_ERR_HIP : MZ_ERR_HIP;
   }
   free(g);
   return rc;

@@ -1,5 +1,5 @@
-// mz_device.h — device-side pieces shared by the kernel translation units (ant_kernels.hip, planar_kernels.hip):
-// the lane-group context, the counter-based RNG of the reset distribution, episode seeding.
+// mz_device.h — device-side pieces shared by the step-kernel translation units (ant_kernels.hip, planar_kernels.hip,
+// generic_kernels.hip): the lane-group context, the counter-based RNG of the reset distribution, episode seeding.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -21,7 +21,8 @@ __device__ __forceinline__ int xcd_block(int wg, int nwg) {
   return wg < 8 * per ? (wg & 7) * per + (wg >> 3) : wg;
 }
 
-// ------------------------------------------------------------------ device context of a lane group
+// ------------------------------------------------------------------ device context of a lane group: the device side of the
+// contract stated in mz_lanes.h (whose HostCtx is the one-lane host side)
 template <int G, bool PROF = false>
 struct DevCtx {
   static constexpr int nlanes = G;

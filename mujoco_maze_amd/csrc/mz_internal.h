@@ -1,10 +1,14 @@
-// mz_internal.h — what the three translation units of libmazestep.so share on the HOST side:
+// mz_internal.h — what the five translation units of libmazestep.so share on the HOST side:
 //   mazestep.hip        the C-ABI of include/mazestep.h (handle life cycle, options, argument checks, dispatch)
 //   ant_kernels.hip     Ant kernels (fp32, built with the relaxed floating-point flags of csrc/Makefile)
 //   planar_kernels.hip  Point / Swimmer / Reacher kernels (fp64, built with strict IEEE flags: the Point's manual wall
 //                       detector and every task predicate must reproduce the reference's float64 decisions bit for bit)
+//   generic_kernels.hip the general engine: any compiled model (fp64, no relaxed flags at all: generic_dyn.h)
 //   render_kernels.hip  the top view of render.py for a batch of env states (fp64, no relaxed flags: mz_render.h)
 // Kernels never call across translation units, so no relocatable device code is needed.
+// mz_handle embeds the three specialised robots' constant blocks by value, hence their MODEL headers below; no engine's dynamics
+// header (ant_dyn.h, planar_dyn.h, generic_dyn.h) is included here, and none includes another engine's — what they all need
+// lives in mz_lanes.h (programming model), mz_task.h (TaskDev, task_eval_dev) and mz_maze.h (MazeDev, grid-aligned boxes).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

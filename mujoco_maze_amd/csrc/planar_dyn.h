@@ -1,6 +1,6 @@
 // planar_dyn.h — the Point robot's MazeEnv.step with NB movable XY blocks, as lane-group SPMD code (fp64).
 //
-// Same programming model as ant_dyn.h: G lanes advance one environment, its working set (PlanarScratch<NB, NS>) lives
+// The programming model of mz_lanes.h (as ant_dyn.h): G lanes advance one environment, its working set (PlanarScratch<NB, NS>) lives
 // in LDS for the whole step, a phase is an MZ_FOR over independent items, cx.sync() is the hand-off.  The
 // single-lane host context (tests/emu) runs the same source on the CPU.
 //
@@ -18,7 +18,8 @@
 //     with exact line search, Cholesky by one lane — same cost model and stopping rule as the one-lane code
 //     this replaces.
 #pragma once
-#include "ant_dyn.h"    // MZ_FOR, HostCtx, maze_row
+#include "mz_lanes.h"   // MZ_FOR, MZ_HD, HostCtx
+#include "mz_maze.h"    // maze_row, aligned_box_box
 #include "point_dyn.h"  // PointDev, point_detect, pt_impedance
 template <int NB, int NS>
 struct PlanarDims {
@@ -390,7 +391,7 @@ MZP_HD void pl_box_box_upright(const double* pos1, const double* size1, const do
   pl_box_box_upright_t<false>(pos1, size1, pos2, size2, co, si, rot_first, margin, b1id, b2id, cls, emit, [](double, double) {});
 }
 
-// axis-aligned box (geom1: centre c1, half h1) vs axis-aligned box (geom2: centre c2, half h2): aligned_box_box (ant_dyn.h)
+// axis-aligned box (geom1: centre c1, half h1) vs axis-aligned box (geom2: centre c2, half h2): aligned_box_box (mz_maze.h)
 template <class Emit>
 MZP_HD void pl_box_box_aligned(const double* c1, const double* h1, const double* c2, const double* h2, double margin, int b1, int b2, int cls,
                                Emit&& emit) {

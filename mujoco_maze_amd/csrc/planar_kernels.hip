@@ -16,7 +16,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "ant_dyn.h"
+#include "mz_task.h"
 #include "point_dyn.h"
 #include "planar_dyn.h"
 #include "swimmer_dyn.h"

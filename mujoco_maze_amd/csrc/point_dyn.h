@@ -23,7 +23,8 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "ant_model.h"
+#include "mz_maze.h"  // MazeDev, maze_dev_from_model
+#include "mz_task.h"  // TaskDev, task_dev_from_model, mz_refuse
 
 #define MZ_STATUS_COLLINEAR 8
 
@@ -72,10 +73,10 @@ static inline void pt_mix_pair(PtPair* p, double h, double m1, double m2, const 
 static inline int point_dev_from_model(PointDev* p, const mz_model* m, char* err, int errlen) {
   memset(p, 0, sizeof(*p));
   const int nb = m->nblock, ns = m->nball;
-  if (ns < 0 || ns > 1 || (ns && nb)) return ant_fail(err, errlen, "point kernel: at most one object ball, and not together with movable blocks");
+  if (ns < 0 || ns > 1 || (ns && nb)) return mz_refuse(err, errlen, "point kernel: at most one object ball, and not together with movable blocks");
   if (m->robot != MZ_ROBOT_POINT || nb < 0 || nb > 3 || m->nv != 3 + 2 * nb + 3 * ns || m->nq != 3 + 2 * nb + 3 * ns || m->jnt_type[0] != MZ_JNT_SLIDE ||
       m->jnt_type[1] != MZ_JNT_SLIDE || m->jnt_type[2] != MZ_JNT_HINGE || fabs(m->body_ipos[1][1]) > 1e-12)
-    return ant_fail(err, errlen, "point kernel: model is not the slide-slide-hinge point robot (+ up to 3 XY blocks)");
+    return mz_refuse(err, errlen, "point kernel: model is not the slide-slide-hinge point robot (+ up to 3 XY blocks)");
   p->h = m->timestep; p->com_x = m->body_ipos[1][0]; p->vel_limit = m->velocity_limit; p->restitution = m->restitution;
   p->frame_skip = m->frame_skip; p->nseg = m->manual_collision ? m->nseg : 0;
   for (int k = 0; k < m->nseg; k++) for (int j = 0; j < 4; j++) p->seg[k][j] = m->seg[k][j];
@@ -83,15 +84,15 @@ static inline int point_dev_from_model(PointDev* p, const mz_model* m, char* err
   p->izz = m->body_inertia[1][2] + m->body_mass[1] * m->body_ipos[1][0] * m->body_ipos[1][0];
   p->inv_scale = 1.0 / (m->meaninertia * m->nv);
   if (m->ngeom != 3 + nb + ns || m->geom_type[1] != MZ_GEOM_SPHERE || m->geom_type[2] != MZ_GEOM_BOX)
-    return ant_fail(err, errlen, "point kernel: expected floor + sphere + arrow box (+ block) geoms");
+    return mz_refuse(err, errlen, "point kernel: expected floor + sphere + arrow box (+ block) geoms");
   p->sph_r = m->geom_size[1][0]; p->sph_z = m->body_pos[1][2] + m->geom_pos[1][2];  // torso body height: 0, or 0.75 + platform height in elevated mazes
   p->arr_off = m->geom_pos[2][0]; p->arr_hx = m->geom_size[2][0]; p->arr_hy = m->geom_size[2][1]; p->arr_hz = m->geom_size[2][2];
   p->arr_z = m->body_pos[1][2] + m->geom_pos[2][2];
   p->arr_rxy = sqrt(p->arr_hx * p->arr_hx + p->arr_hy * p->arr_hy);
   for (int k = 0; k < 5; k++)
-    if (m->geom_solimp[1][k] != m->geom_solimp[2][k]) return ant_fail(err, errlen, "point kernel: sphere and arrow must share contact parameters");
+    if (m->geom_solimp[1][k] != m->geom_solimp[2][k]) return mz_refuse(err, errlen, "point kernel: sphere and arrow must share contact parameters");
   if (m->geom_margin[1] != m->geom_margin[2] || m->geom_margin[0] != 0.0 || m->geom_margin[1] != 0.0)
-    return ant_fail(err, errlen, "point kernel: geom margins must be 0 (the floor touches sphere and blocks at dist = 0: no contact)");
+    return mz_refuse(err, errlen, "point kernel: geom margins must be 0 (the floor touches sphere and blocks at dist = 0: no contact)");
   const double bw_robot = m->body_invweight0[1][0];
   pt_mix_pair(&p->pair[0], m->timestep, m->geom_margin[1], m->wall_margin, m->geom_friction[1], m->wall_friction, m->geom_solref[1],
               m->wall_solref, m->geom_solimp[1], m->wall_solimp, bw_robot);
@@ -105,7 +106,7 @@ static inline int point_dev_from_model(PointDev* p, const mz_model* m, char* err
     if (m->body_jntnum[b] != 2 || m->jnt_type[j0] != MZ_JNT_SLIDE || m->jnt_type[j0 + 1] != MZ_JNT_SLIDE || m->geom_type[g] != MZ_GEOM_BOX ||
         ax[0] < 0 || ax[1] <= ax[0] || m->body_dofadr[b] != 3 + 2 * k || m->jnt_limited[j0] != m->jnt_limited[j0 + 1] || m->geom_margin[g] != 0.0 ||
         (k > 0 && (ax[0] != p->block_axis[0] || ax[1] != p->block_axis[1] || m->jnt_limited[j0] != p->block_limited)))
-      return ant_fail(err, errlen, "point kernel: a movable block is a box body with two slides along increasing coordinate axes (x y, y z or x z), margin 0");
+      return mz_refuse(err, errlen, "point kernel: a movable block is a box body with two slides along increasing coordinate axes (x y, y z or x z), margin 0");
     p->block_axis[0] = ax[0]; p->block_axis[1] = ax[1]; p->block_limited = m->jnt_limited[j0];
     for (int a = 0; a < 2; a++) { p->block_lo[a] = m->jnt_range[j0 + a][0]; p->block_hi[a] = m->jnt_range[j0 + a][1]; }
     if (p->block_limited) {  // limit rows: one-sided single rows with the joint's solref / solimp and margin; R from dof_invweight0
@@ -118,7 +119,7 @@ static inline int point_dev_from_model(PointDev* p, const mz_model* m, char* err
     for (int q = 0; q < 3; q++) { p->block_pos0[k][q] = m->body_pos[b][q]; p->block_half[q] = m->geom_size[g][q]; }
     p->block_mass = m->body_mass[b];
     if (k > 0 && (m->geom_size[g][0] != m->geom_size[m->block_geomid[0]][0] || m->body_mass[b] != m->body_mass[m->block_bodyid[0]]))
-      return ant_fail(err, errlen, "point kernel: movable blocks must share one size and mass");
+      return mz_refuse(err, errlen, "point kernel: movable blocks must share one size and mass");
   }
   if (nb > 0) {
     int g = m->block_geomid[0];
@@ -140,7 +141,7 @@ static inline int point_dev_from_model(PointDev* p, const mz_model* m, char* err
         fabs(m->jnt_axis[j0 + 1][1] - 1.0) > 1e-12 || fabs(m->jnt_axis[j0 + 2][2] - 1.0) > 1e-12 || m->jnt_limited[j0] || m->jnt_limited[j0 + 1] ||
         m->jnt_limited[j0 + 2] || m->geom_margin[g] != 0.0 || fabs(m->geom_pos[g][0]) + fabs(m->geom_pos[g][1]) > 1e-12 ||
         fabs(m->geom_pos[g][2] - m->geom_size[g][0]) > 1e-12 || m->dof_armature[3] != 0.0 || m->dof_damping[3] != 0.0 || m->dof_damping[5] != 0.0)
-      return ant_fail(err, errlen, "point kernel: object ball is not the slide-x / slide-y / hinge-z sphere body resting on the floor");
+      return mz_refuse(err, errlen, "point kernel: object ball is not the slide-x / slide-y / hinge-z sphere body resting on the floor");
     p->ball_mass = m->body_mass[b]; p->ball_izz = m->body_inertia[b][2]; p->ball_r = m->geom_size[g][0];
     for (int q = 0; q < 3; q++) p->ball_pos0[q] = m->body_pos[b][q];
     const double bw_ball = m->body_invweight0[b][0];
@@ -149,19 +150,19 @@ static inline int point_dev_from_model(PointDev* p, const mz_model* m, char* err
     pt_mix_pair(&p->pair[5], m->timestep, m->geom_margin[1], m->geom_margin[g], m->geom_friction[1], m->geom_friction[g], m->geom_solref[1],
                 m->geom_solref[g], m->geom_solimp[1], m->geom_solimp[g], bw_robot + bw_ball);
   }
-  if (m->wall_margin != 0.0) return ant_fail(err, errlen, "point kernel: wall margin must be 0");
+  if (m->wall_margin != 0.0) return mz_refuse(err, errlen, "point kernel: wall margin must be 0");
   p->reach = 0.0;
   for (int g = 1; g < 3; g++) {
     double r = hypot(m->geom_pos[g][0], m->geom_pos[g][1]) + m->geom_rbound[g];
     if (r > p->reach) p->reach = r;
   }
-  if (p->reach >= m->maze_scale) return ant_fail(err, errlen, "point kernel: maze cells must be wider than the robot's reach");
+  if (p->reach >= m->maze_scale) return mz_refuse(err, errlen, "point kernel: maze cells must be wider than the robot's reach");
   if (m->elevated) {
     // the robot has no z dof: lifted with the torso (maze_env.py:102-107) it hovers above the platforms and can touch neither
     // them nor the floor — the kernel relies on that
     const double top = m->height_offset, zoff = m->body_pos[1][2];
     if (zoff + m->geom_pos[1][2] - m->geom_size[1][0] < top || zoff + m->geom_pos[2][2] - m->geom_size[2][2] < top)
-      return ant_fail(err, errlen, "point kernel: in an elevated maze the robot's geoms must stay above the platforms");
+      return mz_refuse(err, errlen, "point kernel: in an elevated maze the robot's geoms must stay above the platforms");
   }
   maze_dev_from_model(&p->maze, m);
   task_dev_from_model(&p->task, m);
@@ -277,13 +278,6 @@ MZP_HD int point_bounce(const PD& P, const double* old_xy, const double* new_xy,
   if (again > 0) { fin[0] = old_xy[0]; fin[1] = old_xy[1]; return 2; }
   fin[0] = pos[0]; fin[1] = pos[1];
   return 1;
-}
-
-MZP_HD void point_qacc(const PointDev& P, const double* q, const double* v, double* a) {
-  double w2 = v[2] * v[2];
-  a[0] = P.com_x * w2 * cos(q[2]);
-  a[1] = P.com_x * w2 * sin(q[2]);
-  a[2] = 0.0;
 }
 
 // distance from the torso origin to the nearest BLOCK cell box (xy), used only to flag the

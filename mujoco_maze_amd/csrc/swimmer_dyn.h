@@ -22,7 +22,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "ant_model.h"
+#include "mz_task.h"  // TaskDev, task_dev_from_model, mz_refuse
 
 // MZ_SW_MAXL: longest planar chain the kernels are instantiated for (user MJCF: mjcf.py accepts 2..6 links)
 #define MZ_SW_MAXL 6
@@ -52,26 +52,26 @@ struct SwimmerDev {
 static inline int swimmer_dev_from_model(SwimmerDev* p, const mz_model* m, char* err, int errlen) {
   memset(p, 0, sizeof(*p));
   const int nbk = m->nblock, nl = m->nbody - 1 - nbk;
-  if (nbk < 0 || nbk > 1) return ant_fail(err, errlen, "swimmer kernel: at most one movable block");
+  if (nbk < 0 || nbk > 1) return mz_refuse(err, errlen, "swimmer kernel: at most one movable block");
   const int nbd0 = nbk ? m->body_jntnum[m->block_bodyid[0]] : 0;
   bool ok = m->robot == MZ_ROBOT_SWIMMER && nl >= 2 && nl <= MZ_SW_MAXL && (nl <= 3 || nbk == 0) && m->nv == nl + 2 + nbd0 && m->nq == nl + 2 + nbd0 && m->nu == nl - 1 &&
             m->collision_predefined && m->jnt_type[0] == MZ_JNT_SLIDE && m->jnt_type[1] == MZ_JNT_SLIDE;
   for (int j = 2; ok && j < nl + 2; j++) ok = m->jnt_type[j] == MZ_JNT_HINGE;
   for (int a = 0; ok && a < nl - 1; a++) ok = m->act_dofid[a] == 3 + a;
-  if (!ok) return ant_fail(err, errlen, "swimmer kernel: model is not a planar chain of 2..6 links on two slides (movable blocks: 2- and 3-link chains only)");
+  if (!ok) return mz_refuse(err, errlen, "swimmer kernel: model is not a planar chain of 2..6 links on two slides (movable blocks: 2- and 3-link chains only)");
   p->nlink = nl; p->nblock = nbk; p->observe_blocks = m->observe_blocks;
   p->gz = m->gravity[2];
   const int nbd = nbk ? m->body_jntnum[m->block_bodyid[0]] : 0;
   for (int k = 0; k < nbk; k++) {
     int b = m->block_bodyid[k], j0 = m->body_jntadr[b];
-    if (nbd < 2 || nbd > 3 || m->body_dofadr[b] != nl + 2) return ant_fail(err, errlen, "swimmer kernel: movable block needs 2 or 3 slide joints right after the robot");
+    if (nbd < 2 || nbd > 3 || m->body_dofadr[b] != nl + 2) return mz_refuse(err, errlen, "swimmer kernel: movable block needs 2 or 3 slide joints right after the robot");
     p->nbdof = nbd;
     for (int a = 0; a < nbd; a++) {
       int j = j0 + a, ax = -1;
       for (int c = 0; c < 3; c++) if (fabs(m->jnt_axis[j][c] - 1.0) < 1e-12) ax = c;
-      if (m->jnt_type[j] != MZ_JNT_SLIDE || ax < 0 || (a > 0 && ax <= p->bd_axis[a - 1])) return ant_fail(err, errlen, "swimmer kernel: block joints must be slides along increasing coordinate axes");
+      if (m->jnt_type[j] != MZ_JNT_SLIDE || ax < 0 || (a > 0 && ax <= p->bd_axis[a - 1])) return mz_refuse(err, errlen, "swimmer kernel: block joints must be slides along increasing coordinate axes");
       p->bd_axis[a] = ax; p->bd_limited[a] = m->jnt_limited[j]; p->bd_lo[a] = m->jnt_range[j][0]; p->bd_hi[a] = m->jnt_range[j][1];
-      if (m->dof_armature[m->jnt_dofadr[j]] != 0.0 || m->dof_damping[m->jnt_dofadr[j]] != 0.0) return ant_fail(err, errlen, "swimmer kernel: block slides must be free of armature and damping");
+      if (m->dof_armature[m->jnt_dofadr[j]] != 0.0 || m->dof_damping[m->jnt_dofadr[j]] != 0.0) return mz_refuse(err, errlen, "swimmer kernel: block slides must be free of armature and damping");
     }
     {  // limit rows share the joint defaults (maze_env.py:607-648 sets only margin)
       double tc = fmax(m->jnt_solref[j0][0], 2.0 * m->timestep), dr = m->jnt_solref[j0][1], dmax = m->jnt_solimp[j0][1];
@@ -89,14 +89,14 @@ static inline int swimmer_dev_from_model(SwimmerDev* p, const mz_model* m, char*
   for (int a = 0; a < nl - 1; a++) { p->gear[a] = m->act_gear[a]; p->ctrl_lo[a] = m->act_ctrlrange[a][0]; p->ctrl_hi[a] = m->act_ctrlrange[a][1]; }
   for (int k = 0; k < nl + 2; k++) {
     p->armature[k] = m->dof_armature[k];
-    if (m->dof_damping[k] != 0.0) return ant_fail(err, errlen, "swimmer kernel: joint damping is not modelled (the assets have none)");
+    if (m->dof_damping[k] != 0.0) return mz_refuse(err, errlen, "swimmer kernel: joint damping is not modelled (the assets have none)");
   }
   p->density = m->density; p->viscosity = m->viscosity;
   p->inv_scale = 1.0 / (m->meaninertia * m->nv);  // MuJoCo scales the solver tolerance with the whole model
   for (int b = 0; b < nl; b++) {
     const double* I = m->body_inertia[b + 1];
     if (fabs(m->body_ipos[b + 1][1]) > 1e-12 || fabs(I[3]) + fabs(I[4]) + fabs(I[5]) > 1e-12)
-      return ant_fail(err, errlen, "swimmer kernel: links must lie on their local x axis");
+      return mz_refuse(err, errlen, "swimmer kernel: links must lie on their local x axis");
     p->mass[b] = m->body_mass[b + 1]; p->izz[b] = I[2]; p->com[b] = m->body_ipos[b + 1][0];
     p->off[b] = b == 0 ? 0.0 : m->body_pos[b + 1][0];
     p->box[b][0] = sqrt(fmax(1e-15, I[1] + I[2] - I[0]) / p->mass[b] * 6.0);
@@ -105,7 +105,7 @@ static inline int swimmer_dev_from_model(SwimmerDev* p, const mz_model* m, char*
   }
   for (int k = 0; k < nl - 1; k++) {
     int j = 3 + k;
-    if (!m->jnt_limited[j]) return ant_fail(err, errlen, "swimmer kernel: inner hinges must be limited");
+    if (!m->jnt_limited[j]) return mz_refuse(err, errlen, "swimmer kernel: inner hinges must be limited");
     p->lim_lo[k] = m->jnt_range[j][0]; p->lim_hi[k] = m->jnt_range[j][1]; p->dofw[k] = m->dof_invweight0[j];
   }
   double tc = fmax(m->jnt_solref[3][0], 2.0 * m->timestep), dr = m->jnt_solref[3][1], dmax = m->jnt_solimp[3][1];

@@ -8,6 +8,8 @@
 #include <stdlib.h>
 
 #include "../../mujoco_maze_amd/csrc/ant_dyn.h"
+#include "../../mujoco_maze_amd/csrc/mz_lanes.h"  // HostCtx
+#include "../../mujoco_maze_amd/csrc/mz_task.h"   // TaskDev, task_eval_dev
 
 template <int NB>
 static int env_step_t(const AntDev& K, int n, float* qpos, float* qvel, float* warm, int32_t* t, const float* actions, float* obs,

@@ -142,7 +142,7 @@ def view_fill_rows(cm, rows, view_off):
 
 
 def task_eval(cm, obs):
-    """task_eval_dev of csrc/ant_dyn.h on fp32 observation rows [n, obs_dim]: (reward, done, goal_idx)."""
+    """task_eval_dev of csrc/mz_task.h on fp32 observation rows [n, obs_dim]: (reward, done, goal_idx)."""
     lib = load()
     o = np.ascontiguousarray(obs, np.float32)
     n, d = o.shape

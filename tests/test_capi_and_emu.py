@@ -3,7 +3,8 @@
 * the C-ABI library loads and exports every symbol include/mazestep.h declares (no
   compute calls without a GPU);
 * the product refuses to run without a GPU (no CPU fallback);
-* the kernel's lane-group source (csrc/ant_dyn.h), compiled for the host by the
+* the kernel's lane-group source (csrc/ant_dyn.h and what every engine shares: csrc/mz_lanes.h,
+  mz_task.h, mz_maze.h), compiled for the host by the
   one-lane emulation in tests/emu, agrees with the float64 oracle after one full
   MazeEnv.step — this is how kernel logic and fp32 numerics are iterated on a box
   without a GPU; the GPU tests repeat it on the real device."""
@@ -545,3 +546,57 @@ def test_kernel_sources_carry_no_compile_time_switches():
                 bad.append(f"{f}:{i}: {line.strip()}")
     assert not bad, "\n".join(bad)
     assert subprocess.run(["make", "-C", csrc, "-n", "libmazestep.so"], capture_output=True).returncode == 0
+
+
+def test_engines_share_no_dynamics_header_and_makefiles_list_the_include_graph():
+    """The four engines are independent translation units: no unit but the Ant's reaches an Ant dynamics header, the Ant's reaches
+    no planar, general-engine or renderer header (what all of them need lives in mz_lanes.h, mz_task.h, mz_maze.h), and the
+    hand-written prerequisite lists of csrc/Makefile and tests/emu/Makefile are exactly the headers each source reaches through
+    #include "..." — a missing one lets an object (or libantemu.so, which the CPU golden tests run) go stale silently, a surplus one
+    rebuilds an engine that did not change."""
+    import subprocess
+
+    csrc = os.path.join(ROOT, "mujoco_maze_amd", "csrc")
+    emu = os.path.join(ROOT, "tests", "emu")
+
+    def closure(src):
+        seen, todo = set(), [src]
+        while todo:
+            f = todo.pop()
+            with open(f, errors="replace") as fh:
+                for inc in re.findall(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', fh.read(), re.M):
+                    p = os.path.normpath(os.path.join(os.path.dirname(f), inc))
+                    assert os.path.isfile(p), f"{f} includes {inc}"
+                    if p not in seen:
+                        seen.add(p)
+                        todo.append(p)
+        return seen
+
+    def prerequisites(mkdir):  # {target: [prerequisite, ...]} of the explicit rules, from make's own data base
+        out = subprocess.run(["make", "-pnr", "-C", mkdir], capture_output=True, text=True, env=dict(os.environ, LC_ALL="C")).stdout
+        rules = {}
+        for m in re.finditer(r"^([\w./-]+):(?!=)[ \t]*(.*)$", out, re.M):
+            rules.setdefault(m.group(1), []).extend(m.group(2).split("|")[0].split())
+        return rules
+
+    units = sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
+    assert units == ["ant_kernels.hip", "generic_kernels.hip", "mazestep.hip", "planar_kernels.hip", "render_kernels.hip"]
+    reach = {u: closure(os.path.join(csrc, u)) for u in units}
+    reach["ant_emu.cpp"] = closure(os.path.join(emu, "ant_emu.cpp"))
+    names = {u: {os.path.basename(p) for p in reach[u]} for u in reach}
+    ant_only = {"ant_dyn.h", "ant_forward_rows.h", "ant_newton_rows.h"}
+    assert ant_only <= names["ant_kernels.hip"]
+    for u in ("planar_kernels.hip", "generic_kernels.hip", "render_kernels.hip", "mazestep.hip"):
+        assert not names[u] & ant_only, (u, sorted(names[u] & ant_only))
+    others = {"planar_dyn.h", "point_bare.h", "generic_dyn.h", "mz_render.h"}
+    assert not names["ant_kernels.hip"] & others, sorted(names["ant_kernels.hip"] & others)
+
+    rules = prerequisites(csrc)
+    objects = [p for p in rules["libmazestep.so"] if p.endswith(".o")]
+    assert sorted(objects) == sorted(u[:-4] + ".o" for u in units)
+    checked = [(csrc, o, o[:-2] + ".hip", rules[o]) for o in objects] + [(emu, "libantemu.so", "ant_emu.cpp", prerequisites(emu)["libantemu.so"])]
+    for mkdir, target, src, pre in checked:
+        assert src in pre, (target, pre)
+        listed = {os.path.normpath(os.path.join(mkdir, p)) for p in pre if p != src}
+        want = reach[src]
+        assert listed == want, f"{target}: listed but not included {sorted(listed - want)}, included but not listed {sorted(want - listed)}"

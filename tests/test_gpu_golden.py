@@ -4,7 +4,7 @@ north_star: "bit-exact for termination flags and goal indices"; SURVEY §8c list
 reproduce float64 DECISIONS of the reference: the task predicates (maze_task.py:43-47,77-81,403-407) and the Point's
 manual wall rule (maze_env_utils.py:96-123,186-206; maze_env.py:457-464).  Both run here on the GPU build on ALL golden
 vectors — `mz_debug_task_eval` / `mz_debug_detect` launch the very device functions the step kernels inline
-(task_eval_dev of the handle's translation unit; point_detect / point_bounce).
+(task_eval_dev of csrc/mz_task.h as compiled into the handle's translation unit; point_detect / point_bounce of csrc/point_dyn.h).
 """
 import json
 import os

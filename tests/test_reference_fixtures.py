@@ -4,7 +4,7 @@
 * obs_layout.json pins the observation layout and the reset noise pattern of every robot family against the reference's
   own `_get_obs` / `reset_model` code.
 * The kernel sources that must reproduce the reference's float64 DECISIONS (csrc/point_dyn.h: mz_hypot, point_detect,
-  point_bounce; csrc/ant_dyn.h: task_eval_dev) are compiled for the host (tests/emu) and run on ALL golden moves /
+  point_bounce; csrc/mz_task.h: task_eval_dev) are compiled for the host (tests/emu) and run on ALL golden moves /
   observations.  The same vectors go through the HIP build in tests/test_gpu_golden.py.
 """
 import json
