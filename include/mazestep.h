@@ -278,7 +278,8 @@ int32_t mz_set_option(mz_handle* h, const char* key, double value);
  * "lanes_per_env" / "waves_per_simd" above), and the instantiations agree to fp32 round-off, not bit for bit: the same seed and
  * states give round-off-different trajectories at different num_envs, on shards of unequal size or on devices with another
  * CU count.  Keys: "engine" (0 = the robot family's specialised kernel, 1 = the general engine of mz_model.engine),
- * "lanes_per_env", "waves_per_simd", "device_simds" (4 x compute units), "ls_fast_iterations".  Returns MZ_OK or MZ_ERR_ARG. */
+ * "lanes_per_env", "waves_per_simd", "device_simds" (4 x compute units), "ls_fast_iterations", "rollout_fused" (1: mz_rollout runs
+ * this handle on its fused kernels, 0: it runs the step's launches in a loop).  Returns MZ_OK or MZ_ERR_ARG. */
 int32_t mz_get_info(const mz_handle* h, const char* key, double* value);
 
 /* Auto-reset observation convention.  With option "auto_reset" = 1 an env whose step ended its episode (done != 0) is
@@ -340,6 +341,28 @@ int32_t mz_get_state(mz_handle* h, float* qpos_dev, float* qvel_dev, float* warm
  *  info_dev    [N, 4]         position x, y, reward_forward, reward_ctrl (nullable) */
 int32_t mz_step(mz_handle* h, const float* actions_dev, float* obs_dev, float* reward_dev, uint8_t* done_dev,
                 int32_t* goal_idx_dev, float* info_dev, void* stream);
+
+/* n_steps successive steps in one call, for callers that need nothing from the host between steps: sampling planners that run
+ * pre-drawn action sequences from one state, action repeat, random-walk data collection.
+ * The call leaves the handle and every output exactly as n_steps successive mz_step calls on the same stream would: state, t,
+ * episode counters, warm start, status words, the bound final_obs buffer (under auto-reset row i is overwritten each time env i
+ * finishes) and the bound record (the last step's row).
+ *  n_steps            1 .. 65536; longer windows are split inside the call: no kernel launch advances more than 256 steps
+ *  actions_dev        step k reads its [N, nu] actions at actions_dev + k * action_step_stride floats
+ *  action_step_stride N * nu (a [n_steps, N, nu] tensor) or 0 (one [N, nu] block repeated: action repeat); else MZ_ERR_ARG
+ *  obs_dev      [N, obs_dim]           what the last step's mz_step would have written (under auto-reset the first observation
+ *                                      of the new episode for envs the last step finished)
+ *  reward_dev   [n_steps, N]           every step's reward
+ *  done_dev     [n_steps, N] u8        every step's done bits
+ *  goal_idx_dev [n_steps, N] i32       every step's goal index (nullable)
+ *  info_dev     [n_steps, N, 4]        every step's info row (nullable)
+ *  obs_seq_dev  [n_steps, N, obs_dim]  every step's observation row, i.e. what obs_dev held after that step (nullable)
+ * The Point, Swimmer and Reacher (with or without movable bodies, no top-down view) run fused kernels that keep the env on chip
+ * between steps; the Ant, the general engine and top-down-view tasks run the step's own launches n_steps times inside the call
+ * (mz_get_info key "rollout_fused": 1 / 0).  The "time_kernels" event ring does not record rollouts: mz_last_kernel_ms is
+ * unaffected by this call.  Returns MZ_OK, MZ_ERR_ARG (NULL handle or required array, n_steps or stride out of range) or MZ_ERR_HIP. */
+int32_t mz_rollout(mz_handle* h, int32_t n_steps, const float* actions_dev, int64_t action_step_stride, float* obs_dev,
+                   float* reward_dev, uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev, float* obs_seq_dev, void* stream);
 
 /* Per-env status words accumulated since the last call (then cleared). [N] i32. */
 int32_t mz_get_status(mz_handle* h, int32_t* status_dev, void* stream);

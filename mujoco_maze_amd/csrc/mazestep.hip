@@ -252,6 +252,7 @@ int32_t mz_get_info(const mz_handle* h, const char* key, double* value) {
   if (!h || !key || !value) return MZ_ERR_ARG;
   if (!strcmp(key, "engine")) { *value = h->robot == MZ_ROBOT_GENERIC ? 1.0 : 0.0; return MZ_OK; }
   if (!strcmp(key, "device_simds")) { *value = (double)h->simds; return MZ_OK; }
+  if (!strcmp(key, "rollout_fused")) { *value = (double)mzk_planar_rollout_fused(h); return MZ_OK; }  // mz_rollout: fused kernels (1) or the step's launches in a loop (0)
   if (!strcmp(key, "ls_fast_iterations")) {  // Newton iterations of a solve that take unit steps (-1: this handle's kernels have no such phase)
     *value = h->robot == MZ_ROBOT_ANT ? (double)h->ant.ls_fast_iters : (h->robot == MZ_ROBOT_POINT ? (double)h->point.unit_steps : -1.0);
     return MZ_OK;
@@ -364,13 +365,10 @@ int32_t mz_get_state(mz_handle* h, float* qpos_dev, float* qvel_dev, float* warm
   return MZ_OK;
 }
 
-int32_t mz_step(mz_handle* h, const float* actions_dev, float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t* goal_idx_dev,
-                float* info_dev, void* stream) {
-  if (!h || !actions_dev || !obs_dev || !reward_dev || !done_dev) return h ? set_err(h, MZ_ERR_ARG, "mz_step: null array", hipSuccess) : MZ_ERR_ARG;
-  DeviceScope scope(h->device);
-  hipStream_t st = (hipStream_t)stream;
-  int slot = -1;
-  if (h->ntime > 0 && (h->time_phase++ % (h->time_stride > 0 ? h->time_stride : 1)) == 0) { slot = h->itime % h->ntime; HIPCHK(h, hipEventRecord(h->ev[2 * slot], st)); }
+// one step's launches: the engine's step kernel, the top-down view of the rows it wrote, the packed record (mz_step, and mz_rollout
+// where it steps launch by launch)
+static int step_launches(mz_handle* h, hipStream_t st, const float* actions_dev, float* obs_dev, float* reward_dev, uint8_t* done_dev,
+                         int32_t* goal_idx_dev, float* info_dev) {
   if (h->robot == MZ_ROBOT_ANT) HIPCHK(h, mzk_ant_step(h, st, actions_dev, obs_dev, reward_dev, done_dev, goal_idx_dev, info_dev));
   else if (h->robot == MZ_ROBOT_GENERIC) HIPCHK(h, mzk_generic_step(h, st, actions_dev, obs_dev, reward_dev, done_dev, goal_idx_dev, info_dev));
   else HIPCHK(h, mzk_planar_step(h, st, actions_dev, obs_dev, reward_dev, done_dev, goal_idx_dev, info_dev));
@@ -380,8 +378,51 @@ int32_t mz_step(mz_handle* h, const float* actions_dev, float* obs_dev, float* r
     hipLaunchKernelGGL(pack_record_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, h->n, h->model.obs_dim, obs_dev, reward_dev, done_dev, h->record);
   }
   HIPCHK(h, hipGetLastError());
+  return MZ_OK;
+}
+
+int32_t mz_step(mz_handle* h, const float* actions_dev, float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t* goal_idx_dev,
+                float* info_dev, void* stream) {
+  if (!h || !actions_dev || !obs_dev || !reward_dev || !done_dev) return h ? set_err(h, MZ_ERR_ARG, "mz_step: null array", hipSuccess) : MZ_ERR_ARG;
+  DeviceScope scope(h->device);
+  hipStream_t st = (hipStream_t)stream;
+  int slot = -1;
+  if (h->ntime > 0 && (h->time_phase++ % (h->time_stride > 0 ? h->time_stride : 1)) == 0) { slot = h->itime % h->ntime; HIPCHK(h, hipEventRecord(h->ev[2 * slot], st)); }
+  const int rc = step_launches(h, st, actions_dev, obs_dev, reward_dev, done_dev, goal_idx_dev, info_dev);
+  if (rc != MZ_OK) return rc;
   if (slot >= 0) { HIPCHK(h, hipEventRecord(h->ev[2 * slot + 1], st)); h->itime++; }
   h->nsteps++;
+  return MZ_OK;
+}
+
+// n_steps successive mz_step calls in one (include/mazestep.h).  Fused handles (mzk_planar_rollout_fused) advance up to
+// MZ_ROLLOUT_CHUNK steps per launch on a state that stays on chip; every other handle runs the step's own launches n_steps times
+// with the output pointers advanced, which is sequential stepping by construction.
+int32_t mz_rollout(mz_handle* h, int32_t n_steps, const float* actions_dev, int64_t action_step_stride, float* obs_dev, float* reward_dev,
+                   uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev, float* obs_seq_dev, void* stream) {
+  if (!h || !actions_dev || !obs_dev || !reward_dev || !done_dev) return h ? set_err(h, MZ_ERR_ARG, "mz_rollout: null array", hipSuccess) : MZ_ERR_ARG;
+  if (n_steps < 1 || n_steps > 65536) return set_err(h, MZ_ERR_ARG, "mz_rollout: n_steps must be 1 .. 65536", hipSuccess);
+  const size_t n = (size_t)h->n, od = (size_t)h->model.obs_dim;
+  if (action_step_stride != 0 && action_step_stride != (int64_t)n * h->model.nu)
+    return set_err(h, MZ_ERR_ARG, "mz_rollout: action_step_stride must be num_envs * nu ([K, N, nu] actions) or 0 (one [N, nu] block repeated)", hipSuccess);
+  DeviceScope scope(h->device);
+  hipStream_t st = (hipStream_t)stream;
+  if (mzk_planar_rollout_fused(h)) {
+    HIPCHK(h, mzk_planar_rollout(h, st, n_steps, actions_dev, (long)action_step_stride, obs_dev, reward_dev, done_dev, goal_idx_dev, info_dev, obs_seq_dev));
+    if (h->record) {  // the last step's row
+      const size_t tot = n * (od + 2), last = (size_t)(n_steps - 1) * n;
+      hipLaunchKernelGGL(pack_record_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, h->n, h->model.obs_dim, obs_dev, reward_dev + last, done_dev + last, h->record);
+      HIPCHK(h, hipGetLastError());
+    }
+  } else {
+    for (size_t k = 0; k < (size_t)n_steps; k++) {
+      const int rc = step_launches(h, st, actions_dev + k * (size_t)action_step_stride, obs_dev, reward_dev + k * n, done_dev + k * n,
+                                   goal_idx_dev ? goal_idx_dev + k * n : NULL, info_dev ? info_dev + k * n * 4 : NULL);
+      if (rc != MZ_OK) return rc;
+      if (obs_seq_dev) HIPCHK(h, hipMemcpyAsync(obs_seq_dev + k * n * od, obs_dev, n * od * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
+  }
+  h->nsteps += n_steps;
   return MZ_OK;
 }
 

@@ -84,6 +84,12 @@ hipError_t mzk_point_detect(mz_handle* h, hipStream_t st, int n, const double* o
 // MazeEnv.get_top_down_view into the rows the step / reset kernel just wrote (no-op unless the task has TOP_DOWN_VIEW):
 // every row of obs, and the rows of final_obs of envs that finished (done != NULL: the step under auto-reset)
 hipError_t mzk_view_fill(mz_handle* h, hipStream_t st, float* obs, float* final_obs, const uint8_t* done);
+// mz_rollout on the fused kernels (Point / Swimmer / Reacher without a top-down view): no launch advances more than
+// MZ_ROLLOUT_CHUNK steps, which bounds a kernel's duration
+constexpr int MZ_ROLLOUT_CHUNK = 256;
+int mzk_planar_rollout_fused(const mz_handle* h);
+hipError_t mzk_planar_rollout(mz_handle* h, hipStream_t st, int nsteps, const float* actions, long astride, float* obs, float* reward,
+                              uint8_t* done, int* goal_idx, float* info, float* obs_seq);
 int mzk_planar_state_width(const mz_handle* h);  // coordinates per env of the state (NV)
 int mzk_planar_record_width(const mz_handle* h); // Point: floats per env-major record; 0 for the chains (SoA)
 

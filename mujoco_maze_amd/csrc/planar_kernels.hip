@@ -3,6 +3,7 @@
 //   planar_step_kernel<NB,NS,G>  one MazeEnv.step for the Point (+ NB movable blocks or NS object balls): lane group
 //                                per env, PlanarScratch in LDS, fp64.
 //   swimmer_step_kernel<NL,NB,G> one MazeEnv.step for the Swimmer (NL = 3) / Reacher (NL = 2): G = 4 lanes per env (lane b = link b), fp64.
+//   planar_rollout_kernel / swimmer_rollout_kernel  up to MZ_ROLLOUT_CHUNK steps of the same on a state that stays on chip (mz_rollout).
 //   reset / state copy kernels; debug kernels for the parity tests (task predicates, the Point's wall detector).
 //
 // HBM layout: SoA  q_0..q_{NV-1} | v_0..v_{NV-1}, each [N] fp32; t[N], episode[N] i32.  API arrays are row-major [N, k].
@@ -127,6 +128,104 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && 
   if (!live) env = n - 1;  // idle groups shadow the last env (no stores) so that every lane reaches the wave-level votes
   planar_step_body<NB, NS, G>(P, scr[grp], obuf[grp], cx, n, S, env, live, actions, obs, reward, done, goal_idx, info, status, auto_reset, seed, env0, final_obs,
                               ostride);
+}
+
+// `nsteps` (<= MZ_ROLLOUT_CHUNK) successive planar_step_kernel launches in one (mz_rollout): PointDev and the env's state are loaded
+// once, the steps run on the state in LDS, the state is stored once.  Between two steps the state takes exactly the values the HBM
+// round trip of separate launches gives it — q, v and the bare Point's warm start rounded to fp32 and widened again, t and the episode
+// counter carried as ints — so the outputs equal those of sequential stepping bit for bit.  Step k reads its actions at
+// actions + k * astride and writes row k of reward / done / goal_idx / info / obs_seq ([nsteps][n][..]; obs_seq nullable); `obs` gets
+// the row of step last_obs_step only (-1: none — a later launch of the same rollout writes it).  No top-down view: rows are NOBS floats apart.
+template <int NB, int NS, int G>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && NS == 0 && G == 32) ? 2 : 1))) void planar_rollout_kernel(
+    const PointDev* __restrict__ Pp, int n, PointState S, int nsteps, const float* __restrict__ actions, long astride, float* __restrict__ obs,
+    int last_obs_step, float* __restrict__ reward, uint8_t* __restrict__ done, int* __restrict__ goal_idx, float* __restrict__ info,
+    float* __restrict__ obs_seq, int* __restrict__ status, int auto_reset, uint64_t seed, uint64_t env0, float* __restrict__ final_obs) {
+  using D = PlanarDims<NB, NS>;
+  constexpr int NV = D::NV, NOBS = D::NOBS, EPW = 64 / G;
+  constexpr bool BARE = NB == 0 && NS == 0;
+  __shared__ PointDev P;
+  __shared__ PlanarScratch<NB, NS> scr[EPW];
+  __shared__ float obuf[EPW][MZ_MAX_OBS];
+  for (int i = threadIdx.x; i < (int)(sizeof(PointDev) / 4); i += blockDim.x) ((uint32_t*)&P)[i] = ((const uint32_t*)Pp)[i];
+  __syncthreads();
+  DevCtx<G> cx{(int)threadIdx.x % G};
+  const int grp = threadIdx.x / G;
+  int env = xcd_block(blockIdx.x, gridDim.x) * EPW + grp;
+  const bool live = env < n;
+  if (!live) env = n - 1;  // idle groups shadow the last env (no stores), as in planar_step_kernel
+  PlanarScratch<NB, NS>& s = scr[grp];
+  float* o = obuf[grp];
+  for (int k = cx.l; k < NV; k += G) { s.q[k] = (double)st_q(S, n, NV, k, env); s.v[k] = (double)st_v(S, n, NV, k, env); }
+  if constexpr (BARE) { for (int k = cx.l; k < 3; k += G) s.wds[k] = (double)S.qv[(size_t)env * S.rec + PT_WARM_OFF + k]; }
+  int t = st_t(S, NV, env), stacc = 0;
+  uint32_t ep = st_ep(S, NV, env);
+  for (int step = 0; step < nsteps; step++) {
+    const float* act = actions + (size_t)step * astride + (size_t)env * 2;
+    double a[2] = {(double)act[0], (double)act[1]};
+    cx.sync();
+    planar_env_step<NB, NS>(cx, P, s, a);
+    const int t_new = t + 1;
+    for (int i = cx.l; i < NOBS; i += G) o[i] = planar_obs_elem<NB, NS>(P, s, i, t_new);
+    cx.sync();
+    float outer; int tm, gi;
+    task_eval_dev(P.task, o, &outer, &tm, &gi, env);
+    const uint8_t d = (uint8_t)((tm ? 1 : 0) | (t_new >= P.task.max_steps ? 2 : 0));
+    const bool rst = auto_reset && d;
+    const size_t row = (size_t)step * n + env;
+    float* oseq = obs_seq ? obs_seq + row * NOBS : nullptr;
+    float* olast = step == last_obs_step ? obs + (size_t)env * NOBS : nullptr;
+    if (live) {
+      if (rst) {
+        if (final_obs) for (int i = cx.l; i < NOBS; i += G) final_obs[(size_t)env * NOBS + i] = o[i];
+      } else {
+        if (oseq) for (int i = cx.l; i < NOBS; i += G) oseq[i] = o[i];
+        if (olast) for (int i = cx.l; i < NOBS; i += G) olast[i] = o[i];
+      }
+      if (cx.l == 0) {
+        reward[row] = outer;
+        done[row] = d;
+        if (goal_idx) goal_idx[row] = gi;
+        if (info) { info[row * 4] = o[0]; info[row * 4 + 1] = o[1]; info[row * 4 + 2] = 0.f; info[row * 4 + 3] = 0.f; }
+        int st = s.status;
+        bool badv = false;
+        for (int k = 0; k < NV; k++) badv = badv || !(fabs(s.q[k]) < 1e10) || !(fabs(s.v[k]) < 1e10);
+        if (badv) st |= MZ_STATUS_BAD_STATE;
+        stacc |= st;
+      }
+    }
+    cx.sync();  // lane 0 has read the whole state
+    if (rst) {
+      ep += 1;
+      const uint64_t es = episode_seed(seed, ep);
+      for (int k = cx.l; k < NV; k += G) {
+        s.q[k] = k < 3 ? (double)reset_qpos((float)P.qpos0[k], es, env0 + (uint64_t)env, k) : 0.0;
+        s.v[k] = k < 3 ? (double)reset_qvel(P.reset_kind, NV, es, env0 + (uint64_t)env, k) : 0.0;
+      }
+      cx.sync();
+      if (live) {
+        if (oseq) for (int i = cx.l; i < NOBS; i += G) oseq[i] = planar_obs_elem<NB, NS>(P, s, i, 0);
+        if (olast) for (int i = cx.l; i < NOBS; i += G) olast[i] = planar_obs_elem<NB, NS>(P, s, i, 0);
+      }
+      cx.sync();
+    }
+    t = rst ? 0 : t_new;
+    // the state as the next launch of planar_step_kernel would load it
+    for (int k = cx.l; k < NV; k += G) { s.q[k] = (double)(float)s.q[k]; s.v[k] = (double)(float)s.v[k]; }
+    if constexpr (BARE) { for (int k = cx.l; k < 3; k += G) s.wds[k] = rst ? 0.0 : (double)(float)s.wds[k]; }
+  }
+  cx.sync();
+  if (live) {
+    for (int k = cx.l; k < NV; k += G) {
+      st_q(S, n, NV, k, env) = (float)s.q[k];
+      st_v(S, n, NV, k, env) = (float)s.v[k];
+    }
+    if (cx.l == 0) {
+      st_t(S, NV, env) = t; st_ep(S, NV, env) = ep;
+      if (stacc) atomicOr(&status[env], stacc);
+    }
+    if constexpr (BARE) { for (int k = cx.l; k < 3; k += G) S.qv[(size_t)env * S.rec + PT_WARM_OFF + k] = (float)s.wds[k]; }
+  }
 }
 
 template <int NB, int NS>
@@ -276,6 +375,81 @@ __global__ __launch_bounds__(256) void swimmer_step_kernel(const SwimmerDev* __r
   S.ep[env] = ep;
 }
 
+// `nsteps` successive swimmer_step_kernel launches in one (mz_rollout; arguments as planar_rollout_kernel): the fp32 state stays in
+// registers.  A separate launch hands every lane of a group the state its first lane stored, so after each step the group takes its
+// first lane's state (and the episode verdict that follows from it) before it goes on.
+template <int NL, int NB, int G>
+__global__ __launch_bounds__(256) void swimmer_rollout_kernel(const SwimmerDev* __restrict__ Pp, int n, PointState S, int nsteps,
+                                                               const float* __restrict__ actions, long astride, float* __restrict__ obs,
+                                                               int last_obs_step, float* __restrict__ reward, uint8_t* __restrict__ done,
+                                                               int* __restrict__ goal_idx, float* __restrict__ info, float* __restrict__ obs_seq,
+                                                               int* __restrict__ status, int auto_reset, uint64_t seed, uint64_t env0,
+                                                               float* __restrict__ final_obs) {
+  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+  int env = gid / G;
+  const SwimmerCtx<G> cx{(int)(threadIdx.x % G)};
+  const bool live = env < n && cx.l == 0;
+  if (env >= n) env = n - 1;  // surplus groups shadow the last env (no stores)
+  constexpr int NR = NL + 2, NV = NR + NB, NH = NL - 1;
+  const SwimmerDev& P = *Pp;
+  const int nb3 = (NB && P.observe_blocks) ? 3 : 0, NO = 2 * NV + 1 + nb3;
+  float qf[NV], vf[NV], af[NH > 0 ? NH : 1], o[2 * NV + 4];
+  double inner, inf4[4];
+  for (int k = 0; k < NV; k++) { qf[k] = S.qv[(size_t)k * n + env]; vf[k] = S.qv[(size_t)(NV + k) * n + env]; }
+  int t = S.t[env], stacc = 0;
+  uint32_t ep = S.ep[env];
+  const int lane0 = (int)(threadIdx.x & 63u) - cx.l;
+  for (int step = 0; step < nsteps; step++) {
+    const float* act = actions + (size_t)step * astride + (size_t)env * NH;
+    for (int k = 0; k < NH; k++) af[k] = act[k];
+    int t_new;
+    stacc |= swimmer_maze_step<NL, NB>(P, qf, vf, af, t, o, &inner, inf4, &t_new, cx);
+    for (int k = 0; k < NV; k++) { qf[k] = __shfl(qf[k], lane0, 64); vf[k] = __shfl(vf[k], lane0, 64); }
+    swimmer_obs_row<NL, NB>(P, qf, vf, t_new, o);
+    float outer; int tm, gi;
+    task_eval_dev(P.task, o, &outer, &tm, &gi, env);
+    const uint8_t d = (uint8_t)((tm ? 1 : 0) | (t_new >= P.task.max_steps ? 2 : 0));
+    const bool rst = auto_reset && d;
+    const size_t row = (size_t)step * n + env;
+    float* oseq = obs_seq ? obs_seq + row * NO : nullptr;
+    float* olast = step == last_obs_step ? obs + (size_t)env * NO : nullptr;
+    if (live) {
+      if (rst) {
+        if (final_obs) swimmer_store_row<NL, NB>(P, qf, o, NO, NO, final_obs + (size_t)env * NO);
+      } else {
+        if (oseq) swimmer_store_row<NL, NB>(P, qf, o, NO, NO, oseq);
+        if (olast) swimmer_store_row<NL, NB>(P, qf, o, NO, NO, olast);
+      }
+      reward[row] = (float)(P.task.inner_scale * inner) + outer;
+      done[row] = d;
+      if (goal_idx) goal_idx[row] = gi;
+      if (info) for (int k = 0; k < 4; k++) info[row * 4 + k] = (float)inf4[k];
+    }
+    if (rst) {
+      ep += 1; t_new = 0;
+      const uint64_t es = episode_seed(seed, ep);
+      for (int k = 0; k < NV; k++) {
+        qf[k] = reset_qpos(k < NR ? (float)P.qpos0[k] : 0.f, es, env0 + (uint64_t)env, k);
+        vf[k] = reset_qvel(P.reset_kind, NV, es, env0 + (uint64_t)env, k);
+      }
+      if (live && (oseq || olast)) {
+        swimmer_obs_row<NL, NB>(P, qf, vf, 0, o);
+        if (oseq) swimmer_store_row<NL, NB>(P, qf, o, NO, NO, oseq);
+        if (olast) swimmer_store_row<NL, NB>(P, qf, o, NO, NO, olast);
+      }
+    }
+    t = t_new;
+  }
+  if (!live) return;
+  for (int k = 0; k < NV; k++) {
+    S.qv[(size_t)k * n + env] = qf[k];
+    S.qv[(size_t)(NV + k) * n + env] = vf[k];
+  }
+  S.t[env] = t;
+  S.ep[env] = ep;
+  if (stacc) atomicOr(&status[env], stacc);
+}
+
 template <int NL, int NB>
 __global__ void swimmer_reset_kernel(const SwimmerDev* Pp, int n, PointState S, const uint8_t* mask, uint64_t seed, uint64_t env0, float* obs,
                                      int ostride) {
@@ -417,6 +591,64 @@ hipError_t mzk_planar_step(mz_handle* h, hipStream_t st, const float* actions_de
   }
 #undef MZ_PLANAR_LAUNCH
   return hipGetLastError();
+}
+
+// mz_rollout: does this handle take the fused kernels below?  (A top-down view is filled by a kernel of its own after every step,
+// so such handles — like the Ant and the general engine — step launch by launch inside mz_rollout.)
+int mzk_planar_rollout_fused(const mz_handle* h) {
+  return (h->robot == MZ_ROBOT_POINT || h->robot == MZ_ROBOT_SWIMMER) && !h->view.on;
+}
+
+// steps k = 0 .. nsteps - 1 of a rollout in launches of at most MZ_ROLLOUT_CHUNK steps, each with the launch geometry of the step
+// kernel it stands for; arrays as in mz_rollout (include/mazestep.h)
+hipError_t mzk_planar_rollout(mz_handle* h, hipStream_t st, int nsteps, const float* actions_dev, long astride, float* obs_dev, float* reward_dev,
+                              uint8_t* done_dev, int* goal_idx_dev, float* info_dev, float* obs_seq_dev) {
+  PointState S{h->state, h->pt_t, h->pt_ep, h->pt_rec};
+  const size_t n = (size_t)h->n, od = (size_t)h->model.obs_dim;
+  for (int k0 = 0; k0 < nsteps; k0 += MZ_ROLLOUT_CHUNK) {
+    const int ks = nsteps - k0 < MZ_ROLLOUT_CHUNK ? nsteps - k0 : MZ_ROLLOUT_CHUNK;
+    const int last = k0 + ks == nsteps ? ks - 1 : -1;  // the launch that holds the rollout's last step writes obs_dev
+    const float* act = actions_dev + (size_t)k0 * astride;
+    float* rew = reward_dev + k0 * n;
+    uint8_t* dn = done_dev + k0 * n;
+    int* gi = goal_idx_dev ? goal_idx_dev + k0 * n : nullptr;
+    float* inf = info_dev ? info_dev + k0 * n * 4 : nullptr;
+    float* oseq = obs_seq_dev ? obs_seq_dev + k0 * n * od : nullptr;
+    if (h->robot == MZ_ROBOT_SWIMMER) {
+#define MZ_SW_ROLL(NL, NB)                                                                                                          \
+  hipLaunchKernelGGL((swimmer_rollout_kernel<NL, NB, (NL <= 4 ? 4 : 8)>), dim3((unsigned)((n * (NL <= 4 ? 4 : 8) + sw_bd - 1) / sw_bd)), dim3(sw_bd), 0, st, \
+                     h->swimmer_dev, h->n, S, ks, act, astride, obs_dev, last, rew, dn, gi, inf, oseq, h->status, h->auto_reset, h->seed, h->env0, h->final_obs)
+      const int bd = h->swimmer.nblock ? h->swimmer.nbdof : 0;
+      const unsigned sw_bd = 64u * (unsigned)(h->wpb_set ? h->waves_per_block : 4);
+      if (h->swimmer.nlink == 3) { if (bd == 3) MZ_SW_ROLL(3, 3); else if (bd == 2) MZ_SW_ROLL(3, 2); else MZ_SW_ROLL(3, 0); }
+      else if (h->swimmer.nlink == 2) { if (bd == 3) MZ_SW_ROLL(2, 3); else if (bd == 2) MZ_SW_ROLL(2, 2); else MZ_SW_ROLL(2, 0); }
+      else if (h->swimmer.nlink == 4) MZ_SW_ROLL(4, 0);
+      else if (h->swimmer.nlink == 5) MZ_SW_ROLL(5, 0);
+      else MZ_SW_ROLL(6, 0);
+#undef MZ_SW_ROLL
+    } else {
+#define MZ_PLANAR_ROLL(NB, NS, G)                                                                                                      \
+  hipLaunchKernelGGL((planar_rollout_kernel<NB, NS, G>), dim3((h->n + 64 / G - 1) / (64 / G)), dim3(64), 0, st, h->point_dev, h->n, S, ks, act, astride, \
+                     obs_dev, last, rew, dn, gi, inf, oseq, h->status, h->auto_reset, h->seed, h->env0, h->final_obs)
+      if (h->point.nball) MZ_PLANAR_ROLL(0, 1, 32);
+      else switch (h->point.nblock) {
+        case 0: {
+          const int lanes = mzk_planar_lanes(h);  // the step's rule
+          if (lanes == 8) MZ_PLANAR_ROLL(0, 0, 8);
+          else if (lanes == 16) MZ_PLANAR_ROLL(0, 0, 16);
+          else MZ_PLANAR_ROLL(0, 0, 32);
+          break;
+        }
+        case 1: MZ_PLANAR_ROLL(1, 0, 32); break;
+        case 2: MZ_PLANAR_ROLL(2, 0, 64); break;
+        default: MZ_PLANAR_ROLL(3, 0, 64); break;
+      }
+#undef MZ_PLANAR_ROLL
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 hipError_t mzk_planar_reset(mz_handle* h, hipStream_t st, const uint8_t* mask_dev, uint64_t seed, float* obs_dev) {

@@ -214,10 +214,11 @@ class VecMazeEnv:
 
     def launch_info(self) -> dict:
         """What the next step launches (mz_get_info): the engine (0 = the robot family's specialised kernel, 1 = the general engine),
-        lanes per env, waves per SIMD, the device's SIMD count.  The instantiation depends on the batch size and the device; its
+        lanes per env, waves per SIMD, the device's SIMD count, and whether rollout() runs this env on fused kernels ("rollout_fused":
+        1) or on the step's launches in a loop (0).  The instantiation depends on the batch size and the device; its
         results agree across instantiations to fp32 round-off, not bit for bit (include/mazestep.h)."""
         out = {}
-        for key in ("engine", "lanes_per_env", "waves_per_simd", "device_simds", "ls_fast_iterations"):
+        for key in ("engine", "lanes_per_env", "waves_per_simd", "device_simds", "ls_fast_iterations", "rollout_fused"):
             v = C.c_double(0.0)
             _capi.check(self._lib, self._h, self._lib.mz_get_info(self._h, key.encode(), C.byref(v)), f"mz_get_info({key})")
             out[key] = int(v.value)
@@ -407,6 +408,65 @@ class VecMazeEnv:
         if self._auto_reset:
             info["final_observation"] = self._final_obs  # valid in the rows where done != 0
         return self._obs, self._reward, self._done, info
+
+    def rollout(self, actions, repeat: Optional[int] = None, return_obs: bool = False):
+        """K steps in one call, for callers that need nothing from the host between steps (sampling planners on pre-drawn action
+        sequences, action repeat, random walks): the results and the env's state afterwards are exactly those of K `step()` calls.
+
+        actions: float32 [K, N, nu] on the same GPU — or [N, nu] with `repeat=K`, the same actions held for K steps.
+        Returns (obs, rewards [K, N], dones [K, N] uint8, info): `obs` [N, obs_dim] is what the last step returned; info holds
+        "goal_index" [K, N], "position" [K, N, 2], "reward_forward" / "reward_ctrl" [K, N], "observations" [K, N, obs_dim] with
+        `return_obs`, and under auto-reset "final_observation" (row i: the last terminal observation of env i).  The output tensors
+        are reused by the next rollout of the same K.
+
+        One mz_rollout call (fused kernels for the Point, Swimmer and Reacher: `launch_info()["rollout_fused"]`) — except where the
+        host has work between steps (Python reward()/termination() overrides; per-env goals under auto-reset, which are resampled
+        after every step): there this method calls `step()` K times itself and stacks the results."""
+        torch, n = self._torch, self.num_envs
+        a = actions if torch.is_tensor(actions) else torch.as_tensor(np.asarray(actions, dtype=np.float32), device=self.device)
+        if a.dtype != torch.float32 or not a.is_contiguous() or a.device != self.device:
+            a = a.to(device=self.device, dtype=torch.float32).contiguous()
+        if repeat is not None:
+            K = int(repeat)
+            if tuple(a.shape) != (n, self.nu):
+                raise ValueError(f"with repeat, actions must have shape {(n, self.nu)}, got {tuple(a.shape)}")
+        else:
+            if a.dim() != 3 or tuple(a.shape[1:]) != (n, self.nu):
+                raise ValueError(f"actions must have shape (K, {n}, {self.nu}) — or {(n, self.nu)} with repeat=K —, got {tuple(a.shape)}")
+            K = int(a.shape[0])
+        if not 1 <= K <= 65536:
+            raise ValueError(f"a rollout takes 1 .. 65536 steps, got {K}")
+        buf = self._rollout_buffers(K, return_obs)
+        if self._host_rewards or (self._env_goals is not None and self._auto_reset):
+            for k in range(K):
+                obs, rew, done, inf = self.step(a if repeat is not None else a[k])
+                buf["reward"][k], buf["done"][k], buf["goal"][k], buf["info"][k] = rew, done, inf["goal_index"], self._info
+                if return_obs:
+                    buf["obs_seq"][k] = obs
+        else:
+            rc = self._lib.mz_rollout(self._h, K, _ptr(a), 0 if repeat is not None else n * self.nu, _ptr(self._obs), _ptr(buf["reward"]),
+                                      _ptr(buf["done"]), _ptr(buf["goal"]), _ptr(buf["info"]), _ptr(buf["obs_seq"]) if return_obs else None,
+                                      self._stream())
+            _capi.check(self._lib, self._h, rc, "mz_rollout")
+        info = {"position": buf["info"][:, :, :2], "reward_forward": buf["info"][:, :, 2], "reward_ctrl": buf["info"][:, :, 3],
+                "goal_index": buf["goal"]}
+        if return_obs:
+            info["observations"] = buf["obs_seq"]
+        if self._auto_reset:
+            info["final_observation"] = self._final_obs
+        return self._obs, buf["reward"], buf["done"], info
+
+    def _rollout_buffers(self, K: int, with_obs: bool) -> dict:
+        """Output tensors of rollout(), allocated per K and kept."""
+        torch, n, dev = self._torch, self.num_envs, self.device
+        cache = self.__dict__.setdefault("_rollout_cache", {})
+        buf = cache.get(K)
+        if buf is None:
+            buf = cache[K] = {"reward": torch.empty((K, n), dtype=torch.float32, device=dev), "done": torch.empty((K, n), dtype=torch.uint8, device=dev),
+                              "goal": torch.empty((K, n), dtype=torch.int32, device=dev), "info": torch.empty((K, n, 4), dtype=torch.float32, device=dev)}
+        if with_obs and "obs_seq" not in buf:
+            buf["obs_seq"] = torch.empty((K, n, self.obs_dim), dtype=torch.float32, device=dev)
+        return buf
 
     def _apply_host_task(self):
         """User-defined Python reward()/termination(): evaluated on the host from the obs batch (one device-to-host copy

@@ -1,0 +1,93 @@
+"""K = 64 steps as 64 `env.step` calls against one `env.rollout` of the same [64, N, nu] action tensor, at 4096 envs under auto-reset:
+PointUMaze-v0, SwimmerUMaze-v0, ReacherUMaze-v0, PointPush-v0 (fused kernels) and AntUMaze-v0 (the step's launches in a loop inside
+mz_rollout).  Both legs run in one process, alternating, three repeats each after a warm-up of both; a leg repeats its window until
+at least `--seconds` of work has passed, with a device synchronise around the host clock.  Whole-call wall clock, inputs resident.
+    python tools/rollout_bench.py [--envs N] [--steps K] [--seconds S] [--repeats R] [--ids a,b,..] [--out FILE]
+Kernel durations come from a run of their own:  rocprofv3 --kernel-trace --stats -d <dir> -- python tools/rollout_bench.py --seconds 0.2"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import mujoco_maze_amd as mm  # noqa: E402
+
+IDS = ["PointUMaze-v0", "SwimmerUMaze-v0", "ReacherUMaze-v0", "PointPush-v0", "AntUMaze-v0"]
+
+
+def leg(fn, windows_min, seconds, dev):
+    """env-steps per second of `fn` (one K-step window per call): windows until `seconds` have passed, at least `windows_min`."""
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    done = 0
+    while True:
+        for _ in range(windows_min):
+            fn()
+        done += windows_min
+        torch.cuda.synchronize(dev)
+        dt = time.perf_counter() - t0
+        if dt >= seconds:
+            return done, dt
+
+
+def bench(env_id, n, K, seconds, repeats):
+    dev = torch.device("cuda", 0)
+    env = mm.make(env_id, num_envs=n, auto_reset=True, device=dev, force_vec=True)
+    env.reset(seed=20260928)
+    g = torch.Generator(device=dev).manual_seed(1234)
+    lo, hi = torch.as_tensor(env.action_space.low, device=dev), torch.as_tensor(env.action_space.high, device=dev)
+    acts = (lo + (hi - lo) * torch.rand((K, n, env.nu), device=dev, generator=g)).contiguous()
+    rows = [acts[k] for k in range(K)]
+
+    def stepping():
+        for k in range(K):
+            env.step(rows[k])
+
+    def rollout():
+        env.rollout(acts)
+
+    for _ in range(4):  # warm-up of both legs: code objects loaded, output tensors of this K allocated, episodes in their steady mix
+        stepping(); rollout()
+    res = {"step": [], "rollout": []}
+    for _ in range(repeats):
+        for name, fn in (("step", stepping), ("rollout", rollout)):
+            w, dt = leg(fn, 4, seconds, dev)
+            res[name].append(n * K * w / dt)
+    bad = int((env.status() & 3).ne(0).sum())
+    fused = env.launch_info()["rollout_fused"]
+    env.close()
+    return {"env": env_id, "envs": n, "steps_per_window": K, "fused": fused, "flagged_envs": bad,
+            "step_env_steps_per_s": res["step"], "rollout_env_steps_per_s": res["rollout"]}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--steps", type=int, default=64)
+    ap.add_argument("--seconds", type=float, default=1.0, help="least duration of one timed leg")
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--ids", type=str, default=",".join(IDS))
+    ap.add_argument("--out", type=str, default=None, help="also write the rows as JSON lines")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "rollout_bench.py measures on the GPU only"
+    out = []
+    print(f"{args.steps} x env.step against one env.rollout, {args.envs} envs, auto-reset, >= {args.seconds} s per leg, {args.repeats} alternating repeats")
+    print("%-18s %5s %14s %10s %14s %10s %7s" % ("env", "fused", "step M/s", "spread", "rollout M/s", "spread", "ratio"))
+    for env_id in args.ids.split(","):
+        r = bench(env_id, args.envs, args.steps, args.seconds, args.repeats)
+        out.append(r)
+        s, ro = r["step_env_steps_per_s"], r["rollout_env_steps_per_s"]
+        med = lambda v: sorted(v)[len(v) // 2]
+        print("%-18s %5d %12.3f M %8.3f M %12.3f M %8.3f M %7.2f" % (env_id, r["fused"], med(s) / 1e6, (max(s) - min(s)) / 1e6, med(ro) / 1e6,
+                                                                  (max(ro) - min(ro)) / 1e6, med(ro) / med(s)), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            for r in out:
+                f.write(json.dumps(r) + "\n")
+
+
+if __name__ == "__main__":
+    main()
