@@ -378,11 +378,18 @@ __device__ __forceinline__ float ant_forward_rows(const DevCtx<G, PROF>& cx_step
     cin[9] = dax * w[1] * w[2] - m * com[1] * com[2];
   }
   float Ip[10];  // composite inertia of this lane's dof: whole body (root), aux + ankle (hip), ankle (ankle)
+  // the whole body's sums and own + ankle's (hip lanes), three at a time where both are plain additions (rows::rsum3_q1).  Not for
+  // cin[1 .. 3]: they are bare products m * com, and `cin[k] + ank` is contracted into fma(m, com, ank) — formed by hand from the
+  // rounded product it would differ in the last bit; those keep the compiler's broadcast + fma next to rsum3
+  float call[10], cank[10];
+  call[0] = rsum(cin[0]);
+  rsum3(cin[1], cin[2], cin[3], call[1], call[2], call[3]);
 #pragma unroll
-  for (int k = 0; k < 10; k++) {
-    const float all = rsum(cin[k]), ank = qbcast<1>(cin[k]);
-    Ip[k] = role(cin[k] + ank, cin[k], all, all);
-  }
+  for (int k = 0; k < 4; k++) cank[k] = cin[k] + qbcast<1>(cin[k]);
+  rsum3_q1(cin[4], cin[5], cin[6], call[4], call[5], call[6], cank[4], cank[5], cank[6]);
+  rsum3_q1(cin[7], cin[8], cin[9], call[7], call[8], call[9], cank[7], cank[8], cank[9]);
+#pragma unroll
+  for (int k = 0; k < 10; k++) Ip[k] = role(cank[k], cin[k], call[k], call[k]);
   // ---- motion axis of this lane's dof at the torso origin: [angular; linear]
   float S[6];
   {
@@ -454,12 +461,11 @@ __device__ __forceinline__ float ant_forward_rows(const DevCtx<G, PROF>& cx_step
     force_crossf(vf, vb, Iv);
     for (int k = 0; k < 6; k++) f[k] = Ia[k] + vf[k];
     // force on the subtree of this lane's dof: ankle = its body; hip = aux + ankle; root = all bodies
-    float bias = 0.f;
+    float bias = 0.f, fall[6], fank[6];
+    rsum3_q1(f[0], f[1], f[2], fall[0], fall[1], fall[2], fank[0], fank[1], fank[2]);
+    rsum3_q1(f[3], f[4], f[5], fall[3], fall[4], fall[5], fank[3], fank[4], fank[5]);
 #pragma unroll
-    for (int k = 0; k < 6; k++) {
-      const float all = rsum(f[k]), ank = qbcast<1>(f[k]);
-      bias += S[k] * role(f[k] + ank, f[k], all, all);
-    }
+    for (int k = 0; k < 6; k++) bias += S[k] * role(fank[k], f[k], fall[k], fall[k]);
     const float fact = s.fact[hinge ? pos2dof(p) : 6];  // motors sit on the hinges only
     qfs = bsel(mh, -ant_u(cx, K).damping * bsel(m0, qdh, qda) - bias + fact, bsel(-(int)isroot, -bias, 0.f));
     if constexpr (NB == 1) {  // block slides: undamped, unactuated; gravity acts on a z slide (falling blocks)

@@ -38,12 +38,14 @@ __host__ __device__ __forceinline__ constexpr int pos2dof(int p) { return (p & 3
 __host__ __device__ __forceinline__ constexpr int dof2pos(int d) { return d < 6 ? 4 * (d >> 1) + 2 + (d & 1) : (d < 14 ? 4 * ((d - 6) >> 1) + ((d - 6) & 1) : d); }
 static_assert(dof2pos(0) == 2 && dof2pos(5) == 11 && dof2pos(6) == 0 && dof2pos(13) == 13 && pos2dof(7) == 3 && pos2dof(9) == 11 && pos2dof(15) == 15, "row layout");
 
+// (`row_newbcast` reads a valid lane for every lane of the row: there is no `old` value to keep — mov_dpp with bound_ctrl, as in
+// rows::qbcast, where update_dpp(0, ...) had the compiler materialise a zero in the destination first, one v_mov per broadcast)
 template <int P>
 __device__ __forceinline__ float bcast(float x) {  // value of lane P of this 16-lane row, on every lane of the row
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x150 + P, 0xF, 0xF, false));
+  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), 0x150 + P, 0xF, 0xF, true));
 }
 template <int P>
-__device__ __forceinline__ int bcast_i(int x) { return __builtin_amdgcn_update_dpp(0, x, 0x150 + P, 0xF, 0xF, false); }
+__device__ __forceinline__ int bcast_i(int x) { return __builtin_amdgcn_mov_dpp(x, 0x150 + P, 0xF, 0xF, true); }
 // Every lane must end up with the SAME BITS: alpha, the convergence tests and the active-set votes are computed redundantly by the
 // lanes of a row from these sums, and a row whose lanes disagree in the last bit can part ways at a branch (round 3 soak: one env
 // in 2.5e8 env-steps — a line search whose Newton step landed exactly on its bracket on one lane and one ulp inside it on the
@@ -71,6 +73,44 @@ __device__ __forceinline__ float rsum(float x) {  // all-reduce over the 16 lane
 // matvec: three accumulators round-robin (a dependent fmac_dpp chain would need two idle slots per link)
 #define MZ_MV_MUL(acc, k) "v_mul_f32_dpp %" #acc ", %[x], %[a" #k "] row_newbcast:" #k MZ_DPP_TAIL
 #define MZ_MV_FMA(acc, k) "v_fmac_f32_dpp %" #acc ", %[x], %[a" #k "] row_newbcast:" #k MZ_DPP_TAIL
+
+// Three independent row sums at once: rsum's butterfly, same partners and same order of additions (so every lane of the row still
+// ends with the same bits, and plain additions they are — nothing here can be contracted), the three chains round-robin.  Left to
+// the compiler, two or three butterflies side by side are packed: two unfused v_mov_b32_dpp feeding one v_pk_add_f32 (a packed
+// instruction takes no DPP operand) plus the wait state between them — 4.5 issue slots per butterfly step of three sums where
+// three v_add_f32_dpp do the work.  A chain link sits two slots behind the write it reads, so no wait state inside the block.
+// A single rsum stays with the compiler, which fuses its moves into v_add_f32_dpp and fills the wait states with other work.
+#define MZ_R3_OP(d, x, ctrl) "v_add_f32_dpp %[" #d "], %[" #x "], %[" #x "] " ctrl MZ_DPP_TAIL
+#define MZ_R3_FIRST(ctrl) MZ_R3_OP(sa, a, ctrl) MZ_R3_OP(sb, b, ctrl) MZ_R3_OP(sc, c, ctrl)
+#define MZ_R3_STEP(ctrl) MZ_R3_OP(sa, sa, ctrl) MZ_R3_OP(sb, sb, ctrl) MZ_R3_OP(sc, sc, ctrl)
+#define MZ_R3_TREE MZ_R3_FIRST("quad_perm:[1,0,3,2]") MZ_R3_STEP("quad_perm:[2,3,0,1]") MZ_R3_STEP("row_half_mirror") MZ_R3_STEP("row_mirror")
+__device__ __forceinline__ void rsum3(float a, float b, float c, float& sa, float& sb, float& sc) {
+  asm("s_nop 1\n\t" MZ_R3_TREE : [sa] "=&v"(sa), [sb] "=&v"(sb), [sc] "=&v"(sc) : [a] "v"(a), [b] "v"(b), [c] "v"(c));
+}
+// ... and next to each row sum the value plus that of its quad's lane 1 (the forward pass's composites: a hip lane adds its ankle's
+// term, `x + qbcast<1>(x)`) — three more fused adds on the same inputs in the same block; as a broadcast and an add of their own
+// the compiler packs pairs of them like the butterflies
+__device__ __forceinline__ void rsum3_q1(float a, float b, float c, float& sa, float& sb, float& sc, float& qa, float& qb, float& qc) {
+  asm("s_nop 1\n\t" MZ_R3_OP(qa, a, "quad_perm:[1,1,1,1]") MZ_R3_OP(qb, b, "quad_perm:[1,1,1,1]") MZ_R3_OP(qc, c, "quad_perm:[1,1,1,1]") MZ_R3_TREE
+      : [sa] "=&v"(sa), [sb] "=&v"(sb), [sc] "=&v"(sc), [qa] "=&v"(qa), [qb] "=&v"(qb), [qc] "=&v"(qc) : [a] "v"(a), [b] "v"(b), [c] "v"(c));
+}
+
+// Two sums at once.  The compiler packs such a pair — per butterfly step two unfused v_mov_b32_dpp, a v_pk_add_f32 and the two wait
+// states in front of the moves that read its result: five slots — where the two chains, one wait state between the steps, take three.
+#define MZ_R2_FIRST(ctrl) "v_add_f32_dpp %0, %2, %2 " ctrl MZ_DPP_TAIL "v_add_f32_dpp %1, %3, %3 " ctrl MZ_DPP_TAIL
+#define MZ_R2_STEP(ctrl) "s_nop 0\n\tv_add_f32_dpp %0, %0, %0 " ctrl MZ_DPP_TAIL "v_add_f32_dpp %1, %1, %1 " ctrl MZ_DPP_TAIL
+__device__ __forceinline__ void rsum2(float a, float b, float& sa, float& sb) {
+  asm("s_nop 1\n\t" MZ_R2_FIRST("quad_perm:[1,0,3,2]") MZ_R2_STEP("quad_perm:[2,3,0,1]") MZ_R2_STEP("row_half_mirror") MZ_R2_STEP("row_mirror")
+      : "=&v"(sa), "=&v"(sb) : "v"(a), "v"(b));
+}
+// The same over three products with a common factor (J x for the three rows of a contact, jdot3): with the multiplications inside,
+// every register a DPP instruction of the block reads was written by the block itself, three slots earlier — no wait state at all.
+// v_mul_f32 is the instruction the compiler had for `j * x` (nothing to contract with: the butterfly's additions are contract(off)).
+#define MZ_R3_MUL "v_mul_f32 %[sa], %[a], %[x]\n\tv_mul_f32 %[sb], %[b], %[x]\n\tv_mul_f32 %[sc], %[c], %[x]\n\t"
+__device__ __forceinline__ void rsum3_scaled(float a, float b, float c, float x, float& sa, float& sb, float& sc) {  // sums of a x, b x, c x
+  asm(MZ_R3_MUL MZ_R3_STEP("quad_perm:[1,0,3,2]") MZ_R3_STEP("quad_perm:[2,3,0,1]") MZ_R3_STEP("row_half_mirror") MZ_R3_STEP("row_mirror")
+      : [sa] "=&v"(sa), [sb] "=&v"(sb), [sc] "=&v"(sc) : [a] "v"(a), [b] "v"(b), [c] "v"(c), [x] "v"(x));
+}
 
 // y_r = sum_k A[r][k] x_k with row r of A in registers (Arow) and x distributed one entry per lane: 14 / 16 instructions
 __device__ __forceinline__ float matvec(const float (&A)[14], float x) {
@@ -214,16 +254,28 @@ __device__ __forceinline__ void mfma_rows(const v16f& acc, float (&out)[16]) {
     for (int v = 0; v < 4; v++) out[4 * g + v] = G[g][v];
 }
 
+// The pivot entry, clamped: max(h[lane P of my row], tiny) on every lane of the row in ONE instruction, where bcast + fmaxf came out
+// as four (a v_mov of the zero `old`, the v_mov_b32_dpp, the v_max x, x, x that canonicalises fmaxf's operand, the v_max itself).
+// Same value bit for bit: v_max_f32 returns the other operand for a NaN either way.  A DPP instruction takes no literal, so the
+// 1e-30 sits in a register — opaque, once per solve (pivot_floor), or the compiler would set it up again in front of each pivot.
+// `h` was written by the previous pivot's elim block: the block opens with the two wait states like its neighbours.
+__device__ __forceinline__ float pivot_floor() { float t = 1e-30f; asm("" : "+v"(t)); return t; }
+template <int P>
+__device__ __forceinline__ float pivot_clamped(float h, float tiny) {
+  float d;
+  asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "=&v"(d) : "v"(h), "v"(tiny), "n"(P));
+  return d;
+}
+
 // one Gauss-Jordan pivot P on the row-distributed system (Hrow | b): every other row gets rid of column P.
 // COLS... = the columns that can still be non-zero in the pivot row (compile-time list: the arrow structure).
 template <int P, int N, int... COLS>
-__device__ __forceinline__ void pivot(int r, float (&Hrow)[N], float& b, float& dinv, float (&mlt)[N]) {
+__device__ __forceinline__ void pivot(int r, float tiny, float (&Hrow)[N], float& b, float& dinv, float (&mlt)[N]) {
   // `r == P` is compared HERE, next to its two selects (one v_cmp into VCC): left to itself the compiler hoists the 14-16 lane masks of
   // a solve out of every loop, runs out of scalar registers, spills them to VGPR lanes and restores each with two v_readlane per
   // pivot (round 4: 387 -> 315 v_readlane in the kernel, 48 -> 42 accumulation registers, 0.2949 -> 0.2937 ms)
   asm("" : "+v"(r));
-  const float d = bcast<P>(Hrow[P]);
-  const float ri = 1.0f / fmaxf(d, 1e-30f);
+  const float ri = 1.0f / pivot_clamped<P>(Hrow[P], tiny);
   const float nli = (r == P) ? 0.f : -(Hrow[P] * ri);
   elim<P>(nli, b, Hrow[COLS]...);
   dinv = (r == P) ? ri : dinv;
@@ -234,22 +286,23 @@ __device__ __forceinline__ void pivot(int r, float (&Hrow)[N], float& b, float& 
 // are eliminated first, each touching its partner and the hub columns (root: positions 2 3 6 7 10 11) only
 __device__ __forceinline__ float solve_rows(int r, float (&Hrow)[14], float b, float (&mlt)[14], float& dinv) {
   dinv = 0.f;
+  const float tiny = pivot_floor();
   // the four legs do not couple: their hip pivots (then their ankle pivots) are independent chains — issued next to each
   // other so that the reciprocal / broadcast latencies of one hide behind the others
-  pivot<0, 14, 1, 2, 3, 6, 7, 10, 11>(r, Hrow, b, dinv, mlt);
-  pivot<4, 14, 5, 2, 3, 6, 7, 10, 11>(r, Hrow, b, dinv, mlt);
-  pivot<8, 14, 9, 2, 3, 6, 7, 10, 11>(r, Hrow, b, dinv, mlt);
-  pivot<12, 14, 13, 2, 3, 6, 7, 10, 11>(r, Hrow, b, dinv, mlt);
-  pivot<1, 14, 2, 3, 6, 7, 10, 11>(r, Hrow, b, dinv, mlt);
-  pivot<5, 14, 2, 3, 6, 7, 10, 11>(r, Hrow, b, dinv, mlt);
-  pivot<9, 14, 2, 3, 6, 7, 10, 11>(r, Hrow, b, dinv, mlt);
-  pivot<13, 14, 2, 3, 6, 7, 10, 11>(r, Hrow, b, dinv, mlt);
-  pivot<2, 14, 3, 6, 7, 10, 11>(r, Hrow, b, dinv, mlt);
-  pivot<3, 14, 6, 7, 10, 11>(r, Hrow, b, dinv, mlt);
-  pivot<6, 14, 7, 10, 11>(r, Hrow, b, dinv, mlt);
-  pivot<7, 14, 10, 11>(r, Hrow, b, dinv, mlt);
-  pivot<10, 14, 11>(r, Hrow, b, dinv, mlt);
-  pivot<11, 14>(r, Hrow, b, dinv, mlt);
+  pivot<0, 14, 1, 2, 3, 6, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
+  pivot<4, 14, 5, 2, 3, 6, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
+  pivot<8, 14, 9, 2, 3, 6, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
+  pivot<12, 14, 13, 2, 3, 6, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
+  pivot<1, 14, 2, 3, 6, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
+  pivot<5, 14, 2, 3, 6, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
+  pivot<9, 14, 2, 3, 6, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
+  pivot<13, 14, 2, 3, 6, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
+  pivot<2, 14, 3, 6, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
+  pivot<3, 14, 6, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
+  pivot<6, 14, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
+  pivot<7, 14, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
+  pivot<10, 14, 11>(r, tiny, Hrow, b, dinv, mlt);
+  pivot<11, 14>(r, tiny, Hrow, b, dinv, mlt);
   return b * dinv;
 }
 __device__ __forceinline__ float solve_rows(int r, float (&Hrow)[14], float b) {
@@ -260,22 +313,23 @@ __device__ __forceinline__ float solve_rows(int r, float (&Hrow)[14], float b) {
 // root and with one leg), eliminated between the legs and the root
 __device__ __forceinline__ float solve_rows(int r, float (&Hrow)[16], float b, float (&mlt)[16], float& dinv) {
   dinv = 0.f;
-  pivot<0, 16, 1, 2, 3, 6, 7, 10, 11, 14, 15>(r, Hrow, b, dinv, mlt);
-  pivot<4, 16, 5, 2, 3, 6, 7, 10, 11, 14, 15>(r, Hrow, b, dinv, mlt);
-  pivot<8, 16, 9, 2, 3, 6, 7, 10, 11, 14, 15>(r, Hrow, b, dinv, mlt);
-  pivot<12, 16, 13, 2, 3, 6, 7, 10, 11, 14, 15>(r, Hrow, b, dinv, mlt);
-  pivot<1, 16, 2, 3, 6, 7, 10, 11, 14, 15>(r, Hrow, b, dinv, mlt);
-  pivot<5, 16, 2, 3, 6, 7, 10, 11, 14, 15>(r, Hrow, b, dinv, mlt);
-  pivot<9, 16, 2, 3, 6, 7, 10, 11, 14, 15>(r, Hrow, b, dinv, mlt);
-  pivot<13, 16, 2, 3, 6, 7, 10, 11, 14, 15>(r, Hrow, b, dinv, mlt);
-  pivot<14, 16, 15, 2, 3, 6, 7, 10, 11>(r, Hrow, b, dinv, mlt);
-  pivot<15, 16, 2, 3, 6, 7, 10, 11>(r, Hrow, b, dinv, mlt);
-  pivot<2, 16, 3, 6, 7, 10, 11>(r, Hrow, b, dinv, mlt);
-  pivot<3, 16, 6, 7, 10, 11>(r, Hrow, b, dinv, mlt);
-  pivot<6, 16, 7, 10, 11>(r, Hrow, b, dinv, mlt);
-  pivot<7, 16, 10, 11>(r, Hrow, b, dinv, mlt);
-  pivot<10, 16, 11>(r, Hrow, b, dinv, mlt);
-  pivot<11, 16>(r, Hrow, b, dinv, mlt);
+  const float tiny = pivot_floor();
+  pivot<0, 16, 1, 2, 3, 6, 7, 10, 11, 14, 15>(r, tiny, Hrow, b, dinv, mlt);
+  pivot<4, 16, 5, 2, 3, 6, 7, 10, 11, 14, 15>(r, tiny, Hrow, b, dinv, mlt);
+  pivot<8, 16, 9, 2, 3, 6, 7, 10, 11, 14, 15>(r, tiny, Hrow, b, dinv, mlt);
+  pivot<12, 16, 13, 2, 3, 6, 7, 10, 11, 14, 15>(r, tiny, Hrow, b, dinv, mlt);
+  pivot<1, 16, 2, 3, 6, 7, 10, 11, 14, 15>(r, tiny, Hrow, b, dinv, mlt);
+  pivot<5, 16, 2, 3, 6, 7, 10, 11, 14, 15>(r, tiny, Hrow, b, dinv, mlt);
+  pivot<9, 16, 2, 3, 6, 7, 10, 11, 14, 15>(r, tiny, Hrow, b, dinv, mlt);
+  pivot<13, 16, 2, 3, 6, 7, 10, 11, 14, 15>(r, tiny, Hrow, b, dinv, mlt);
+  pivot<14, 16, 15, 2, 3, 6, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
+  pivot<15, 16, 2, 3, 6, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
+  pivot<2, 16, 3, 6, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
+  pivot<3, 16, 6, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
+  pivot<6, 16, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
+  pivot<7, 16, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
+  pivot<10, 16, 11>(r, tiny, Hrow, b, dinv, mlt);
+  pivot<11, 16>(r, tiny, Hrow, b, dinv, mlt);
   return b * dinv;
 }
 
@@ -769,7 +823,8 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
         {  // (no per-row guard `C < ncon`: a row without contact C holds zero columns and adds zeros; one exec-mask region less per slot)
           float jc[3];
           own_col(Cc, jc);
-          const float t0 = rsum(jc[0] * x), t1 = rsum(jc[1] * x), t2 = rsum(jc[2] * x);
+          float t0, t1, t2;
+          rsum3_scaled(jc[0], jc[1], jc[2], x, t0, t1, t2);
           if (r == (C & 15)) { o[C / 16][0] = t0; o[C / 16][1] = t1; o[C / 16][2] = t2; }
         }
       });
@@ -809,7 +864,7 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
       if (jw < 0.f) cw += 0.5f * lD * jw * jw;
       if (js < 0.f) cs += 0.5f * lD * js * js;
     }
-    cw = rsum(cw); cs = rsum(cs);
+    rsum2(cw, cs, cw, cs);
     if constexpr (NB == 1) {
       float bw[MB][3], bs[MB][3], cwb = 0.f, csb = 0.f;
       bdot(bcast<14>(warm), bcast<15>(warm), bw);
@@ -891,8 +946,12 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
           else bh11 += t0 * j0 + t1 * j1 + t2 * j2;
         }
       }
-      bg0 = bsum(bg0); bg1 = bsum(bg1); bga0 = bsum(bga0); bga1 = bsum(bga1);
-      bh00 = bsum(bh00); bh01 = bsum(bh01); bh11 = bsum(bh11);
+      if constexpr (WR) {  // (row sums: seven butterflies as 3 + 2 + 2)
+        rsum3(bg0, bg1, bh00, bg0, bg1, bh00); rsum2(bga0, bga1, bga0, bga1); rsum2(bh01, bh11, bh01, bh11);
+      } else {
+        bg0 = bsum(bg0); bg1 = bsum(bg1); bga0 = bsum(bga0); bga1 = bsum(bga1);
+        bh00 = bsum(bh00); bh01 = bsum(bh01); bh11 = bsum(bh11);
+      }
     }
     // ---- row r of H = M + sum_c Jc^T Wc Jc + limit curvature; gradient entry r
     float Hrow[NR];
@@ -948,7 +1007,8 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
     // less per evaluation (A / B: 0.2470 -> 0.2456 ms).
     float gnorm = 0.f, anorm = 0.f;
     if (it > 0) {
-      gnorm = sqrtf(rsum(g * g)); anorm = sqrtf(rsum(ga * ga));
+      rsum2(g * g, ga * ga, gnorm, anorm);
+      gnorm = sqrtf(gnorm); anorm = sqrtf(anorm);
       if (!done && (ant_u(cx, K).inv_scale * gnorm < ant_u(cx, K).tol || gnorm <= ant_u(cx, K).rtol * anorm)) done = true;
     }
     if (!cx.any(!done)) { cx.tick(s, 5); break; }
@@ -983,8 +1043,9 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
     const bool exact = !changed;
     if (changed) {  // exact line search on phi(alpha) = cost(qacc + alpha search): safeguarded Newton on the piecewise-linear phi'
       Ms = matvec(Mrow, search);
-      const float p1 = rsum(search * Mx), p2 = rsum(search * Ms);
-      sn = rsum(isdof ? search * search : 0.f); qn = rsum(isdof ? qacc * qacc : 0.f);
+      float p1, p2;
+      rsum2(search * Mx, search * Ms, p1, p2);
+      rsum2(isdof ? search * search : 0.f, isdof ? qacc * qacc : 0.f, sn, qn);
       float lo = 0.f, hi = -1.f, prev_d2 = -1.f;  // phi'(0) < 0 (descent direction); hi < 0: no upper bracket yet
       // Round 5: the first K.ls_fast_iters (5) iterations of an evaluation take the UNIT step when the active set changes (K.ls_fast = 0
       // evaluations of phi'), later ones search the line exactly as before.  What the line search buys is global convergence, not
@@ -1010,8 +1071,9 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
           }
         MZ_IF_OWNER(lsign != 0.f) { const float rr = ljar + alpha * ljv; if (rr < 0.f) { d1 += lD * rr * ljv; d2 += lD * ljv * ljv; } }
         if constexpr (NB != 1 || !WR) {
-          d1 = rsum(d1) + p1 + alpha * p2;
-          d2 = rsum(d2) + p2;
+          rsum2(d1, d2, d1, d2);
+          d1 = d1 + p1 + alpha * p2;
+          d2 = d2 + p2;
         }
         if constexpr (NB == 1) {
           float e1 = 0.f, e2 = 0.f;
@@ -1025,7 +1087,7 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
             rr = x0 + x2; vv = y0 + y2; if (rr < 0.f) { e1 += Dm * rr * vv; e2 += Dm * vv * vv; }
             rr = x0 - x2; vv = y0 - y2; if (rr < 0.f) { e1 += Dm * rr * vv; e2 += Dm * vv * vv; }
           }
-          if constexpr (WR) { d1 = rsum(d1 + e1) + p1 + alpha * p2; d2 = rsum(d2 + e2) + p2; }
+          if constexpr (WR) { rsum2(d1 + e1, d2 + e2, d1, d2); d1 = d1 + p1 + alpha * p2; d2 = d2 + p2; }
           else { d1 += cx.gsum(e1); d2 += cx.gsum(e2); }
         }
         if (d2 == prev_d2) break;  // same slope as at the previous iterate: same linear piece, alpha is its root
@@ -1098,7 +1160,7 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
             c0 += bj[m][0][0] * g0 + bj[m][1][0] * g1 + bj[m][2][0] * gg2;
             c1 += bj[m][0][1] * g0 + bj[m][1][1] * g1 + bj[m][2][1] * gg2;
           }
-          c0 = bsum(c0); c1 = bsum(c1);
+          if constexpr (WR) rsum2(c0, c1, c0, c1); else { c0 = bsum(c0); c1 = bsum(c1); }
           if (r == 14) g2 += c0;
           if (r == 15) g2 += c1;
         }
