@@ -722,12 +722,25 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
   //   Jf[m][a][k] the ROW a of this lane's own contact over all dofs k (zero outside hub + its leg) — J x as three DPP matvecs.
   // With them a Newton iteration touches no memory at all.
   auto each_contact = [&](auto&& f) {  // f(C) for the contact slots some env of the wave uses (wave-uniform guards)
-    if (cx.any(ncon > 0)) {
-      f(std::integral_constant<int, 0>{}); f(std::integral_constant<int, 1>{}); f(std::integral_constant<int, 2>{}); f(std::integral_constant<int, 3>{});
+    // Slots 0 .. 3 one by one, nested: a wave whose largest count is 2 takes one taken branch per call.  In the settled rollout of
+    // the bench the largest count among a wave's four envs is 2 in 59 % of the evaluations, 3 in 32 % and 4 in 2 %, so the block of
+    // four ran 1.7 slots per call on zero columns.  Measured (profiles/slot_guards/ab.md, AntUMaze-v0 4096 envs): SQ_INSTS_VALU per
+    // launch 7.13e7 -> 6.32e7, the mean wave's cycles -6.8 %, the launch — its slowest wave, more often one that needs three
+    // slots — 0.2307 -> 0.2260 ms; 8192 envs (two waves per SIMD) -4.4 %.  Two things measured and left out (same file):
+    //   * the predicates once per solve, in scalar registers: 0.7 % faster still, but with ANY hoisted form the compiler packs and
+    //     contracts four blocks of the forward pass differently — every env's result moves in the last bits.  They stay at the call;
+    //   * the same guards for the one-block ant: its waves hold two envs that mostly use the four slots, the three extra votes per
+    //     call cost AntPush-v0 0.3 .. 0.5 %.  NB = 1 keeps one guard for the block of four.
+    // A skipped slot leaves its jown[C] unwritten, as the slots from 4 up always have: own_col reads it inside each_contact only,
+    // behind the same guards (ncon does not change within a solve).
+    auto more = [&](int k) { return NB == 1 || cx.any(ncon > k); };
+    if (cx.any(ncon > 0)) { f(std::integral_constant<int, 0>{});
+    if (more(1)) { f(std::integral_constant<int, 1>{});
+    if (more(2)) { f(std::integral_constant<int, 2>{});
+    if (more(3)) { f(std::integral_constant<int, 3>{});
       if (cx.any(ncon > 4)) {
         // (slots 4 .. 7 in pairs: the waves a launch waits for are those whose ants lean on a wall — five or six contacts — and two
-        // skipped slots are 160 instructions per Newton iteration; measured 0.2971 -> 0.2949 ms.  The same guard between slots 1 and 2
-        // gains nothing: the waves with at most two contacts per env are not the ones the launch waits for)
+        // skipped slots are 160 instructions per Newton iteration; measured 0.2971 -> 0.2949 ms)
         f(std::integral_constant<int, 4>{}); f(std::integral_constant<int, 5>{});
         if (cx.any(ncon > 6)) { f(std::integral_constant<int, 6>{}); f(std::integral_constant<int, 7>{}); }
         if (cx.any(ncon > 8)) {
@@ -748,7 +761,7 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
           }
         }
       }
-    }
+    }}}}
   };
   // WR: the columns of the SECOND slot's contacts (C >= 16: an ant on its back next to the block, rare, behind the wave-uniform
   // `any2`) are not kept — 48 registers live through the whole solve for a path hardly any wave takes — but recomputed from the
