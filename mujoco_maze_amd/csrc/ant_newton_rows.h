@@ -66,10 +66,22 @@ __device__ __forceinline__ float rsum(float x) {  // all-reduce over the 16 lane
 // an FMA on gfx950 — V_FMA_F32 is still three-address when the combiner runs — and emits  v_mov 0 ; s_nop 1 ; v_mov_dpp ; v_fma,
 // five issue slots, for what the hardware does in one:  v_fmac_f32_dpp acc, x, m row_newbcast:P  =  acc += x[lane P of my row] * m).
 // Hazard rule kept by construction and checked on the built code by tools/check_dpp_hazards.py (tests/test_capi_and_emu.py):
-// a VGPR read by a DPP instruction — any operand — must not have been written by the two preceding VALU issue slots.  Every
-// block below therefore opens with `s_nop 1` (its inputs may be fresh) and never reads a register it wrote less than three
-// instructions earlier.
+// a VGPR read by a DPP instruction — any operand — must not have been written by the two preceding VALU issue slots.  No block
+// below reads a register it wrote less than three instructions earlier, and how many wait states a block OPENS with is a property
+// of the call site (template parameter W = 0, 1 or 2): a string cannot know what precedes it, the caller often does.  W = 2, the
+// default, is for inputs the compiler may have written in the slot before; less only where every register the block's DPP
+// instructions read was last written by another block of this file, that many slots earlier — the compiler can put instructions
+// between two blocks, never take one away — and the check on the built code still holds the call site to it (the compiler could
+// restore an operand from an accumulation register in front of the block: that would be a finding of the check, not silent).
 #define MZ_DPP_TAIL " row_mask:0xf bank_mask:0xf\n\t"
+// asm(body ...) behind W opening wait states; the operand lists follow the body as they would in the asm statement
+#define MZ_ASM_W(W, body, ...)                                       \
+  do {                                                               \
+    static_assert(W >= 0 && W <= 2, "opening wait states: 0, 1, 2"); \
+    if constexpr (W == 0) asm(body __VA_ARGS__);                     \
+    else if constexpr (W == 1) asm("s_nop 0\n\t" body __VA_ARGS__);  \
+    else asm("s_nop 1\n\t" body __VA_ARGS__);                        \
+  } while (0)
 // matvec: three accumulators round-robin (a dependent fmac_dpp chain would need two idle slots per link)
 #define MZ_MV_MUL(acc, k) "v_mul_f32_dpp %" #acc ", %[x], %[a" #k "] row_newbcast:" #k MZ_DPP_TAIL
 #define MZ_MV_FMA(acc, k) "v_fmac_f32_dpp %" #acc ", %[x], %[a" #k "] row_newbcast:" #k MZ_DPP_TAIL
@@ -84,24 +96,43 @@ __device__ __forceinline__ float rsum(float x) {  // all-reduce over the 16 lane
 #define MZ_R3_FIRST(ctrl) MZ_R3_OP(sa, a, ctrl) MZ_R3_OP(sb, b, ctrl) MZ_R3_OP(sc, c, ctrl)
 #define MZ_R3_STEP(ctrl) MZ_R3_OP(sa, sa, ctrl) MZ_R3_OP(sb, sb, ctrl) MZ_R3_OP(sc, sc, ctrl)
 #define MZ_R3_TREE MZ_R3_FIRST("quad_perm:[1,0,3,2]") MZ_R3_STEP("quad_perm:[2,3,0,1]") MZ_R3_STEP("row_half_mirror") MZ_R3_STEP("row_mirror")
+template <int W = 2>
 __device__ __forceinline__ void rsum3(float a, float b, float c, float& sa, float& sb, float& sc) {
-  asm("s_nop 1\n\t" MZ_R3_TREE : [sa] "=&v"(sa), [sb] "=&v"(sb), [sc] "=&v"(sc) : [a] "v"(a), [b] "v"(b), [c] "v"(c));
+  MZ_ASM_W(W, MZ_R3_TREE, : [sa] "=&v"(sa), [sb] "=&v"(sb), [sc] "=&v"(sc) : [a] "v"(a), [b] "v"(b), [c] "v"(c));
 }
 // ... and next to each row sum the value plus that of its quad's lane 1 (the forward pass's composites: a hip lane adds its ankle's
 // term, `x + qbcast<1>(x)`) — three more fused adds on the same inputs in the same block; as a broadcast and an add of their own
 // the compiler packs pairs of them like the butterflies
+template <int W = 2>
 __device__ __forceinline__ void rsum3_q1(float a, float b, float c, float& sa, float& sb, float& sc, float& qa, float& qb, float& qc) {
-  asm("s_nop 1\n\t" MZ_R3_OP(qa, a, "quad_perm:[1,1,1,1]") MZ_R3_OP(qb, b, "quad_perm:[1,1,1,1]") MZ_R3_OP(qc, c, "quad_perm:[1,1,1,1]") MZ_R3_TREE
-      : [sa] "=&v"(sa), [sb] "=&v"(sb), [sc] "=&v"(sc), [qa] "=&v"(qa), [qb] "=&v"(qb), [qc] "=&v"(qc) : [a] "v"(a), [b] "v"(b), [c] "v"(c));
+  MZ_ASM_W(W, MZ_R3_OP(qa, a, "quad_perm:[1,1,1,1]") MZ_R3_OP(qb, b, "quad_perm:[1,1,1,1]") MZ_R3_OP(qc, c, "quad_perm:[1,1,1,1]") MZ_R3_TREE,
+           : [sa] "=&v"(sa), [sb] "=&v"(sb), [sc] "=&v"(sc), [qa] "=&v"(qa), [qb] "=&v"(qb), [qc] "=&v"(qc) : [a] "v"(a), [b] "v"(b), [c] "v"(c));
 }
 
 // Two sums at once.  The compiler packs such a pair — per butterfly step two unfused v_mov_b32_dpp, a v_pk_add_f32 and the two wait
 // states in front of the moves that read its result: five slots — where the two chains, one wait state between the steps, take three.
 #define MZ_R2_FIRST(ctrl) "v_add_f32_dpp %0, %2, %2 " ctrl MZ_DPP_TAIL "v_add_f32_dpp %1, %3, %3 " ctrl MZ_DPP_TAIL
 #define MZ_R2_STEP(ctrl) "s_nop 0\n\tv_add_f32_dpp %0, %0, %0 " ctrl MZ_DPP_TAIL "v_add_f32_dpp %1, %1, %1 " ctrl MZ_DPP_TAIL
+template <int W = 2>
 __device__ __forceinline__ void rsum2(float a, float b, float& sa, float& sb) {
-  asm("s_nop 1\n\t" MZ_R2_FIRST("quad_perm:[1,0,3,2]") MZ_R2_STEP("quad_perm:[2,3,0,1]") MZ_R2_STEP("row_half_mirror") MZ_R2_STEP("row_mirror")
+  MZ_ASM_W(W, MZ_R2_FIRST("quad_perm:[1,0,3,2]") MZ_R2_STEP("quad_perm:[2,3,0,1]") MZ_R2_STEP("row_half_mirror") MZ_R2_STEP("row_mirror"),
+           : "=&v"(sa), "=&v"(sb) : "v"(a), "v"(b));
+}
+// ... of two squares (the convergence test): with the multiplications inside — v_mul_f32, what the compiler had for `g * g` — the
+// block reads nothing fresh and opens with no wait state; one is left between the products and the first step
+__device__ __forceinline__ void rsum2_sq(float a, float b, float& sa, float& sb) {
+  asm("v_mul_f32 %0, %2, %2\n\tv_mul_f32 %1, %3, %3\n\t" MZ_R2_STEP("quad_perm:[1,0,3,2]") MZ_R2_STEP("quad_perm:[2,3,0,1]") MZ_R2_STEP("row_half_mirror")
+      MZ_R2_STEP("row_mirror")
       : "=&v"(sa), "=&v"(sb) : "v"(a), "v"(b));
+}
+// Four sums at once: the four chains round-robin, a link three slots behind the write it reads — no wait state inside the block
+// where two blocks of two chains each need six.  Every sum keeps rsum's partners and order of additions.
+#define MZ_R4_FIRST(ctrl) MZ_R3_FIRST(ctrl) MZ_R3_OP(sd, d, ctrl)
+#define MZ_R4_STEP(ctrl) MZ_R3_STEP(ctrl) MZ_R3_OP(sd, sd, ctrl)
+template <int W = 2>
+__device__ __forceinline__ void rsum4(float a, float b, float c, float d, float& sa, float& sb, float& sc, float& sd) {
+  MZ_ASM_W(W, MZ_R4_FIRST("quad_perm:[1,0,3,2]") MZ_R4_STEP("quad_perm:[2,3,0,1]") MZ_R4_STEP("row_half_mirror") MZ_R4_STEP("row_mirror"),
+           : [sa] "=&v"(sa), [sb] "=&v"(sb), [sc] "=&v"(sc), [sd] "=&v"(sd) : [a] "v"(a), [b] "v"(b), [c] "v"(c), [d] "v"(d));
 }
 // The same over three products with a common factor (J x for the three rows of a contact, jdot3): with the multiplications inside,
 // every register a DPP instruction of the block reads was written by the block itself, three slots earlier — no wait state at all.
@@ -113,98 +144,74 @@ __device__ __forceinline__ void rsum3_scaled(float a, float b, float c, float x,
 }
 
 // y_r = sum_k A[r][k] x_k with row r of A in registers (Arow) and x distributed one entry per lane: 14 / 16 instructions
+template <int W = 2>
 __device__ __forceinline__ float matvec(const float (&A)[14], float x) {
   float s0, s1, s2;
-  asm("s_nop 1\n\t" MZ_MV_MUL(0, 0) MZ_MV_MUL(1, 1) MZ_MV_MUL(2, 2) MZ_MV_FMA(0, 3) MZ_MV_FMA(1, 4) MZ_MV_FMA(2, 5) MZ_MV_FMA(0, 6) MZ_MV_FMA(1, 7)
-      MZ_MV_FMA(2, 8) MZ_MV_FMA(0, 9) MZ_MV_FMA(1, 10) MZ_MV_FMA(2, 11) MZ_MV_FMA(0, 12) MZ_MV_FMA(1, 13)
+  MZ_ASM_W(W, MZ_MV_MUL(0, 0) MZ_MV_MUL(1, 1) MZ_MV_MUL(2, 2) MZ_MV_FMA(0, 3) MZ_MV_FMA(1, 4) MZ_MV_FMA(2, 5) MZ_MV_FMA(0, 6) MZ_MV_FMA(1, 7)
+      MZ_MV_FMA(2, 8) MZ_MV_FMA(0, 9) MZ_MV_FMA(1, 10) MZ_MV_FMA(2, 11) MZ_MV_FMA(0, 12) MZ_MV_FMA(1, 13),
       : "=&v"(s0), "=&v"(s1), "=&v"(s2)
       : [x] "v"(x), [a0] "v"(A[0]), [a1] "v"(A[1]), [a2] "v"(A[2]), [a3] "v"(A[3]), [a4] "v"(A[4]), [a5] "v"(A[5]), [a6] "v"(A[6]), [a7] "v"(A[7]),
         [a8] "v"(A[8]), [a9] "v"(A[9]), [a10] "v"(A[10]), [a11] "v"(A[11]), [a12] "v"(A[12]), [a13] "v"(A[13]));
   return (s0 + s1) + s2;
 }
+template <int W = 2>
 __device__ __forceinline__ float matvec(const float (&A)[16], float x) {
   float s0, s1, s2;
-  asm("s_nop 1\n\t" MZ_MV_MUL(0, 0) MZ_MV_MUL(1, 1) MZ_MV_MUL(2, 2) MZ_MV_FMA(0, 3) MZ_MV_FMA(1, 4) MZ_MV_FMA(2, 5) MZ_MV_FMA(0, 6) MZ_MV_FMA(1, 7)
-      MZ_MV_FMA(2, 8) MZ_MV_FMA(0, 9) MZ_MV_FMA(1, 10) MZ_MV_FMA(2, 11) MZ_MV_FMA(0, 12) MZ_MV_FMA(1, 13) MZ_MV_FMA(2, 14) MZ_MV_FMA(0, 15)
+  MZ_ASM_W(W, MZ_MV_MUL(0, 0) MZ_MV_MUL(1, 1) MZ_MV_MUL(2, 2) MZ_MV_FMA(0, 3) MZ_MV_FMA(1, 4) MZ_MV_FMA(2, 5) MZ_MV_FMA(0, 6) MZ_MV_FMA(1, 7)
+      MZ_MV_FMA(2, 8) MZ_MV_FMA(0, 9) MZ_MV_FMA(1, 10) MZ_MV_FMA(2, 11) MZ_MV_FMA(0, 12) MZ_MV_FMA(1, 13) MZ_MV_FMA(2, 14) MZ_MV_FMA(0, 15),
       : "=&v"(s0), "=&v"(s1), "=&v"(s2)
       : [x] "v"(x), [a0] "v"(A[0]), [a1] "v"(A[1]), [a2] "v"(A[2]), [a3] "v"(A[3]), [a4] "v"(A[4]), [a5] "v"(A[5]), [a6] "v"(A[6]), [a7] "v"(A[7]),
         [a8] "v"(A[8]), [a9] "v"(A[9]), [a10] "v"(A[10]), [a11] "v"(A[11]), [a12] "v"(A[12]), [a13] "v"(A[13]), [a14] "v"(A[14]), [a15] "v"(A[15]));
   return (s0 + s1) + s2;
 }
 
-// elimination step of one pivot: h_k += nli * h_k[lane P] for the right-hand side and every column that can still be non-zero
-// in the pivot row — one instruction per column, the columns independent of each other (overloads by column count)
-#define MZ_EL(i) "v_fmac_f32_dpp %" #i ", %" #i ", %[li] row_newbcast:%[p]" MZ_DPP_TAIL
-#define MZ_EL_IN [li] "v"(nli), [p] "n"(P)
-template <int P> __device__ __forceinline__ void elim(float nli, float& b) { asm("s_nop 1\n\t" MZ_EL(0) : "+v"(b) : MZ_EL_IN); }
-template <int P> __device__ __forceinline__ void elim(float nli, float& b, float& h0) { asm("s_nop 1\n\t" MZ_EL(0) MZ_EL(1) : "+v"(b), "+v"(h0) : MZ_EL_IN); }
-template <int P> __device__ __forceinline__ void elim(float nli, float& b, float& h0, float& h1) {
-  asm("s_nop 1\n\t" MZ_EL(0) MZ_EL(1) MZ_EL(2) : "+v"(b), "+v"(h0), "+v"(h1) : MZ_EL_IN);
-}
-template <int P> __device__ __forceinline__ void elim(float nli, float& b, float& h0, float& h1, float& h2) {
-  asm("s_nop 1\n\t" MZ_EL(0) MZ_EL(1) MZ_EL(2) MZ_EL(3) : "+v"(b), "+v"(h0), "+v"(h1), "+v"(h2) : MZ_EL_IN);
-}
-template <int P> __device__ __forceinline__ void elim(float nli, float& b, float& h0, float& h1, float& h2, float& h3) {
-  asm("s_nop 1\n\t" MZ_EL(0) MZ_EL(1) MZ_EL(2) MZ_EL(3) MZ_EL(4) : "+v"(b), "+v"(h0), "+v"(h1), "+v"(h2), "+v"(h3) : MZ_EL_IN);
-}
-template <int P> __device__ __forceinline__ void elim(float nli, float& b, float& h0, float& h1, float& h2, float& h3, float& h4) {
-  asm("s_nop 1\n\t" MZ_EL(0) MZ_EL(1) MZ_EL(2) MZ_EL(3) MZ_EL(4) MZ_EL(5) : "+v"(b), "+v"(h0), "+v"(h1), "+v"(h2), "+v"(h3), "+v"(h4) : MZ_EL_IN);
-}
-template <int P> __device__ __forceinline__ void elim(float nli, float& b, float& h0, float& h1, float& h2, float& h3, float& h4, float& h5) {
-  asm("s_nop 1\n\t" MZ_EL(0) MZ_EL(1) MZ_EL(2) MZ_EL(3) MZ_EL(4) MZ_EL(5) MZ_EL(6)
-      : "+v"(b), "+v"(h0), "+v"(h1), "+v"(h2), "+v"(h3), "+v"(h4), "+v"(h5) : MZ_EL_IN);
-}
-template <int P> __device__ __forceinline__ void elim(float nli, float& b, float& h0, float& h1, float& h2, float& h3, float& h4, float& h5, float& h6) {
-  asm("s_nop 1\n\t" MZ_EL(0) MZ_EL(1) MZ_EL(2) MZ_EL(3) MZ_EL(4) MZ_EL(5) MZ_EL(6) MZ_EL(7)
-      : "+v"(b), "+v"(h0), "+v"(h1), "+v"(h2), "+v"(h3), "+v"(h4), "+v"(h5), "+v"(h6) : MZ_EL_IN);
-}
-template <int P> __device__ __forceinline__ void elim(float nli, float& b, float& h0, float& h1, float& h2, float& h3, float& h4, float& h5, float& h6, float& h7) {
-  asm("s_nop 1\n\t" MZ_EL(0) MZ_EL(1) MZ_EL(2) MZ_EL(3) MZ_EL(4) MZ_EL(5) MZ_EL(6) MZ_EL(7) MZ_EL(8)
-      : "+v"(b), "+v"(h0), "+v"(h1), "+v"(h2), "+v"(h3), "+v"(h4), "+v"(h5), "+v"(h6), "+v"(h7) : MZ_EL_IN);
-}
-template <int P> __device__ __forceinline__ void elim(float nli, float& b, float& h0, float& h1, float& h2, float& h3, float& h4, float& h5, float& h6, float& h7, float& h8) {
-  asm("s_nop 1\n\t" MZ_EL(0) MZ_EL(1) MZ_EL(2) MZ_EL(3) MZ_EL(4) MZ_EL(5) MZ_EL(6) MZ_EL(7) MZ_EL(8) MZ_EL(9)
-      : "+v"(b), "+v"(h0), "+v"(h1), "+v"(h2), "+v"(h3), "+v"(h4), "+v"(h5), "+v"(h6), "+v"(h7), "+v"(h8) : MZ_EL_IN);
-}
 
 // contribution of contact C (owner: lane P of the row) to row r of the Hessian and to the gradient.  cg[8] = the contact's gradient
 // block (3) and curvature block (5), read on the owner lane; (j0, j1, j2) = this lane's own column of the contact's Jacobian.
 //   fold_t:  t = g . j,  (t0, t1, t2) = (W j)         ten instructions, four independent chains
-//   fold_h:  Hrow[k] += t0 j0[lane k] + t1 j1[lane k] + t2 j2[lane k]   three instructions per column, the columns independent
+//   fold_th: fold_t, then Hrow[k] += t0 j0[lane k] + t1 j1[lane k] + t2 j2[lane k]   three instructions per column, the columns independent
 #define MZ_FA_MUL(o, c, j) "v_mul_f32_dpp %" #o ", %[" #c "], %[" #j "] row_newbcast:%[p]" MZ_DPP_TAIL
 #define MZ_FA_FMA(o, c, j) "v_fmac_f32_dpp %" #o ", %[" #c "], %[" #j "] row_newbcast:%[p]" MZ_DPP_TAIL
-template <int P>
+#define MZ_FT(t, t0, t1, t2)                                                                                                        \
+  MZ_FA_MUL(t0, c3, j0) MZ_FA_MUL(t, c0, j0) MZ_FA_MUL(t1, c4, j0) MZ_FA_FMA(t0, c4, j1) MZ_FA_FMA(t, c1, j1) MZ_FA_MUL(t2, c5, j0) \
+  MZ_FA_FMA(t0, c5, j2) MZ_FA_FMA(t, c2, j2) MZ_FA_FMA(t1, c6, j1) MZ_FA_FMA(t2, c7, j2)
+#define MZ_FT_IN                                                                                                                             \
+  [c0] "v"(cg[0]), [c1] "v"(cg[1]), [c2] "v"(cg[2]), [c3] "v"(cg[3]), [c4] "v"(cg[4]), [c5] "v"(cg[5]), [c6] "v"(cg[6]), [c7] "v"(cg[7]), \
+      [j0] "v"(j0), [j1] "v"(j1), [j2] "v"(j2), [p] "n"(P)
+// (t0, which the Hessian's columns read first, is complete three instructions before the block ends — each chain in its own
+// order, a link three slots behind the one before it — so fold_th goes on without a wait state)
+template <int P, int W = 2>
 __device__ __forceinline__ void fold_t(const float (&cg)[8], float j0, float j1, float j2, float& t, float& t0, float& t1, float& t2) {
-  asm("s_nop 1\n\t" MZ_FA_MUL(0, c0, j0) MZ_FA_MUL(1, c3, j0) MZ_FA_MUL(2, c4, j0) MZ_FA_MUL(3, c5, j0) MZ_FA_FMA(0, c1, j1) MZ_FA_FMA(1, c4, j1)
-      MZ_FA_FMA(2, c6, j1) MZ_FA_FMA(3, c7, j2) MZ_FA_FMA(0, c2, j2) MZ_FA_FMA(1, c5, j2)
-      : "=&v"(t), "=&v"(t0), "=&v"(t1), "=&v"(t2)
-      : [c0] "v"(cg[0]), [c1] "v"(cg[1]), [c2] "v"(cg[2]), [c3] "v"(cg[3]), [c4] "v"(cg[4]), [c5] "v"(cg[5]), [c6] "v"(cg[6]), [c7] "v"(cg[7]),
-        [j0] "v"(j0), [j1] "v"(j1), [j2] "v"(j2), [p] "n"(P));
+  MZ_ASM_W(W, MZ_FT(0, 1, 2, 3), : "=&v"(t), "=&v"(t0), "=&v"(t1), "=&v"(t2) : MZ_FT_IN);
 }
 // gradient part alone (the refinement step of ant_solve_rows_core): t = g . j with g = three registers of the owner lane P
-template <int P>
+template <int P, int W = 2>
 __device__ __forceinline__ float fold_g(float g0, float g1, float g2, float j0, float j1, float j2) {
   float a0, a1, a2;  // three independent products (a dependent fmac_dpp chain would read its accumulator inside the DPP hazard window)
-  asm("s_nop 1\n\t" MZ_FA_MUL(0, c0, j0) MZ_FA_MUL(1, c1, j1) MZ_FA_MUL(2, c2, j2)
+  MZ_ASM_W(W, MZ_FA_MUL(0, c0, j0) MZ_FA_MUL(1, c1, j1) MZ_FA_MUL(2, c2, j2),
       : "=&v"(a0), "=&v"(a1), "=&v"(a2) : [c0] "v"(g0), [c1] "v"(g1), [c2] "v"(g2), [j0] "v"(j0), [j1] "v"(j1), [j2] "v"(j2), [p] "n"(P));
   return (a0 + a1) + a2;
 }
-#define MZ_FH(k, j, t) "v_fmac_f32_dpp %" #k ", %[" #j "], %[" #t "] row_newbcast:" #k MZ_DPP_TAIL
-#define MZ_FH14(j, t) MZ_FH(0, j, t) MZ_FH(1, j, t) MZ_FH(2, j, t) MZ_FH(3, j, t) MZ_FH(4, j, t) MZ_FH(5, j, t) MZ_FH(6, j, t) MZ_FH(7, j, t) \
-                      MZ_FH(8, j, t) MZ_FH(9, j, t) MZ_FH(10, j, t) MZ_FH(11, j, t) MZ_FH(12, j, t) MZ_FH(13, j, t)
-#define MZ_FH16(j, t) MZ_FH14(j, t) MZ_FH(14, j, t) MZ_FH(15, j, t)
-#define MZ_FH_IN [j0] "v"(j0), [j1] "v"(j1), [j2] "v"(j2), [t0] "v"(t0), [t1] "v"(t1), [t2] "v"(t2)
-__device__ __forceinline__ void fold_h(float (&H)[14], float j0, float j1, float j2, float t0, float t1, float t2) {
-  asm("s_nop 1\n\t" MZ_FH14(j0, t0) MZ_FH14(j1, t1) MZ_FH14(j2, t2)
-      : "+v"(H[0]), "+v"(H[1]), "+v"(H[2]), "+v"(H[3]), "+v"(H[4]), "+v"(H[5]), "+v"(H[6]), "+v"(H[7]), "+v"(H[8]), "+v"(H[9]), "+v"(H[10]),
-        "+v"(H[11]), "+v"(H[12]), "+v"(H[13])
-      : MZ_FH_IN);
+// fold_t and the Hessian fold of one contact slot as ONE block: (W j) is complete three instructions before the first column reads it, so
+// nothing waits between the two, and — one string — the compiler cannot put a copy of a column's accumulator in between
+#define MZ_FTH(k, j, t) "v_fmac_f32_dpp %[h" #k "], %[" #j "], %[" #t "] row_newbcast:" #k MZ_DPP_TAIL
+#define MZ_FTH14(j, t) MZ_FTH(0, j, t) MZ_FTH(1, j, t) MZ_FTH(2, j, t) MZ_FTH(3, j, t) MZ_FTH(4, j, t) MZ_FTH(5, j, t) MZ_FTH(6, j, t) MZ_FTH(7, j, t) \
+                       MZ_FTH(8, j, t) MZ_FTH(9, j, t) MZ_FTH(10, j, t) MZ_FTH(11, j, t) MZ_FTH(12, j, t) MZ_FTH(13, j, t)
+#define MZ_FTH16(j, t) MZ_FTH14(j, t) MZ_FTH(14, j, t) MZ_FTH(15, j, t)
+#define MZ_FTH_OUT14                                                                                                                              \
+  [t] "=&v"(t), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [h0] "+v"(H[0]), [h1] "+v"(H[1]), [h2] "+v"(H[2]), [h3] "+v"(H[3]), [h4] "+v"(H[4]), \
+      [h5] "+v"(H[5]), [h6] "+v"(H[6]), [h7] "+v"(H[7]), [h8] "+v"(H[8]), [h9] "+v"(H[9]), [h10] "+v"(H[10]), [h11] "+v"(H[11]), [h12] "+v"(H[12]), [h13] "+v"(H[13])
+template <int P, int W = 2>
+__device__ __forceinline__ float fold_th(float (&H)[14], const float (&cg)[8], float j0, float j1, float j2) {
+  float t, t0, t1, t2;
+  MZ_ASM_W(W, MZ_FT([t], [t0], [t1], [t2]) MZ_FTH14(j0, t0) MZ_FTH14(j1, t1) MZ_FTH14(j2, t2), : MZ_FTH_OUT14 : MZ_FT_IN);
+  return t;
 }
-__device__ __forceinline__ void fold_h(float (&H)[16], float j0, float j1, float j2, float t0, float t1, float t2) {
-  asm("s_nop 1\n\t" MZ_FH16(j0, t0) MZ_FH16(j1, t1) MZ_FH16(j2, t2)
-      : "+v"(H[0]), "+v"(H[1]), "+v"(H[2]), "+v"(H[3]), "+v"(H[4]), "+v"(H[5]), "+v"(H[6]), "+v"(H[7]), "+v"(H[8]), "+v"(H[9]), "+v"(H[10]),
-        "+v"(H[11]), "+v"(H[12]), "+v"(H[13]), "+v"(H[14]), "+v"(H[15])
-      : MZ_FH_IN);
+template <int P, int W = 2>
+__device__ __forceinline__ float fold_th(float (&H)[16], const float (&cg)[8], float j0, float j1, float j2) {
+  float t, t0, t1, t2;
+  MZ_ASM_W(W, MZ_FT([t], [t0], [t1], [t2]) MZ_FTH16(j0, t0) MZ_FTH16(j1, t1) MZ_FTH16(j2, t2), : MZ_FTH_OUT14, [h14] "+v"(H[14]), [h15] "+v"(H[15]) : MZ_FT_IN);
+  return t;
 }
 
 // ---- the Hessian update on the matrix cores (round 5).  `v_mfma_f32_16x16x1_4b_f32` is FOUR independent 16 x 16 rank-1 updates,
@@ -254,104 +261,134 @@ __device__ __forceinline__ void mfma_rows(const v16f& acc, float (&out)[16]) {
     for (int v = 0; v < 4; v++) out[4 * g + v] = G[g][v];
 }
 
-// The pivot entry, clamped: max(h[lane P of my row], tiny) on every lane of the row in ONE instruction, where bcast + fmaxf came out
-// as four (a v_mov of the zero `old`, the v_mov_b32_dpp, the v_max x, x, x that canonicalises fmaxf's operand, the v_max itself).
-// Same value bit for bit: v_max_f32 returns the other operand for a NaN either way.  A DPP instruction takes no literal, so the
-// 1e-30 sits in a register — opaque, once per solve (pivot_floor), or the compiler would set it up again in front of each pivot.
-// `h` was written by the previous pivot's elim block: the block opens with the two wait states like its neighbours.
-__device__ __forceinline__ float pivot_floor() { float t = 1e-30f; asm("" : "+v"(t)); return t; }
-template <int P>
-__device__ __forceinline__ float pivot_clamped(float h, float tiny) {
-  float d;
-  asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "=&v"(d) : "v"(h), "v"(tiny), "n"(P));
-  return d;
-}
-
-// one Gauss-Jordan pivot P on the row-distributed system (Hrow | b): every other row gets rid of column P.
-// COLS... = the columns that can still be non-zero in the pivot row (compile-time list: the arrow structure).
-template <int P, int N, int... COLS>
-__device__ __forceinline__ void pivot(int r, float tiny, float (&Hrow)[N], float& b, float& dinv, float (&mlt)[N]) {
-  // `r == P` is compared HERE, next to its two selects (one v_cmp into VCC): left to itself the compiler hoists the 14-16 lane masks of
-  // a solve out of every loop, runs out of scalar registers, spills them to VGPR lanes and restores each with two v_readlane per
-  // pivot (round 4: 387 -> 315 v_readlane in the kernel, 48 -> 42 accumulation registers, 0.2949 -> 0.2937 ms)
-  asm("" : "+v"(r));
-  const float ri = 1.0f / pivot_clamped<P>(Hrow[P], tiny);
-  const float nli = (r == P) ? 0.f : -(Hrow[P] * ri);
-  elim<P>(nli, b, Hrow[COLS]...);
-  dinv = (r == P) ? ri : dinv;
-  mlt[P] = nli;  // this row's multiplier of pivot P: kept for a second right-hand side (resolve_rows); dead code where nobody asks
-}
-
-// H x = b, arrow-structured SPD H, row-distributed in POSITION order (pos2dof above): the hinges (positions 0 1 | 4 5 | 8 9 | 12 13)
-// are eliminated first, each touching its partner and the hub columns (root: positions 2 3 6 7 10 11) only
-__device__ __forceinline__ float solve_rows(int r, float (&Hrow)[14], float b, float (&mlt)[14], float& dinv) {
+// ---- H x = b, arrow-structured SPD H, row-distributed in POSITION order (pos2dof above), by Gauss-Jordan elimination: the hinges
+// (positions 0 1 | 4 5 | 8 9 | 12 13) first, each touching its partner and the hub columns (root: positions 2 3 6 7 10 11, and the
+// movable block's 14 15) only, then the hub.  The WHOLE elimination is one scheduled sequence in one asm string: what a pivot costs
+// beyond its arithmetic is wait states, and which of them are needed is known here and nowhere else.  (As a string per block the
+// compiler cannot see what the blocks write: it put `s_nop 1` worth of caution in front of every one, and one more `s_nop 0`
+// between two strings that define the same register.)  One pivot P:
+//   v_max_f32_dpp ri, hP, tiny row_newbcast:P   the pivot entry, clamped: max(h[lane P of my row], tiny) on every lane in one instruction
+//                                               (bcast + fmaxf came out as four: a zero `old`, v_mov_b32_dpp, the canonicalising
+//                                               v_max x, x, x, the v_max.  Same bits: v_max_f32 returns the other operand for a NaN
+//                                               either way.  A DPP instruction takes no literal: 1e-30 sits in a register)
+//   v_rcp_f32     ri, ri                        what the compiler has for 1.0f / x under -freciprocal-math
+//   v_cmp_eq_u32  mask', P', r                  the NEXT pivot's lane mask `r == P'`, in the wait state a transcendental's result needs
+//                                               before a VALU reads it.  This pivot's own compare cannot sit here — a VALU read of an
+//                                               SGPR wants two slots after the VALU write — so the compare rides one pivot ahead and two
+//                                               SGPR pairs alternate.  (All masks up front, the compiler's way when left to itself, ran
+//                                               out of scalar registers: round 4, 387 -> 315 v_readlane.)  Last pivot: `s_nop 0`
+//   v_mul_f32     hP, hP, -ri                   this row's multiplier nli = (r == P) ? 0 : -(h * ri), in place of the entry — nobody
+//   v_cndmask     hP, hP, 0, mask               reads the entry again, and a second right-hand side wants the multiplier (resolve_rows)
+//   v_cndmask     dinv, dinv, ri, mask          independent: fills one of the two slots between nli's write and its first DPP read
+//   s_nop 0                                     the other one — the one wait state of a pivot
+//   v_fmac_f32_dpp hk, hk, hP row_newbcast:P    h_k += nli * h_k[lane P] for the right-hand side and every column k that can still be
+//                                               non-zero in the pivot row (the arrow structure), the columns independent of each other
+// The v_max reads an entry that the elimination before it wrote as one of its columns: always the first one behind the right-hand
+// side or none — two or more instructions earlier — but for 13 -> 14 (the last column but one: one wait state), 7 -> 10 (likewise)
+// and 10 -> 11 (the last: two).  What the string reads first comes from the compiler's code: it opens with two.  tools/check_dpp_hazards.py checks the DPP rule on the built code, check_asm_valu_hazards there the other two.
+typedef unsigned long long lanemask_t;
+#define MZ_GJ_CMP(m, p) "v_cmp_eq_u32_e64 %[" #m "], " #p ", %[r]\n\t"
+#define MZ_GJ_GAP "s_nop 0\n\t"
+#define MZ_GJ_B(p) "v_fmac_f32_dpp %[b], %[b], %[h" #p "] row_newbcast:" #p MZ_DPP_TAIL
+#define MZ_GJ_E(k, p) "v_fmac_f32_dpp %[h" #k "], %[h" #k "], %[h" #p "] row_newbcast:" #p MZ_DPP_TAIL
+#define MZ_GJ_PIVOT(p, m, slot, el)                                                      \
+  "v_max_f32_dpp %[ri], %[h" #p "], %[tiny] row_newbcast:" #p MZ_DPP_TAIL                \
+  "v_rcp_f32_e32 %[ri], %[ri]\n\t" slot "v_mul_f32_e64 %[h" #p "], %[h" #p "], -%[ri]\n\t" \
+  "v_cndmask_b32_e64 %[h" #p "], %[h" #p "], 0, %[" #m "]\n\t"                             \
+  "v_cndmask_b32_e64 %[dinv], %[dinv], %[ri], %[" #m "]\n\t"                               \
+  "s_nop 0\n\t" el
+// The eight hinge pivots (0 4 8 12 | 1 5 9 13) do not wait for each other's eliminations — the entry of the next one was last
+// written two pivots earlier or never — so the next pivot's v_max / v_rcp (into the other of two registers, ri / rj) and this
+// pivot's own compare fill every slot: six instructions in front of the multiply-adds and no wait state.
+//   v_cmp mb, P, r ; v_mul hP, hP, -rk ; v_max rn, hP', tiny ; v_cndmask hP, hP, 0, mb ; v_rcp rn, rn ; v_cndmask dinv, dinv, rk, mb
+#define MZ_GJ_HINGE(p, pn, rk, rn, el)                                                                                    \
+  MZ_GJ_CMP(mb, p) "v_mul_f32_e64 %[h" #p "], %[h" #p "], -%[" #rk "]\n\t"                                                 \
+  "v_max_f32_dpp %[" #rn "], %[h" #pn "], %[tiny] row_newbcast:" #pn MZ_DPP_TAIL "v_cndmask_b32_e64 %[h" #p "], %[h" #p "], 0, %[mb]\n\t" \
+  "v_rcp_f32_e32 %[" #rn "], %[" #rn "]\n\t" "v_cndmask_b32_e64 %[dinv], %[dinv], %[" #rk "], %[mb]\n\t" el
+// ... the last of them (13, reciprocal in rj) has no independent successor: the compare of the pivot that follows (into ma) fills its
+// first gap, one wait state remains
+#define MZ_GJ_HINGE13(pn, el)                                                                                           \
+  MZ_GJ_CMP(mb, 13) "v_mul_f32_e64 %[h13], %[h13], -%[rj]\n\t" MZ_GJ_CMP(ma, pn) "v_cndmask_b32_e64 %[h13], %[h13], 0, %[mb]\n\t" \
+  "v_cndmask_b32_e64 %[dinv], %[dinv], %[rj], %[mb]\n\t" "s_nop 0\n\t" el
+#define MZ_GJ_OPEN "s_nop 1\n\tv_max_f32_dpp %[ri], %[h0], %[tiny] row_newbcast:0" MZ_DPP_TAIL "v_rcp_f32_e32 %[ri], %[ri]\n\t"
+#define MZ_GJ_ROOT(p) MZ_GJ_E(2, p) MZ_GJ_E(3, p) MZ_GJ_E(6, p) MZ_GJ_E(7, p) MZ_GJ_E(10, p) MZ_GJ_E(11, p)
+#define MZ_GJ_TAIL /* the root's own pivots: 2 3 6 7 10 11 (mask of pivot 2 in ma) */                                                          \
+  MZ_GJ_PIVOT(2, ma, MZ_GJ_CMP(mb, 3), MZ_GJ_B(2) MZ_GJ_E(3, 2) MZ_GJ_E(6, 2) MZ_GJ_E(7, 2) MZ_GJ_E(10, 2) MZ_GJ_E(11, 2))                      \
+  MZ_GJ_PIVOT(3, mb, MZ_GJ_CMP(ma, 6), MZ_GJ_B(3) MZ_GJ_E(6, 3) MZ_GJ_E(7, 3) MZ_GJ_E(10, 3) MZ_GJ_E(11, 3))                                   \
+  MZ_GJ_PIVOT(6, ma, MZ_GJ_CMP(mb, 7), MZ_GJ_B(6) MZ_GJ_E(7, 6) MZ_GJ_E(10, 6) MZ_GJ_E(11, 6))                                                \
+  MZ_GJ_PIVOT(7, mb, MZ_GJ_CMP(ma, 10), MZ_GJ_B(7) MZ_GJ_E(10, 7) MZ_GJ_E(11, 7))                                                             \
+  "s_nop 0\n\t" MZ_GJ_PIVOT(10, ma, MZ_GJ_CMP(mb, 11), MZ_GJ_B(10) MZ_GJ_E(11, 10)) "s_nop 1\n\t" MZ_GJ_PIVOT(11, mb, MZ_GJ_GAP, MZ_GJ_B(11))
+#define MZ_GJ_OPS14                                                                                                                          \
+  [b] "+v"(b), [dinv] "+v"(dinv), [h0] "+v"(H[0]), [h1] "+v"(H[1]), [h2] "+v"(H[2]), [h3] "+v"(H[3]), [h4] "+v"(H[4]), [h5] "+v"(H[5]),        \
+      [h6] "+v"(H[6]), [h7] "+v"(H[7]), [h8] "+v"(H[8]), [h9] "+v"(H[9]), [h10] "+v"(H[10]), [h11] "+v"(H[11]), [h12] "+v"(H[12]), [h13] "+v"(H[13])
+#define MZ_GJ_TMP [ri] "=&v"(ri), [rj] "=&v"(rj), [ma] "=&s"(ma), [mb] "=&s"(mb) : [tiny] "v"(tiny), [r] "v"(r)
+// In: H = this lane's row, b its right-hand side.  Out: the solution's entry; H[P] = this row's multiplier of pivot P and dinv the
+// reciprocal of its own pivot, for a second right-hand side (resolve_rows; dead code where nobody asks).
+__device__ __forceinline__ float solve_rows(int r, float (&H)[14], float b, float& dinv) {
   dinv = 0.f;
-  const float tiny = pivot_floor();
-  // the four legs do not couple: their hip pivots (then their ankle pivots) are independent chains — issued next to each
-  // other so that the reciprocal / broadcast latencies of one hide behind the others
-  pivot<0, 14, 1, 2, 3, 6, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
-  pivot<4, 14, 5, 2, 3, 6, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
-  pivot<8, 14, 9, 2, 3, 6, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
-  pivot<12, 14, 13, 2, 3, 6, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
-  pivot<1, 14, 2, 3, 6, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
-  pivot<5, 14, 2, 3, 6, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
-  pivot<9, 14, 2, 3, 6, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
-  pivot<13, 14, 2, 3, 6, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
-  pivot<2, 14, 3, 6, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
-  pivot<3, 14, 6, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
-  pivot<6, 14, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
-  pivot<7, 14, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
-  pivot<10, 14, 11>(r, tiny, Hrow, b, dinv, mlt);
-  pivot<11, 14>(r, tiny, Hrow, b, dinv, mlt);
+  float tiny = 1e-30f, ri, rj;
+  asm("" : "+v"(tiny));  // opaque: set up here, once per solve, not held in a register through the whole step
+  lanemask_t ma, mb;
+  asm(MZ_GJ_OPEN  // the four legs do not couple: hip pivots, then ankle pivots
+      MZ_GJ_HINGE(0, 4, ri, rj, MZ_GJ_B(0) MZ_GJ_E(1, 0) MZ_GJ_ROOT(0))
+      MZ_GJ_HINGE(4, 8, rj, ri, MZ_GJ_B(4) MZ_GJ_E(5, 4) MZ_GJ_ROOT(4))
+      MZ_GJ_HINGE(8, 12, ri, rj, MZ_GJ_B(8) MZ_GJ_E(9, 8) MZ_GJ_ROOT(8))
+      MZ_GJ_HINGE(12, 1, rj, ri, MZ_GJ_B(12) MZ_GJ_E(13, 12) MZ_GJ_ROOT(12))
+      MZ_GJ_HINGE(1, 5, ri, rj, MZ_GJ_B(1) MZ_GJ_ROOT(1))
+      MZ_GJ_HINGE(5, 9, rj, ri, MZ_GJ_B(5) MZ_GJ_ROOT(5))
+      MZ_GJ_HINGE(9, 13, ri, rj, MZ_GJ_B(9) MZ_GJ_ROOT(9))
+      MZ_GJ_HINGE13(2, MZ_GJ_B(13) MZ_GJ_ROOT(13))
+      MZ_GJ_TAIL
+      : MZ_GJ_OPS14, MZ_GJ_TMP);
   return b * dinv;
 }
 __device__ __forceinline__ float solve_rows(int r, float (&Hrow)[14], float b) {
-  float mlt[14], dinv;
-  return solve_rows(r, Hrow, b, mlt, dinv);
+  float dinv;
+  return solve_rows(r, Hrow, b, dinv);
 }
 // the same with one movable block: its two slides (positions 14, 15) belong to the hub (a robot-block contact couples them with the
 // root and with one leg), eliminated between the legs and the root
-__device__ __forceinline__ float solve_rows(int r, float (&Hrow)[16], float b, float (&mlt)[16], float& dinv) {
+#define MZ_GJ_HUB16(p) MZ_GJ_ROOT(p) MZ_GJ_E(14, p) MZ_GJ_E(15, p)
+__device__ __forceinline__ float solve_rows(int r, float (&H)[16], float b, float& dinv) {
   dinv = 0.f;
-  const float tiny = pivot_floor();
-  pivot<0, 16, 1, 2, 3, 6, 7, 10, 11, 14, 15>(r, tiny, Hrow, b, dinv, mlt);
-  pivot<4, 16, 5, 2, 3, 6, 7, 10, 11, 14, 15>(r, tiny, Hrow, b, dinv, mlt);
-  pivot<8, 16, 9, 2, 3, 6, 7, 10, 11, 14, 15>(r, tiny, Hrow, b, dinv, mlt);
-  pivot<12, 16, 13, 2, 3, 6, 7, 10, 11, 14, 15>(r, tiny, Hrow, b, dinv, mlt);
-  pivot<1, 16, 2, 3, 6, 7, 10, 11, 14, 15>(r, tiny, Hrow, b, dinv, mlt);
-  pivot<5, 16, 2, 3, 6, 7, 10, 11, 14, 15>(r, tiny, Hrow, b, dinv, mlt);
-  pivot<9, 16, 2, 3, 6, 7, 10, 11, 14, 15>(r, tiny, Hrow, b, dinv, mlt);
-  pivot<13, 16, 2, 3, 6, 7, 10, 11, 14, 15>(r, tiny, Hrow, b, dinv, mlt);
-  pivot<14, 16, 15, 2, 3, 6, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
-  pivot<15, 16, 2, 3, 6, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
-  pivot<2, 16, 3, 6, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
-  pivot<3, 16, 6, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
-  pivot<6, 16, 7, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
-  pivot<7, 16, 10, 11>(r, tiny, Hrow, b, dinv, mlt);
-  pivot<10, 16, 11>(r, tiny, Hrow, b, dinv, mlt);
-  pivot<11, 16>(r, tiny, Hrow, b, dinv, mlt);
+  float tiny = 1e-30f, ri, rj;
+  asm("" : "+v"(tiny));  // opaque: set up here, once per solve, not held in a register through the whole step
+  lanemask_t ma, mb;
+  asm(MZ_GJ_OPEN
+      MZ_GJ_HINGE(0, 4, ri, rj, MZ_GJ_B(0) MZ_GJ_E(1, 0) MZ_GJ_HUB16(0))
+      MZ_GJ_HINGE(4, 8, rj, ri, MZ_GJ_B(4) MZ_GJ_E(5, 4) MZ_GJ_HUB16(4))
+      MZ_GJ_HINGE(8, 12, ri, rj, MZ_GJ_B(8) MZ_GJ_E(9, 8) MZ_GJ_HUB16(8))
+      MZ_GJ_HINGE(12, 1, rj, ri, MZ_GJ_B(12) MZ_GJ_E(13, 12) MZ_GJ_HUB16(12))
+      MZ_GJ_HINGE(1, 5, ri, rj, MZ_GJ_B(1) MZ_GJ_HUB16(1))
+      MZ_GJ_HINGE(5, 9, rj, ri, MZ_GJ_B(5) MZ_GJ_HUB16(5))
+      MZ_GJ_HINGE(9, 13, ri, rj, MZ_GJ_B(9) MZ_GJ_HUB16(9))
+      MZ_GJ_HINGE13(14, MZ_GJ_B(13) MZ_GJ_HUB16(13))
+      "s_nop 0\n\t" MZ_GJ_PIVOT(14, ma, MZ_GJ_CMP(mb, 15), MZ_GJ_B(14) MZ_GJ_E(15, 14) MZ_GJ_ROOT(14))
+      MZ_GJ_PIVOT(15, mb, MZ_GJ_CMP(ma, 2), MZ_GJ_B(15) MZ_GJ_ROOT(15))
+      MZ_GJ_TAIL
+      : MZ_GJ_OPS14, [h14] "+v"(H[14]), [h15] "+v"(H[15]), MZ_GJ_TMP);
   return b * dinv;
 }
-
 __device__ __forceinline__ float solve_rows(int r, float (&Hrow)[16], float b) {
-  float mlt[16], dinv;
-  return solve_rows(r, Hrow, b, mlt, dinv);
+  float dinv;
+  return solve_rows(r, Hrow, b, dinv);
 }
 // A second right-hand side through the SAME elimination (iterative refinement of the Newton step, ant_solve_rows_core): the pivots
 // of solve_rows in their order, each one instruction on the right-hand side alone — b_r += mlt_P(r) * b[lane P] — then the diagonal.
-template <int P>
-__device__ __forceinline__ void repivot(float m, float& b) { elim<P>(m, b); }
+// A chain through b: every link reads what the link before it wrote, so each has its two wait states; in one string they are all
+// it has (as a string per link the compiler put a third between two strings that define the same register).
+#define MZ_RP(p) "s_nop 1\n\tv_fmac_f32_dpp %[b], %[b], %[h" #p "] row_newbcast:" #p MZ_DPP_TAIL
+#define MZ_RP_LEGS MZ_RP(0) MZ_RP(4) MZ_RP(8) MZ_RP(12) MZ_RP(1) MZ_RP(5) MZ_RP(9) MZ_RP(13)
+#define MZ_RP_ROOT MZ_RP(2) MZ_RP(3) MZ_RP(6) MZ_RP(7) MZ_RP(10) MZ_RP(11)
+#define MZ_RP_IN14                                                                                                                              \
+  [h0] "v"(mlt[0]), [h1] "v"(mlt[1]), [h2] "v"(mlt[2]), [h3] "v"(mlt[3]), [h4] "v"(mlt[4]), [h5] "v"(mlt[5]), [h6] "v"(mlt[6]), [h7] "v"(mlt[7]), \
+      [h8] "v"(mlt[8]), [h9] "v"(mlt[9]), [h10] "v"(mlt[10]), [h11] "v"(mlt[11]), [h12] "v"(mlt[12]), [h13] "v"(mlt[13])
 __device__ __forceinline__ float resolve_rows(const float (&mlt)[16], float dinv, float b) {
-  repivot<0>(mlt[0], b); repivot<4>(mlt[4], b); repivot<8>(mlt[8], b); repivot<12>(mlt[12], b);
-  repivot<1>(mlt[1], b); repivot<5>(mlt[5], b); repivot<9>(mlt[9], b); repivot<13>(mlt[13], b);
-  repivot<14>(mlt[14], b); repivot<15>(mlt[15], b);
-  repivot<2>(mlt[2], b); repivot<3>(mlt[3], b); repivot<6>(mlt[6], b); repivot<7>(mlt[7], b); repivot<10>(mlt[10], b); repivot<11>(mlt[11], b);
+  asm(MZ_RP_LEGS MZ_RP(14) MZ_RP(15) MZ_RP_ROOT : [b] "+v"(b) : MZ_RP_IN14, [h14] "v"(mlt[14]), [h15] "v"(mlt[15]));
   return b * dinv;
 }
 __device__ __forceinline__ float resolve_rows(const float (&mlt)[14], float dinv, float b) {
-  repivot<0>(mlt[0], b); repivot<4>(mlt[4], b); repivot<8>(mlt[8], b); repivot<12>(mlt[12], b);
-  repivot<1>(mlt[1], b); repivot<5>(mlt[5], b); repivot<9>(mlt[9], b); repivot<13>(mlt[13], b);
-  repivot<2>(mlt[2], b); repivot<3>(mlt[3], b); repivot<6>(mlt[6], b); repivot<7>(mlt[7], b); repivot<10>(mlt[10], b); repivot<11>(mlt[11], b);
+  asm(MZ_RP_LEGS MZ_RP_ROOT : [b] "+v"(b) : MZ_RP_IN14);
   return b * dinv;
 }
 
@@ -359,14 +396,31 @@ __device__ __forceinline__ float resolve_rows(const float (&mlt)[14], float dinv
 // three accumulators (the DPP read-after-write rule: ant_newton_rows.h; checked by tools/check_dpp_hazards.py)
 #define MZ_D6_MUL(o, k) "v_mul_f32_dpp %" #o ", %[f" #k "], %[s" #k "] row_newbcast:%[q]" MZ_DPP_TAIL
 #define MZ_D6_FMA(o, k) "v_fmac_f32_dpp %" #o ", %[f" #k "], %[s" #k "] row_newbcast:%[q]" MZ_DPP_TAIL
-template <int Q>
+template <int Q, int W = 2>
 __device__ __forceinline__ float dot6_from(const float (&F)[6], const float (&S)[6]) {
   float a0, a1, a2;
-  asm("s_nop 1\n\t" MZ_D6_MUL(0, 0) MZ_D6_MUL(1, 1) MZ_D6_MUL(2, 2) MZ_D6_FMA(0, 3) MZ_D6_FMA(1, 4) MZ_D6_FMA(2, 5)
+  MZ_ASM_W(W, MZ_D6_MUL(0, 0) MZ_D6_MUL(1, 1) MZ_D6_MUL(2, 2) MZ_D6_FMA(0, 3) MZ_D6_FMA(1, 4) MZ_D6_FMA(2, 5),
       : "=&v"(a0), "=&v"(a1), "=&v"(a2)
       : [f0] "v"(F[0]), [f1] "v"(F[1]), [f2] "v"(F[2]), [f3] "v"(F[3]), [f4] "v"(F[4]), [f5] "v"(F[5]), [s0] "v"(S[0]), [s1] "v"(S[1]), [s2] "v"(S[2]),
         [s3] "v"(S[3]), [s4] "v"(S[4]), [s5] "v"(S[5]), [q] "n"(Q));
   return (a0 + a1) + a2;
+}
+// ... for the three wrenches of a contact at once (wr_col): the same eighteen instructions, nine accumulators round-robin, behind ONE
+// opening pair of wait states instead of three
+#define MZ_D63_MUL(a, k) "v_mul_f32_dpp %[o" #a #k "], %[f" #a #k "], %[s" #k "] row_newbcast:%[q]" MZ_DPP_TAIL
+#define MZ_D63_FMA(a, k, k3) "v_fmac_f32_dpp %[o" #a #k "], %[f" #a #k3 "], %[s" #k3 "] row_newbcast:%[q]" MZ_DPP_TAIL
+#define MZ_D63_F(a) [f##a##0] "v"(F[a][0]), [f##a##1] "v"(F[a][1]), [f##a##2] "v"(F[a][2]), [f##a##3] "v"(F[a][3]), [f##a##4] "v"(F[a][4]), [f##a##5] "v"(F[a][5])
+#define MZ_D63_O(a) [o##a##0] "=&v"(acc[a][0]), [o##a##1] "=&v"(acc[a][1]), [o##a##2] "=&v"(acc[a][2])
+template <int Q, int W = 2>
+__device__ __forceinline__ void dot6x3_from(const float (&F)[3][6], const float (&S)[6], float (&o)[3]) {
+  float acc[3][3];
+  MZ_ASM_W(W, MZ_D63_MUL(0, 0) MZ_D63_MUL(0, 1) MZ_D63_MUL(0, 2) MZ_D63_MUL(1, 0) MZ_D63_MUL(1, 1) MZ_D63_MUL(1, 2) MZ_D63_MUL(2, 0) MZ_D63_MUL(2, 1) MZ_D63_MUL(2, 2)
+           MZ_D63_FMA(0, 0, 3) MZ_D63_FMA(0, 1, 4) MZ_D63_FMA(0, 2, 5) MZ_D63_FMA(1, 0, 3) MZ_D63_FMA(1, 1, 4) MZ_D63_FMA(1, 2, 5) MZ_D63_FMA(2, 0, 3)
+           MZ_D63_FMA(2, 1, 4) MZ_D63_FMA(2, 2, 5),
+           : MZ_D63_O(0), MZ_D63_O(1), MZ_D63_O(2)
+           : MZ_D63_F(0), MZ_D63_F(1), MZ_D63_F(2), [s0] "v"(S[0]), [s1] "v"(S[1]), [s2] "v"(S[2]), [s3] "v"(S[3]), [s4] "v"(S[4]), [s5] "v"(S[5]), [q] "n"(Q));
+#pragma unroll
+  for (int a = 0; a < 3; a++) o[a] = (acc[a][0] + acc[a][1]) + acc[a][2];
 }
 // pyramidal contact: cost, and optionally gradient block g[3] / curvature block W[5] (same as contact_eval)
 __device__ __forceinline__ float ceval(float D, float u0, float u1, float u2) {
@@ -777,8 +831,10 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
     const int mc = bcast_i<(C & 15)>(wmeta[C / 16]), lc = mc & 7, cc = (mc >> 3) & 7;
     const bool sees = C < ncon && (ishinge ? (leg == lc && (d == 0 ? cc >= 2 : cc == 3)) : (r < 12 || (NB == 1 && r >= 14 && (mc & 64) != 0)));
     const int on = -(int)sees;
+    float dots[3];
+    dot6x3_from<(C & 15)>(wr[C / 16], Sax, dots);
 #pragma unroll
-    for (int a = 0; a < 3; a++) o[a] = __int_as_float(__float_as_int(dot6_from<(C & 15)>(wr[C / 16][a], Sax)) & on);
+    for (int a = 0; a < 3; a++) o[a] = __int_as_float(__float_as_int(dots[a]) & on);
   };
   auto own_col = [&](auto Cc, float (&o)[3]) {
     constexpr int C = decltype(Cc)::value;
@@ -997,12 +1053,10 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
     each_contact([&](auto Cc) {
       constexpr int C = decltype(Cc)::value;
       {  // (no per-row guard `C < ncon`, as in jdot3)
-        float t, t0, t1, t2;
         float jc[3];
         own_col(Cc, jc);
-        fold_t<(C & 15)>(mycg[C / 16], jc[0], jc[1], jc[2], t, t0, t1, t2);
+        const float t = fold_th<(C & 15)>(Hrow, mycg[C / 16], jc[0], jc[1], jc[2]);
         g += t; ga += fabsf(t);
-        fold_h(Hrow, jc[0], jc[1], jc[2], t0, t1, t2);
       }
     });
     if constexpr (NB == 1) {
@@ -1020,15 +1074,15 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
     // less per evaluation (A / B: 0.2470 -> 0.2456 ms).
     float gnorm = 0.f, anorm = 0.f;
     if (it > 0) {
-      rsum2(g * g, ga * ga, gnorm, anorm);
+      rsum2_sq(g, ga, gnorm, anorm);
       gnorm = sqrtf(gnorm); anorm = sqrtf(anorm);
       if (!done && (ant_u(cx, K).inv_scale * gnorm < ant_u(cx, K).tol || gnorm <= ant_u(cx, K).rtol * anorm)) done = true;
     }
     if (!cx.any(!done)) { cx.tick(s, 5); break; }
     cx.tick(s, 5);
     // ---- Newton direction: H search = -grad
-    float mlt[NR], dinv;
-    const float search = solve_rows(r, Hrow, -g, mlt, dinv);
+    float dinv;
+    const float search = solve_rows(r, Hrow, -g, dinv);  // (Hrow: from here on this row's multipliers)
     cx.tick(s, 6);
     // ---- J search on the contact lanes, limit rows on their own dofs; vote on the active set
     jdot3(search, v);
@@ -1057,8 +1111,7 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
     if (changed) {  // exact line search on phi(alpha) = cost(qacc + alpha search): safeguarded Newton on the piecewise-linear phi'
       Ms = matvec(Mrow, search);
       float p1, p2;
-      rsum2(search * Mx, search * Ms, p1, p2);
-      rsum2(isdof ? search * search : 0.f, isdof ? qacc * qacc : 0.f, sn, qn);
+      rsum4(search * Mx, search * Ms, isdof ? search * search : 0.f, isdof ? qacc * qacc : 0.f, p1, p2, sn, qn);
       float lo = 0.f, hi = -1.f, prev_d2 = -1.f;  // phi'(0) < 0 (descent direction); hi < 0: no upper bracket yet
       // Round 5: the first K.ls_fast_iters (5) iterations of an evaluation take the UNIT step when the active set changes (K.ls_fast = 0
       // evaluations of phi'), later ones search the line exactly as before.  What the line search buys is global convergence, not
@@ -1178,7 +1231,7 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
           if (r == 15) g2 += c1;
         }
         if (!isdof) g2 = 0.f;
-        const float corr = resolve_rows(mlt, dinv, -g2);
+        const float corr = resolve_rows(Hrow, dinv, -g2);
         if (exact && !done) qacc += corr;
       }
     }

@@ -94,6 +94,59 @@ def check_stream(name, insts, jumps):
     return bad, ndpp
 
 
+TRANS_RE = re.compile(r"^v_(rcp|rsq|sqrt|exp|log|sin|cos)(_iflag|_legacy|_clamp)?_(f32|f16|f64)$")
+SREG_RE = re.compile(r"\bs(\d+)\b|\bs\[(\d+):(\d+)\]|\b(vcc)(?:_lo|_hi)?\b")
+
+
+def sregs(text):
+    out = set()
+    for m in SREG_RE.finditer(text):
+        if m.group(1) is not None:
+            out.add(int(m.group(1)))
+        elif m.group(2) is not None:
+            out.update(range(int(m.group(2)), int(m.group(3)) + 1))
+        else:
+            out.add("vcc")
+    return out
+
+
+def check_asm_valu_hazards(name, insts):
+    """Two more rules of gfx940 / gfx950 that the compiler keeps for its own instructions (GCNHazardRecognizer: TransDefWaitstates
+    = 1, VALUWriteSGPRVALUReadWaitstates = 2) and cannot keep inside an `asm` string — rows::solve_rows has v_rcp_f32 and v_cmp in
+    one — checked on the straight-line stream:
+      * the result of a transcendental VALU instruction is not read by another VALU instruction in the next issue slot;
+      * an SGPR (or VCC) written by a VALU instruction is not read by a VALU instruction in the next two issue slots."""
+    carry = ("v_mad_u64_u32", "v_mad_i64_i32", "v_add_co", "v_sub_co", "v_subrev_co", "v_addc_co", "v_subb_co", "v_subbrev_co", "v_div_scale")
+
+    def split(mn, ops):
+        """(VGPRs written, SGPRs written, VGPRs read, SGPRs read) of a VALU instruction's operand text"""
+        parts = [x for x in DPP_RE.split(ops)[0].split(",")]
+        nd = 2 if mn.startswith(carry) else 1  # (vdst, sdst carry-out, sources ...)
+        dst, src = ",".join(parts[:nd]), ",".join(parts[nd:])
+        rv = vregs(src) | (vregs(parts[0]) if mn.startswith(("v_fmac", "v_mac")) else set())
+        return vregs(parts[0]), sregs(dst), rv, sregs(src)
+
+    bad = []
+    for i, (key, mn, ops) in enumerate(insts):
+        if not mn.startswith("v_"):
+            continue
+        _, _, rv, rs = split(mn, ops)
+        slots, j = [], i - 1  # the two issue slots in front of instruction i: (mnemonic, operands) or None for a wait state
+        while j >= 0 and len(slots) < 2:
+            pmn, pops = insts[j][1], insts[j][2]
+            slots += [None] * (int(pops.strip() or "0", 0) + 1) if pmn == "s_nop" else [(pmn, pops)]
+            j -= 1
+        for d, prev in enumerate(slots[:2]):
+            if prev is None or not prev[0].startswith("v_"):
+                continue
+            wv, ws, _, _ = split(prev[0], prev[1])
+            if d == 0 and TRANS_RE.match(prev[0]) and not TRANS_RE.match(mn) and wv & rv:
+                bad.append(f"{name}: {key}: {mn} {ops.strip()}  <- reads the result of {prev[0]} in the next issue slot")
+            if ws & rs:
+                bad.append(f"{name}: {key}: {mn} {ops.strip()}  <- reads an SGPR that {prev[0]} wrote less than two issue slots earlier")
+    return bad
+
+
 def parse_compiler_s(path):
     funcs, cur = [], None
     for ln, line in enumerate(open(path), 1):
@@ -181,7 +234,7 @@ def main(argv):
     total_bad, total_dpp = [], 0
     for f in funcs:
         bad, ndpp = check_stream(f["name"][:60], f["insts"], f["jumps"])
-        total_bad += bad
+        total_bad += bad + check_asm_valu_hazards(f["name"][:60], f["insts"])
         total_dpp += ndpp
     for b in total_bad[:50]:
         print(b)
