@@ -48,6 +48,7 @@ extern "C" {
 #define MZ_MAX_GOAL 8
 #define MZ_MAX_OBS 48        /* observation without the top-down view */
 #define MZ_VIEW_DIM 75       /* MazeEnv.get_top_down_view: 5 x 5 cells x (walls, chasms, movable blocks), maze_env.py:95 */
+#define MZ_POLICY_MAX_HIDDEN 64 /* widest hidden layer of a device-side policy (mz_policy_act / mz_rollout_policy, csrc/mz_policy.h) */
 
 /* robot kinds */
 #define MZ_ROBOT_POINT 0
@@ -318,7 +319,8 @@ int32_t mz_bind_env_goals(mz_handle* h, const double* goal_pos_dev, void* stream
 /* reset(): envs with mask_dev[i] != 0 (all when NULL) get t = 0 and a fresh state
  * from the reference's reset distribution (counter-based RNG keyed by seed and
  * env slot; streams differ from numpy's — distributional parity only).
- * obs_dev [N, obs_dim] may be NULL. */
+ * obs_dev [N, obs_dim] may be NULL.  Rows of envs the mask leaves alone are written too, from their present state and t: with an
+ * all-zero mask the call resets nothing and returns every env's current observation (e.g. after mz_set_state). */
 int32_t mz_reset(mz_handle* h, const uint8_t* mask_dev, uint64_t seed, float* obs_dev, void* stream);
 
 /* State injection / read-back (row-major [N, nq], [N, nv], [N, nv], [N]).
@@ -363,6 +365,49 @@ int32_t mz_step(mz_handle* h, const float* actions_dev, float* obs_dev, float* r
  * unaffected by this call.  Returns MZ_OK, MZ_ERR_ARG (NULL handle or required array, n_steps or stride out of range) or MZ_ERR_HIP. */
 int32_t mz_rollout(mz_handle* h, int32_t n_steps, const float* actions_dev, int64_t action_step_stride, float* obs_dev,
                    float* reward_dev, uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev, float* obs_seq_dev, void* stream);
+
+/* Device-side policies (closed-loop rollouts): a small policy evaluated where the observation already sits, for population methods
+ * with one policy per env and for evaluating a trained linear or one-hidden-layer policy over whole episodes.
+ *
+ * One policy is `npar` fp32 numbers, weights input-major (nn.Linear.weight.T: adjacent output units at adjacent addresses), with
+ * obs_dim = mz_obs_dim (the top-down view included where the task has one) and nu = mz_nu:
+ *   hidden == 0 (affine)                  Wt [obs_dim][nu], b [nu]                                   npar = obs_dim * nu + nu
+ *   1 <= hidden <= MZ_POLICY_MAX_HIDDEN   W1t [obs_dim][H], b1 [H], W2t [H][nu], b2 [nu]            npar = obs_dim * H + H + H * nu + nu
+ * Arithmetic (csrc/mz_policy.h, the one definition every kernel and the host build compile): each unit starts from its bias and
+ * adds w * x over the inputs in index order, in fp32, the multiply and the add rounded separately (no fused multiply-add); hidden
+ * units are tanhf of that sum; an output is the sum itself (squash == 0) or (float)action_scale * tanhf(sum) (squash == 1).  NaN
+ * propagates.  The affine, unsquashed case is therefore reproduced bit for bit by fp32 arithmetic anywhere (mujoco_maze_amd/policy.py
+ * reference); the tanh cases carry the tanhf of the library that runs them and are bit-equal between the device kernels only.
+ *  params_dev        [npar] (param_env_stride == 0: one policy shared by all envs) or [N, npar] (param_env_stride == npar: env i
+ *                    reads params_dev + i * npar); any other stride is MZ_ERR_ARG
+ *
+ * mz_policy_act: actions_dev[r] = policy(obs_dev[r]) for the N rows; obs_dev [N, obs_dim], actions_dev [N, nu].  The actions are
+ * the policy's outputs, not clamped to the control range (the step clamps where the reference does).
+ *
+ * mz_rollout_policy: n_steps times a = policy(obs); obs, reward, done, ... = step(a).  The call leaves the handle and every output
+ * exactly as this loop on the same stream would:
+ *     for k in 0 .. n_steps - 1:
+ *         mz_policy_act(obs_dev -> a_k)
+ *         mz_step(a_k -> obs_dev, row k of reward_dev / done_dev / goal_idx_dev / info_dev)
+ * — state, t, episode counters, warm start, status words, the bound final_obs buffer and the bound record (the last step's row).
+ * Under auto-reset the policy acts on the first observation of the new episode, as it would in the loop.
+ *  obs_dev [N, obs_dim] is IN/OUT: on entry the observation the policy acts on first — what the last mz_step / mz_reset /
+ *          mz_rollout / mz_rollout_policy wrote there —, on return the last step's observation.  mz_set_state does NOT refresh
+ *          the caller's observation buffer; after it, mz_reset with an all-zero mask writes every env's current observation
+ *          without resetting any (every engine's reset kernel writes the rows of unmasked envs from their present state and t).
+ *  n_steps 1 .. 65536; reward_dev, done_dev, goal_idx_dev, info_dev, obs_seq_dev as in mz_rollout
+ *  actions_seq_dev [n_steps, N, nu] (nullable): the actions the policy produced, before the env's own control clamp
+ * Handles with "rollout_fused" = 1 (mz_get_info) evaluate the policy inside the fused rollout kernels, between two steps, on the
+ * observation row that stays on chip (launches of at most 256 steps, each of which writes obs_dev at its last step and the next
+ * picks it up from there); every other handle runs the loop above inside the call, launch by launch, with a_k in row k of
+ * actions_seq_dev or in a scratch buffer of the handle.  The "time_kernels" ring does not record these calls.
+ * Both return MZ_OK, MZ_ERR_ARG (NULL handle or required array, hidden outside 0 .. MZ_POLICY_MAX_HIDDEN, squash outside {0, 1},
+ * a stride that is neither 0 nor npar, n_steps out of range) or MZ_ERR_HIP. */
+int32_t mz_policy_act(mz_handle* h, const float* params_dev, int64_t param_env_stride, int32_t hidden, int32_t squash,
+                      double action_scale, const float* obs_dev, float* actions_dev, void* stream);
+int32_t mz_rollout_policy(mz_handle* h, int32_t n_steps, const float* params_dev, int64_t param_env_stride, int32_t hidden,
+                          int32_t squash, double action_scale, float* obs_dev, float* reward_dev, uint8_t* done_dev,
+                          int32_t* goal_idx_dev, float* info_dev, float* obs_seq_dev, float* actions_seq_dev, void* stream);
 
 /* Per-env status words accumulated since the last call (then cleared). [N] i32. */
 int32_t mz_get_status(mz_handle* h, int32_t* status_dev, void* stream);

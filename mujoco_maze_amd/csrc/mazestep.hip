@@ -9,6 +9,7 @@
 #include <new>
 
 #include "mz_internal.h"
+#include "mz_policy.h"
 #include "mz_render.h"
 
 __global__ void fetch_clear_status_kernel(int n, int* status, int* out) {
@@ -28,6 +29,22 @@ __global__ void pack_record_kernel(int n, int obs_dim, const float* __restrict__
   if (idx >= (size_t)n * w) return;
   const int env = (int)(idx / w), i = (int)(idx - (size_t)env * w);
   record[idx] = i < obs_dim ? obs[(size_t)env * obs_dim + i] : (i == obs_dim ? reward[env] : (float)done[env]);
+}
+
+// actions[r] = policy(obs[r]) for n rows (mz_policy_act; mz_rollout_policy where it steps launch by launch): the policy of mz_policy.h,
+// one group of MZ_POLICY_LANES adjacent lanes per row — lanes l, l + 16, .. own hidden units, lanes 0 .. nu - 1 the outputs.  Engine-
+// independent.  params: one policy (pstride = 0) or row r's own at params + r * pstride.  Surplus groups shadow the last row (no stores).
+constexpr int MZ_POLICY_LANES = 16;
+__global__ __launch_bounds__(256) void policy_act_kernel(int n, int obs_dim, int nu, int hidden, int squash, float action_scale,
+                                                         const float* __restrict__ params, long pstride, const float* __restrict__ obs,
+                                                         float* __restrict__ actions) {
+  __shared__ float hid[256 / MZ_POLICY_LANES][MZ_POLICY_MAX_HIDDEN];
+  const int l = (int)threadIdx.x % MZ_POLICY_LANES, grp = (int)threadIdx.x / MZ_POLICY_LANES;
+  size_t row = (size_t)blockIdx.x * (256 / MZ_POLICY_LANES) + grp;
+  const bool live = row < (size_t)n;
+  if (!live) row = (size_t)n - 1;
+  mzp_group_eval(l, MZ_POLICY_LANES, params + row * pstride, obs_dim, nu, hidden, squash, action_scale, obs + row * obs_dim, hid[grp],
+                 actions + row * nu, live);
 }
 
 static int set_err(mz_handle* h, int code, const char* what, hipError_t e) {
@@ -162,6 +179,7 @@ void mz_destroy(mz_handle* h) {
   if (h->status) (void)hipFree(h->status);
   if (h->prof) (void)hipFree(h->prof);
   if (h->render_qpos) (void)hipFree(h->render_qpos);
+  if (h->policy_act) (void)hipFree(h->policy_act);
   if (h->ev) { for (int i = 0; i < 2 * h->ntime; i++) (void)hipEventDestroy(h->ev[i]); free(h->ev); }
   delete h;
 }
@@ -418,6 +436,78 @@ int32_t mz_rollout(mz_handle* h, int32_t n_steps, const float* actions_dev, int6
     for (size_t k = 0; k < (size_t)n_steps; k++) {
       const int rc = step_launches(h, st, actions_dev + k * (size_t)action_step_stride, obs_dev, reward_dev + k * n, done_dev + k * n,
                                    goal_idx_dev ? goal_idx_dev + k * n : NULL, info_dev ? info_dev + k * n * 4 : NULL);
+      if (rc != MZ_OK) return rc;
+      if (obs_seq_dev) HIPCHK(h, hipMemcpyAsync(obs_seq_dev + k * n * od, obs_dev, n * od * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
+  }
+  h->nsteps += n_steps;
+  return MZ_OK;
+}
+
+// the checks mz_policy_act and mz_rollout_policy share; MZ_OK or MZ_ERR_ARG with the message set
+static int policy_args(mz_handle* h, const char* who, const float* params_dev, int64_t param_env_stride, int32_t hidden, int32_t squash) {
+  char msg[160];
+  const char* why = nullptr;
+  if (!params_dev) why = "null params_dev";
+  else if (hidden < 0 || hidden > MZ_POLICY_MAX_HIDDEN) why = "hidden must be 0 .. MZ_POLICY_MAX_HIDDEN (64)";
+  else if (squash != 0 && squash != 1) why = "squash must be 0 or 1";
+  else if (param_env_stride != 0 && param_env_stride != (int64_t)mzp_param_count(h->model.obs_dim, h->model.nu, hidden))
+    why = "param_env_stride must be 0 (one shared policy) or npar (one policy per env)";
+  if (!why) return MZ_OK;
+  snprintf(msg, sizeof(msg), "%s: %s", who, why);
+  return set_err(h, MZ_ERR_ARG, msg, hipSuccess);
+}
+
+static void policy_act_launch(mz_handle* h, hipStream_t st, const float* params_dev, int64_t pstride, int hidden, int squash, float scale,
+                              const float* obs_dev, float* actions_dev) {
+  const int rows = 256 / MZ_POLICY_LANES;
+  hipLaunchKernelGGL(policy_act_kernel, dim3((unsigned)((h->n + rows - 1) / rows)), dim3(256), 0, st, h->n, h->model.obs_dim, h->model.nu, hidden, squash,
+                     scale, params_dev, (long)pstride, obs_dev, actions_dev);
+}
+
+int32_t mz_policy_act(mz_handle* h, const float* params_dev, int64_t param_env_stride, int32_t hidden, int32_t squash, double action_scale,
+                      const float* obs_dev, float* actions_dev, void* stream) {
+  if (!h) return MZ_ERR_ARG;
+  if (!obs_dev || !actions_dev) return set_err(h, MZ_ERR_ARG, "mz_policy_act: null array", hipSuccess);
+  const int rc = policy_args(h, "mz_policy_act", params_dev, param_env_stride, hidden, squash);
+  if (rc != MZ_OK) return rc;
+  DeviceScope scope(h->device);
+  policy_act_launch(h, (hipStream_t)stream, params_dev, param_env_stride, hidden, squash, (float)action_scale, obs_dev, actions_dev);
+  HIPCHK(h, hipGetLastError());
+  return MZ_OK;
+}
+
+// n_steps times a = policy(obs); step(a) in one call (include/mazestep.h).  Fused handles evaluate the policy inside the rollout
+// kernels (planar_kernels.hip); every other handle runs the defining loop itself: policy_act_kernel into row k of actions_seq_dev (or
+// the handle's scratch), then the step's own launches.
+int32_t mz_rollout_policy(mz_handle* h, int32_t n_steps, const float* params_dev, int64_t param_env_stride, int32_t hidden, int32_t squash,
+                          double action_scale, float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev,
+                          float* obs_seq_dev, float* actions_seq_dev, void* stream) {
+  if (!h) return MZ_ERR_ARG;
+  if (!obs_dev || !reward_dev || !done_dev) return set_err(h, MZ_ERR_ARG, "mz_rollout_policy: null array", hipSuccess);
+  if (n_steps < 1 || n_steps > 65536) return set_err(h, MZ_ERR_ARG, "mz_rollout_policy: n_steps must be 1 .. 65536", hipSuccess);
+  int rc = policy_args(h, "mz_rollout_policy", params_dev, param_env_stride, hidden, squash);
+  if (rc != MZ_OK) return rc;
+  const size_t n = (size_t)h->n, od = (size_t)h->model.obs_dim, nu = (size_t)h->model.nu;
+  const float scale = (float)action_scale;
+  DeviceScope scope(h->device);
+  hipStream_t st = (hipStream_t)stream;
+  if (mzk_planar_rollout_fused(h)) {
+    HIPCHK(h, mzk_planar_rollout_policy(h, st, n_steps, params_dev, (long)param_env_stride, hidden, squash, scale, obs_dev, reward_dev, done_dev,
+                                        goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev));
+    if (h->record) {  // the last step's row
+      const size_t tot = n * (od + 2), last = (size_t)(n_steps - 1) * n;
+      hipLaunchKernelGGL(pack_record_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, h->n, h->model.obs_dim, obs_dev, reward_dev + last, done_dev + last, h->record);
+      HIPCHK(h, hipGetLastError());
+    }
+  } else {
+    if (!actions_seq_dev && !h->policy_act) HIPCHK(h, hipMalloc(&h->policy_act, n * nu * sizeof(float)));
+    for (size_t k = 0; k < (size_t)n_steps; k++) {
+      float* a = actions_seq_dev ? actions_seq_dev + k * n * nu : h->policy_act;
+      policy_act_launch(h, st, params_dev, param_env_stride, hidden, squash, scale, obs_dev, a);
+      HIPCHK(h, hipGetLastError());
+      rc = step_launches(h, st, a, obs_dev, reward_dev + k * n, done_dev + k * n, goal_idx_dev ? goal_idx_dev + k * n : NULL,
+                         info_dev ? info_dev + k * n * 4 : NULL);
       if (rc != MZ_OK) return rc;
       if (obs_seq_dev) HIPCHK(h, hipMemcpyAsync(obs_seq_dev + k * n * od, obs_dev, n * od * sizeof(float), hipMemcpyDeviceToDevice, st));
     }

@@ -59,6 +59,7 @@ struct mz_handle {
   hipEvent_t* ev;  // 2 * ntime
   long nsteps;
   float* render_qpos;  // [n][nq] scratch of mz_render without a caller's qpos (allocated on first use, freed by mz_destroy)
+  float* policy_act;   // [n][nu] actions of mz_rollout_policy's launch-by-launch loop without a caller's actions_seq (allocated on first use, freed by mz_destroy)
 };
 
 // ---- ant_kernels.hip
@@ -90,6 +91,11 @@ constexpr int MZ_ROLLOUT_CHUNK = 256;
 int mzk_planar_rollout_fused(const mz_handle* h);
 hipError_t mzk_planar_rollout(mz_handle* h, hipStream_t st, int nsteps, const float* actions, long astride, float* obs, float* reward,
                               uint8_t* done, int* goal_idx, float* info, float* obs_seq);
+// mz_rollout_policy on the same handles, with the same launch geometry and split: the policy of csrc/mz_policy.h (params: [npar], or
+// [n][npar] with pstride = npar) is evaluated between two steps on the observation row on chip; every launch writes obs at its last step
+hipError_t mzk_planar_rollout_policy(mz_handle* h, hipStream_t st, int nsteps, const float* params, long pstride, int hidden, int squash,
+                                     float action_scale, float* obs, float* reward, uint8_t* done, int* goal_idx, float* info, float* obs_seq,
+                                     float* actions_seq);
 int mzk_planar_state_width(const mz_handle* h);  // coordinates per env of the state (NV)
 int mzk_planar_record_width(const mz_handle* h); // Point: floats per env-major record; 0 for the chains (SoA)
 

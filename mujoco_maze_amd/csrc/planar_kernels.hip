@@ -4,6 +4,8 @@
 //                                per env, PlanarScratch in LDS, fp64.
 //   swimmer_step_kernel<NL,NB,G> one MazeEnv.step for the Swimmer (NL = 3) / Reacher (NL = 2): G = 4 lanes per env (lane b = link b), fp64.
 //   planar_rollout_kernel / swimmer_rollout_kernel  up to MZ_ROLLOUT_CHUNK steps of the same on a state that stays on chip (mz_rollout).
+//   planar_policy_rollout_kernel / swimmer_policy_rollout_kernel  the same with the actions of every step computed on chip by the policy
+//                                of mz_policy.h from the step's observation row (mz_rollout_policy).
 //   reset / state copy kernels; debug kernels for the parity tests (task predicates, the Point's wall detector).
 //
 // HBM layout: SoA  q_0..q_{NV-1} | v_0..v_{NV-1}, each [N] fp32; t[N], episode[N] i32.  API arrays are row-major [N, k].
@@ -23,6 +25,7 @@
 #include "swimmer_dyn.h"
 #include "mz_device.h"
 #include "mz_internal.h"
+#include "mz_policy.h"
 
 // ------------------------------------------------------------------ state in HBM
 // Chains (Swimmer / Reacher: 64 envs per workgroup): SoA qv[2 NV][n] + t[n] + episode[n] — a wave's loads of one coordinate are one line.
@@ -206,6 +209,116 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && 
       if (live) {
         if (oseq) for (int i = cx.l; i < NOBS; i += G) oseq[i] = planar_obs_elem<NB, NS>(P, s, i, 0);
         if (olast) for (int i = cx.l; i < NOBS; i += G) olast[i] = planar_obs_elem<NB, NS>(P, s, i, 0);
+      }
+      cx.sync();
+    }
+    t = rst ? 0 : t_new;
+    // the state as the next launch of planar_step_kernel would load it
+    for (int k = cx.l; k < NV; k += G) { s.q[k] = (double)(float)s.q[k]; s.v[k] = (double)(float)s.v[k]; }
+    if constexpr (BARE) { for (int k = cx.l; k < 3; k += G) s.wds[k] = rst ? 0.0 : (double)(float)s.wds[k]; }
+  }
+  cx.sync();
+  if (live) {
+    for (int k = cx.l; k < NV; k += G) {
+      st_q(S, n, NV, k, env) = (float)s.q[k];
+      st_v(S, n, NV, k, env) = (float)s.v[k];
+    }
+    if (cx.l == 0) {
+      st_t(S, NV, env) = t; st_ep(S, NV, env) = ep;
+      if (stacc) atomicOr(&status[env], stacc);
+    }
+    if constexpr (BARE) { for (int k = cx.l; k < 3; k += G) S.qv[(size_t)env * S.rec + PT_WARM_OFF + k] = (float)s.wds[k]; }
+  }
+}
+
+// planar_rollout_kernel with the actions computed on chip (mz_rollout_policy): before every step the group evaluates the policy of
+// mz_policy.h on the fp32 observation row in `o` — for the launch's first step the row of `obs` (what the previous launch, mz_step or
+// mz_reset wrote there), afterwards the row the step before computed, after an in-kernel auto-reset the new episode's t = 0 row — with
+// the unit functions policy_act_kernel (mazestep.hip) runs on the same row, so a_k and everything after it equal the loop of
+// mz_policy_act and mz_step bit for bit.  Lanes l, l + G, .. own hidden units (phid), lanes 0 and 1 the two outputs (pact); `obs` is
+// written at the launch's last step, always: the next launch of the same rollout reads its first row there.  Idle groups shadow the
+// last env through every hand-off and store nothing.  A kernel of its own beside planar_rollout_kernel, whose code stays what it was.
+template <int NB, int NS, int G>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && NS == 0 && G == 32) ? 2 : 1))) void planar_policy_rollout_kernel(
+    const PointDev* __restrict__ Pp, int n, PointState S, int nsteps, const float* __restrict__ params, long pstride, int hidden, int squash,
+    float action_scale, float* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ done, int* __restrict__ goal_idx,
+    float* __restrict__ info, float* __restrict__ obs_seq, float* __restrict__ actions_seq, int* __restrict__ status, int auto_reset,
+    uint64_t seed, uint64_t env0, float* __restrict__ final_obs) {
+  using D = PlanarDims<NB, NS>;
+  constexpr int NV = D::NV, NOBS = D::NOBS, EPW = 64 / G;
+  constexpr bool BARE = NB == 0 && NS == 0;
+  __shared__ PointDev P;
+  __shared__ PlanarScratch<NB, NS> scr[EPW];
+  __shared__ float obuf[EPW][MZ_MAX_OBS];
+  __shared__ float phid[EPW][MZ_POLICY_MAX_HIDDEN];
+  __shared__ float pact[EPW][2];
+  for (int i = threadIdx.x; i < (int)(sizeof(PointDev) / 4); i += blockDim.x) ((uint32_t*)&P)[i] = ((const uint32_t*)Pp)[i];
+  __syncthreads();
+  DevCtx<G> cx{(int)threadIdx.x % G};
+  const int grp = threadIdx.x / G;
+  int env = xcd_block(blockIdx.x, gridDim.x) * EPW + grp;
+  const bool live = env < n;
+  if (!live) env = n - 1;  // idle groups shadow the last env (no stores), as in planar_step_kernel
+  PlanarScratch<NB, NS>& s = scr[grp];
+  float* o = obuf[grp];
+  const float* par = params + (size_t)env * pstride;
+  for (int k = cx.l; k < NV; k += G) { s.q[k] = (double)st_q(S, n, NV, k, env); s.v[k] = (double)st_v(S, n, NV, k, env); }
+  if constexpr (BARE) { for (int k = cx.l; k < 3; k += G) s.wds[k] = (double)S.qv[(size_t)env * S.rec + PT_WARM_OFF + k]; }
+  for (int i = cx.l; i < NOBS; i += G) o[i] = obs[(size_t)env * NOBS + i];  // the observation the policy acts on first
+  int t = st_t(S, NV, env), stacc = 0;
+  uint32_t ep = st_ep(S, NV, env);
+  for (int step = 0; step < nsteps; step++) {
+    const size_t row = (size_t)step * n + env;
+    cx.sync();  // the row in o is complete
+    mzp_group_eval(cx.l, G, par, NOBS, 2, hidden, squash, action_scale, o, phid[grp], pact[grp], true);
+    cx.sync();
+    const float a0 = pact[grp][0], a1 = pact[grp][1];
+    if (live && cx.l == 0 && actions_seq) { actions_seq[row * 2] = a0; actions_seq[row * 2 + 1] = a1; }
+    double a[2] = {(double)a0, (double)a1};
+    cx.sync();
+    planar_env_step<NB, NS>(cx, P, s, a);
+    const int t_new = t + 1;
+    for (int i = cx.l; i < NOBS; i += G) o[i] = planar_obs_elem<NB, NS>(P, s, i, t_new);
+    cx.sync();
+    float outer; int tm, gi;
+    task_eval_dev(P.task, o, &outer, &tm, &gi, env);
+    const uint8_t d = (uint8_t)((tm ? 1 : 0) | (t_new >= P.task.max_steps ? 2 : 0));
+    const bool rst = auto_reset && d;
+    float* oseq = obs_seq ? obs_seq + row * NOBS : nullptr;
+    float* olast = step == nsteps - 1 ? obs + (size_t)env * NOBS : nullptr;
+    if (live) {
+      if (rst) {
+        if (final_obs) for (int i = cx.l; i < NOBS; i += G) final_obs[(size_t)env * NOBS + i] = o[i];
+      } else {
+        if (oseq) for (int i = cx.l; i < NOBS; i += G) oseq[i] = o[i];
+        if (olast) for (int i = cx.l; i < NOBS; i += G) olast[i] = o[i];
+      }
+      if (cx.l == 0) {
+        reward[row] = outer;
+        done[row] = d;
+        if (goal_idx) goal_idx[row] = gi;
+        if (info) { info[row * 4] = o[0]; info[row * 4 + 1] = o[1]; info[row * 4 + 2] = 0.f; info[row * 4 + 3] = 0.f; }
+        int st = s.status;
+        bool badv = false;
+        for (int k = 0; k < NV; k++) badv = badv || !(fabs(s.q[k]) < 1e10) || !(fabs(s.v[k]) < 1e10);
+        if (badv) st |= MZ_STATUS_BAD_STATE;
+        stacc |= st;
+      }
+    }
+    cx.sync();  // lane 0 has read the whole state and the terminal row
+    if (rst) {
+      ep += 1;
+      const uint64_t es = episode_seed(seed, ep);
+      for (int k = cx.l; k < NV; k += G) {
+        s.q[k] = k < 3 ? (double)reset_qpos((float)P.qpos0[k], es, env0 + (uint64_t)env, k) : 0.0;
+        s.v[k] = k < 3 ? (double)reset_qvel(P.reset_kind, NV, es, env0 + (uint64_t)env, k) : 0.0;
+      }
+      cx.sync();
+      // the new episode's first row: what the policy acts on next (every lane stores the elements it has just written itself)
+      for (int i = cx.l; i < NOBS; i += G) o[i] = planar_obs_elem<NB, NS>(P, s, i, 0);
+      if (live) {
+        if (oseq) for (int i = cx.l; i < NOBS; i += G) oseq[i] = o[i];
+        if (olast) for (int i = cx.l; i < NOBS; i += G) olast[i] = o[i];
       }
       cx.sync();
     }
@@ -450,6 +563,96 @@ __global__ __launch_bounds__(256) void swimmer_rollout_kernel(const SwimmerDev* 
   if (stacc) atomicOr(&status[env], stacc);
 }
 
+// swimmer_rollout_kernel with the actions computed on chip (mz_rollout_policy; see planar_policy_rollout_kernel).  The observation
+// row lives in registers, redundantly in every lane of the group; the group's first lane puts it into LDS (px), the G lanes split the
+// hidden units (phid) and the outputs (pact) over themselves and every lane reads the NH actions back.  Surplus groups shadow the
+// last env through every hand-off and shuffle and store nothing.
+template <int NL, int NB, int G>
+__global__ __launch_bounds__(256) void swimmer_policy_rollout_kernel(const SwimmerDev* __restrict__ Pp, int n, PointState S, int nsteps,
+                                                                      const float* __restrict__ params, long pstride, int hidden, int squash,
+                                                                      float action_scale, float* __restrict__ obs, float* __restrict__ reward,
+                                                                      uint8_t* __restrict__ done, int* __restrict__ goal_idx, float* __restrict__ info,
+                                                                      float* __restrict__ obs_seq, float* __restrict__ actions_seq, int* __restrict__ status,
+                                                                      int auto_reset, uint64_t seed, uint64_t env0, float* __restrict__ final_obs) {
+  constexpr int NR = NL + 2, NV = NR + NB, NH = NL - 1, NOMAX = 2 * NV + 4, GPB = 256 / G;
+  __shared__ float px[GPB][NOMAX];
+  __shared__ float phid[GPB][MZ_POLICY_MAX_HIDDEN];
+  __shared__ float pact[GPB][NH > 0 ? NH : 1];
+  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+  int env = gid / G;
+  const int grp = (int)threadIdx.x / G;
+  const SwimmerCtx<G> cx{(int)(threadIdx.x % G)};
+  const bool lead = cx.l == 0, live = env < n && lead;
+  if (env >= n) env = n - 1;  // surplus groups shadow the last env (no stores)
+  const SwimmerDev& P = *Pp;
+  const int nb3 = (NB && P.observe_blocks) ? 3 : 0, NO = 2 * NV + 1 + nb3;
+  float qf[NV], vf[NV], af[NH > 0 ? NH : 1], o[NOMAX];
+  double inner, inf4[4];
+  const float* par = params + (size_t)env * pstride;
+  float* x = px[grp];
+  for (int k = 0; k < NV; k++) { qf[k] = S.qv[(size_t)k * n + env]; vf[k] = S.qv[(size_t)(NV + k) * n + env]; }
+  for (int i = cx.l; i < NO; i += G) x[i] = obs[(size_t)env * NO + i];  // the observation the policy acts on first
+  int t = S.t[env], stacc = 0;
+  uint32_t ep = S.ep[env];
+  const int lane0 = (int)(threadIdx.x & 63u) - cx.l;
+  for (int step = 0; step < nsteps; step++) {
+    const size_t row = (size_t)step * n + env;
+    mzp_wave_sync();  // the row in x is complete
+    mzp_group_eval(cx.l, G, par, NO, NH, hidden, squash, action_scale, x, phid[grp], pact[grp], true);
+    mzp_wave_sync();
+    for (int k = 0; k < NH; k++) af[k] = pact[grp][k];
+    if (live && actions_seq) for (int k = 0; k < NH; k++) actions_seq[row * NH + k] = af[k];
+    int t_new;
+    stacc |= swimmer_maze_step<NL, NB>(P, qf, vf, af, t, o, &inner, inf4, &t_new, cx);
+    for (int k = 0; k < NV; k++) { qf[k] = __shfl(qf[k], lane0, 64); vf[k] = __shfl(vf[k], lane0, 64); }
+    swimmer_obs_row<NL, NB>(P, qf, vf, t_new, o);
+    float outer; int tm, gi;
+    task_eval_dev(P.task, o, &outer, &tm, &gi, env);
+    const uint8_t d = (uint8_t)((tm ? 1 : 0) | (t_new >= P.task.max_steps ? 2 : 0));
+    const bool rst = auto_reset && d;
+    float* oseq = obs_seq ? obs_seq + row * NO : nullptr;
+    float* olast = step == nsteps - 1 ? obs + (size_t)env * NO : nullptr;
+    if (live) {
+      if (rst) {
+        if (final_obs) swimmer_store_row<NL, NB>(P, qf, o, NO, NO, final_obs + (size_t)env * NO);
+      } else {
+        if (oseq) swimmer_store_row<NL, NB>(P, qf, o, NO, NO, oseq);
+        if (olast) swimmer_store_row<NL, NB>(P, qf, o, NO, NO, olast);
+      }
+      reward[row] = (float)(P.task.inner_scale * inner) + outer;
+      done[row] = d;
+      if (goal_idx) goal_idx[row] = gi;
+      if (info) for (int k = 0; k < 4; k++) info[row * 4 + k] = (float)inf4[k];
+    }
+    if (rst) {
+      ep += 1; t_new = 0;
+      const uint64_t es = episode_seed(seed, ep);
+      for (int k = 0; k < NV; k++) {
+        qf[k] = reset_qpos(k < NR ? (float)P.qpos0[k] : 0.f, es, env0 + (uint64_t)env, k);
+        vf[k] = reset_qvel(P.reset_kind, NV, es, env0 + (uint64_t)env, k);
+      }
+      swimmer_obs_row<NL, NB>(P, qf, vf, 0, o);  // the new episode's first row: what the policy acts on next
+      if (live) {
+        if (oseq) swimmer_store_row<NL, NB>(P, qf, o, NO, NO, oseq);
+        if (olast) swimmer_store_row<NL, NB>(P, qf, o, NO, NO, olast);
+      }
+    }
+    t = t_new;
+    if (lead) {
+#pragma unroll
+      for (int k = 0; k < NOMAX; k++) if (k < NO) x[k] = o[k];
+    }
+  }
+  if (!live) return;
+  for (int k = 0; k < NV; k++) {
+    S.qv[(size_t)k * n + env] = qf[k];
+    S.qv[(size_t)(NV + k) * n + env] = vf[k];
+  }
+  S.t[env] = t;
+  S.ep[env] = ep;
+  if (stacc) atomicOr(&status[env], stacc);
+}
+
 template <int NL, int NB>
 __global__ void swimmer_reset_kernel(const SwimmerDev* Pp, int n, PointState S, const uint8_t* mask, uint64_t seed, uint64_t env0, float* obs,
                                      int ostride) {
@@ -630,6 +833,59 @@ hipError_t mzk_planar_rollout(mz_handle* h, hipStream_t st, int nsteps, const fl
 #define MZ_PLANAR_ROLL(NB, NS, G)                                                                                                      \
   hipLaunchKernelGGL((planar_rollout_kernel<NB, NS, G>), dim3((h->n + 64 / G - 1) / (64 / G)), dim3(64), 0, st, h->point_dev, h->n, S, ks, act, astride, \
                      obs_dev, last, rew, dn, gi, inf, oseq, h->status, h->auto_reset, h->seed, h->env0, h->final_obs)
+      if (h->point.nball) MZ_PLANAR_ROLL(0, 1, 32);
+      else switch (h->point.nblock) {
+        case 0: {
+          const int lanes = mzk_planar_lanes(h);  // the step's rule
+          if (lanes == 8) MZ_PLANAR_ROLL(0, 0, 8);
+          else if (lanes == 16) MZ_PLANAR_ROLL(0, 0, 16);
+          else MZ_PLANAR_ROLL(0, 0, 32);
+          break;
+        }
+        case 1: MZ_PLANAR_ROLL(1, 0, 32); break;
+        case 2: MZ_PLANAR_ROLL(2, 0, 64); break;
+        default: MZ_PLANAR_ROLL(3, 0, 64); break;
+      }
+#undef MZ_PLANAR_ROLL
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// mz_rollout_policy on the fused handles: mzk_planar_rollout's launches with the policy in place of the action tensor.  Every launch
+// writes obs_dev at its last step, and the next one reads its first observation there.
+hipError_t mzk_planar_rollout_policy(mz_handle* h, hipStream_t st, int nsteps, const float* params_dev, long pstride, int hidden, int squash,
+                                     float action_scale, float* obs_dev, float* reward_dev, uint8_t* done_dev, int* goal_idx_dev, float* info_dev,
+                                     float* obs_seq_dev, float* actions_seq_dev) {
+  PointState S{h->state, h->pt_t, h->pt_ep, h->pt_rec};
+  const size_t n = (size_t)h->n, od = (size_t)h->model.obs_dim, nu = (size_t)h->model.nu;
+  for (int k0 = 0; k0 < nsteps; k0 += MZ_ROLLOUT_CHUNK) {
+    const int ks = nsteps - k0 < MZ_ROLLOUT_CHUNK ? nsteps - k0 : MZ_ROLLOUT_CHUNK;
+    float* rew = reward_dev + k0 * n;
+    uint8_t* dn = done_dev + k0 * n;
+    int* gi = goal_idx_dev ? goal_idx_dev + k0 * n : nullptr;
+    float* inf = info_dev ? info_dev + k0 * n * 4 : nullptr;
+    float* oseq = obs_seq_dev ? obs_seq_dev + k0 * n * od : nullptr;
+    float* aseq = actions_seq_dev ? actions_seq_dev + k0 * n * nu : nullptr;
+    if (h->robot == MZ_ROBOT_SWIMMER) {
+#define MZ_SW_ROLL(NL, NB)                                                                                                          \
+  hipLaunchKernelGGL((swimmer_policy_rollout_kernel<NL, NB, (NL <= 4 ? 4 : 8)>), dim3((unsigned)((n * (NL <= 4 ? 4 : 8) + sw_bd - 1) / sw_bd)), dim3(sw_bd), 0, st, \
+                     h->swimmer_dev, h->n, S, ks, params_dev, pstride, hidden, squash, action_scale, obs_dev, rew, dn, gi, inf, oseq, aseq, h->status,         \
+                     h->auto_reset, h->seed, h->env0, h->final_obs)
+      const int bd = h->swimmer.nblock ? h->swimmer.nbdof : 0;
+      const unsigned sw_bd = 64u * (unsigned)(h->wpb_set ? h->waves_per_block : 4);
+      if (h->swimmer.nlink == 3) { if (bd == 3) MZ_SW_ROLL(3, 3); else if (bd == 2) MZ_SW_ROLL(3, 2); else MZ_SW_ROLL(3, 0); }
+      else if (h->swimmer.nlink == 2) { if (bd == 3) MZ_SW_ROLL(2, 3); else if (bd == 2) MZ_SW_ROLL(2, 2); else MZ_SW_ROLL(2, 0); }
+      else if (h->swimmer.nlink == 4) MZ_SW_ROLL(4, 0);
+      else if (h->swimmer.nlink == 5) MZ_SW_ROLL(5, 0);
+      else MZ_SW_ROLL(6, 0);
+#undef MZ_SW_ROLL
+    } else {
+#define MZ_PLANAR_ROLL(NB, NS, G)                                                                                                      \
+  hipLaunchKernelGGL((planar_policy_rollout_kernel<NB, NS, G>), dim3((h->n + 64 / G - 1) / (64 / G)), dim3(64), 0, st, h->point_dev, h->n, S, ks, params_dev, \
+                     pstride, hidden, squash, action_scale, obs_dev, rew, dn, gi, inf, oseq, aseq, h->status, h->auto_reset, h->seed, h->env0, h->final_obs)
       if (h->point.nball) MZ_PLANAR_ROLL(0, 1, 32);
       else switch (h->point.nblock) {
         case 0: {

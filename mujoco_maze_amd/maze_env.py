@@ -456,6 +456,96 @@ class VecMazeEnv:
             info["final_observation"] = self._final_obs
         return self._obs, buf["reward"], buf["done"], info
 
+    def _policy_params(self, params, hidden: int):
+        """params as a contiguous float32 device tensor [npar] or [N, npar]; returns (tensor, param_env_stride)."""
+        from mujoco_maze_amd import policy
+
+        torch = self._torch
+        hidden = int(hidden)
+        if not 0 <= hidden <= policy.MAX_HIDDEN:
+            raise ValueError(f"hidden must be 0 .. {policy.MAX_HIDDEN}, got {hidden}")
+        npar = policy.param_count(self.obs_dim, self.nu, hidden)
+        p = params if torch.is_tensor(params) else torch.as_tensor(np.asarray(params, dtype=np.float32), device=self.device)
+        if p.dtype != torch.float32 or not p.is_contiguous() or p.device != self.device:
+            p = p.to(device=self.device, dtype=torch.float32).contiguous()
+        if tuple(p.shape) not in ((npar,), (self.num_envs, npar)):
+            raise ValueError(f"params must have shape {(npar,)} (one policy) or {(self.num_envs, npar)} (one per env) for obs_dim {self.obs_dim}, "
+                             f"nu {self.nu}, hidden {hidden}, got {tuple(p.shape)}")
+        return p, (npar if p.dim() == 2 else 0)
+
+    def _policy_obs(self, obs):
+        torch = self._torch
+        o = obs if torch.is_tensor(obs) else torch.as_tensor(np.asarray(obs, dtype=np.float32), device=self.device)
+        if tuple(o.shape) != (self.num_envs, self.obs_dim):
+            raise ValueError(f"obs must have shape {(self.num_envs, self.obs_dim)}, got {tuple(o.shape)}")
+        if o.dtype != torch.float32 or not o.is_contiguous() or o.device != self.device:
+            o = o.to(device=self.device, dtype=torch.float32).contiguous()
+        return o
+
+    def policy_act(self, params, obs=None, hidden: int = 0, squash: bool = False, action_scale: float = 1.0):
+        """Actions [N, nu] of a small policy evaluated on the device (mz_policy_act): affine (`hidden=0`) or one tanh hidden layer of
+        up to 64 units; `squash` makes the output action_scale * tanh(.).  params: float32 [npar] (one policy for all envs) or
+        [N, npar] (one per env), packed by `mujoco_maze_amd.policy.pack` / `pack_linear`; obs: [N, obs_dim], default the env's last
+        returned observation.  The actions are not clamped (step() clamps where the reference does).  A new tensor per call."""
+        p, stride = self._policy_params(params, hidden)
+        o = self._obs if obs is None else self._policy_obs(obs)
+        out = self._torch.empty((self.num_envs, self.nu), dtype=self._torch.float32, device=self.device)
+        rc = self._lib.mz_policy_act(self._h, _ptr(p), stride, int(hidden), 1 if squash else 0, float(action_scale), _ptr(o), _ptr(out), self._stream())
+        _capi.check(self._lib, self._h, rc, "mz_policy_act")
+        return out
+
+    def rollout_policy(self, params, steps: int, hidden: int = 0, squash: bool = False, action_scale: float = 1.0, obs=None,
+                       return_obs: bool = False, return_actions: bool = False):
+        """K = `steps` closed-loop steps in one call: a = policy(obs); obs, reward, done = step(a) — exactly what K times
+        (`policy_act`, `step`) give, state and outputs bit for bit.  params / hidden / squash / action_scale as in `policy_act`.
+        The policy acts first on the env's last returned observation (what reset / step / rollout left in the observation buffer),
+        or on `obs` [N, obs_dim] when given (copied into that buffer first).  set_state() does not refresh the buffer:
+        `reset(mask=zeros)` returns every env's current observation without resetting any.
+
+        Returns (obs, rewards [K, N], dones [K, N] uint8, info) like `rollout`; info["actions"] [K, N, nu] with `return_actions` (the
+        policy's outputs, before the env's control clamp), info["observations"] [K, N, obs_dim] with `return_obs`.
+
+        One mz_rollout_policy call — the Point, Swimmer and Reacher evaluate the policy inside their fused rollout kernels
+        (`launch_info()["rollout_fused"]`), the other handles loop policy kernel + step launches inside the call — except where the
+        host has work between steps (Python reward()/termination() overrides; per-env goals under auto-reset): there this method
+        loops `policy_act` + `step` itself."""
+        torch, n = self._torch, self.num_envs
+        p, stride = self._policy_params(params, hidden)
+        K = int(steps)
+        if not 1 <= K <= 65536:
+            raise ValueError(f"a rollout takes 1 .. 65536 steps, got {K}")
+        if obs is not None:
+            o = self._policy_obs(obs)
+            if o.data_ptr() != self._obs.data_ptr():
+                self._obs.copy_(o)
+        buf = self._rollout_buffers(K, return_obs)
+        if return_actions and "actions" not in buf:
+            buf["actions"] = torch.empty((K, n, self.nu), dtype=torch.float32, device=self.device)
+        if self._host_rewards or (self._env_goals is not None and self._auto_reset):
+            for k in range(K):
+                a = self.policy_act(p, None, hidden, squash, action_scale)
+                o, rew, done, inf = self.step(a)
+                buf["reward"][k], buf["done"][k], buf["goal"][k], buf["info"][k] = rew, done, inf["goal_index"], self._info
+                if return_obs:
+                    buf["obs_seq"][k] = o
+                if return_actions:
+                    buf["actions"][k] = a
+        else:
+            rc = self._lib.mz_rollout_policy(self._h, K, _ptr(p), stride, int(hidden), 1 if squash else 0, float(action_scale), _ptr(self._obs),
+                                             _ptr(buf["reward"]), _ptr(buf["done"]), _ptr(buf["goal"]), _ptr(buf["info"]),
+                                             _ptr(buf["obs_seq"]) if return_obs else None, _ptr(buf["actions"]) if return_actions else None,
+                                             self._stream())
+            _capi.check(self._lib, self._h, rc, "mz_rollout_policy")
+        info = {"position": buf["info"][:, :, :2], "reward_forward": buf["info"][:, :, 2], "reward_ctrl": buf["info"][:, :, 3],
+                "goal_index": buf["goal"]}
+        if return_obs:
+            info["observations"] = buf["obs_seq"]
+        if return_actions:
+            info["actions"] = buf["actions"]
+        if self._auto_reset:
+            info["final_observation"] = self._final_obs
+        return self._obs, buf["reward"], buf["done"], info
+
     def _rollout_buffers(self, K: int, with_obs: bool) -> dict:
         """Output tensors of rollout(), allocated per K and kept."""
         torch, n, dev = self._torch, self.num_envs, self.device

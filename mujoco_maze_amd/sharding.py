@@ -101,7 +101,10 @@ class RecordGatherer:
 
 
 class ShardedVecMazeEnv:
-    """One rank's shard of a node-wide batch: a local `VecMazeEnv` + the record all-gather."""
+    """One rank's shard of a node-wide batch: a local `VecMazeEnv` + the record all-gather.
+
+    Device-side policies (`VecMazeEnv.policy_act` / `rollout_policy`) are out of scope here: a closed-loop rollout has no per-step
+    record to gather.  A rank may call them on its local `self.env`."""
 
     def __init__(self, env_id: str, envs_per_rank: int, device=None, gather: bool = True, group=None, always_collective: bool = False,
                  **kwargs):

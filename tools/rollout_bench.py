@@ -3,6 +3,9 @@ PointUMaze-v0, SwimmerUMaze-v0, ReacherUMaze-v0, PointPush-v0 (fused kernels) an
 mz_rollout).  Both legs run in one process, alternating, three repeats each after a warm-up of both; a leg repeats its window until
 at least `--seconds` of work has passed, with a device synchronise around the host clock.  Whole-call wall clock, inputs resident.
     python tools/rollout_bench.py [--envs N] [--steps K] [--seconds S] [--repeats R] [--ids a,b,..] [--out FILE]
+With --policy H the three closed-loop ways to run the same K steps of one shared policy (H = 0: affine; else one tanh hidden layer of H
+units) are timed instead, same protocol: K x (torch policy + env.step), K x (env.policy_act + env.step), one env.rollout_policy.
+    python tools/rollout_bench.py --policy 32 [--ids PointUMaze-v0,SwimmerUMaze-v0,AntUMaze-v0]
 Kernel durations come from a run of their own:  rocprofv3 --kernel-trace --stats -d <dir> -- python tools/rollout_bench.py --seconds 0.2"""
 import argparse
 import json
@@ -63,6 +66,76 @@ def bench(env_id, n, K, seconds, repeats):
             "step_env_steps_per_s": res["step"], "rollout_env_steps_per_s": res["rollout"]}
 
 
+def bench_policy(env_id, n, K, H, seconds, repeats):
+    """K closed-loop steps of one shared policy, three ways: torch policy + step, policy_act + step, one rollout_policy."""
+    from mujoco_maze_amd import policy
+
+    dev = torch.device("cuda", 0)
+    env = mm.make(env_id, num_envs=n, auto_reset=True, device=dev, force_vec=True)
+    env.reset(seed=20260928)
+    g = torch.Generator(device=dev).manual_seed(1234)
+
+    def lin(out, fan_in):
+        k = fan_in ** -0.5
+        return (2 * torch.rand((out, fan_in), device=dev, generator=g) - 1) * k, (2 * torch.rand(out, device=dev, generator=g) - 1) * k
+
+    if H:
+        (W1, b1), (W2, b2) = lin(H, env.obs_dim), lin(env.nu, H)
+        params = torch.as_tensor(policy.pack(W1, b1, W2, b2), device=dev)
+        W1t, W2t = W1.T.contiguous(), W2.T.contiguous()
+        torch_policy = lambda obs: torch.addmm(b2, torch.tanh(torch.addmm(b1, obs, W1t)), W2t)
+    else:
+        W, b = lin(env.nu, env.obs_dim)
+        params = torch.as_tensor(policy.pack_linear(W, b), device=dev)
+        Wt = W.T.contiguous()
+        torch_policy = lambda obs: torch.addmm(b, obs, Wt)
+    state = {"obs": env._obs}
+
+    def torch_step():
+        for k in range(K):
+            state["obs"] = env.step(torch_policy(state["obs"]))[0]
+
+    def act_step():
+        for k in range(K):
+            env.step(env.policy_act(params, hidden=H))
+
+    def fused():
+        env.rollout_policy(params, K, hidden=H)
+
+    legs = (("torch_step", torch_step), ("act_step", act_step), ("rollout_policy", fused))
+    for _ in range(4):
+        for _, fn in legs:
+            fn()
+    res = {name: [] for name, _ in legs}
+    for _ in range(repeats):
+        for name, fn in legs:
+            w, dt = leg(fn, 4, seconds, dev)
+            res[name].append(n * K * w / dt)
+    bad = int((env.status() & 3).ne(0).sum())
+    fused_flag = env.launch_info()["rollout_fused"]
+    env.close()
+    return {"env": env_id, "envs": n, "steps_per_window": K, "hidden": H, "fused": fused_flag, "flagged_envs": bad,
+            **{name + "_env_steps_per_s": v for name, v in res.items()}}
+
+
+def main_policy(args):
+    out = []
+    med = lambda v: sorted(v)[len(v) // 2]
+    print(f"closed loop, one shared policy (hidden {args.policy}), {args.steps} steps per window, {args.envs} envs, auto-reset, >= {args.seconds} s per leg, "
+          f"{args.repeats} alternating repeats; M env-steps/s, median (max - min)")
+    print("%-18s %5s %24s %24s %24s" % ("env", "fused", "torch policy + step", "policy_act + step", "rollout_policy"))
+    for env_id in args.ids.split(","):
+        r = bench_policy(env_id, args.envs, args.steps, args.policy, args.seconds, args.repeats)
+        out.append(r)
+        cell = lambda v: "%10.3f (%6.3f)" % (med(v) / 1e6, (max(v) - min(v)) / 1e6)
+        print("%-18s %5d %24s %24s %24s" % (env_id, r["fused"], cell(r["torch_step_env_steps_per_s"]), cell(r["act_step_env_steps_per_s"]),
+                                            cell(r["rollout_policy_env_steps_per_s"])), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            for r in out:
+                f.write(json.dumps(r) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=4096)
@@ -71,8 +144,11 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--ids", type=str, default=",".join(IDS))
     ap.add_argument("--out", type=str, default=None, help="also write the rows as JSON lines")
+    ap.add_argument("--policy", type=int, default=None, metavar="H", help="closed-loop mode: hidden units of the policy (0 = affine)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "rollout_bench.py measures on the GPU only"
+    if args.policy is not None:
+        return main_policy(args)
     out = []
     print(f"{args.steps} x env.step against one env.rollout, {args.envs} envs, auto-reset, >= {args.seconds} s per leg, {args.repeats} alternating repeats")
     print("%-18s %5s %14s %10s %14s %10s %7s" % ("env", "fused", "step M/s", "spread", "rollout M/s", "spread", "ratio"))
