@@ -198,7 +198,14 @@ MZ_HD void mz_sincosf(float x, float* sn, float* cs) {
   const float z = y * y;
   const float ps = y + y * z * (-1.6666654611e-1f + z * (8.3321608736e-3f + z * -1.9515295891e-4f));
   const float pc = 1.0f - 0.5f * z + z * z * (4.166664568298827e-2f + z * (-1.388731625493765e-3f + z * 2.443315711809948e-5f));
+#if !defined(__HIP_DEVICE_COMPILE__)
+  // (host: the conversion of a NaN / huge k — a diverged angle — is undefined in C++; such an angle has no meaningful quadrant)
+  const int q = fabsf(k) < 2147483648.f ? (int)k & 3 : 0;
+#else
+  // device form kept as it is (the benchmark kernel's instruction stream): the device's conversion is defined for every input — it
+  // saturates, NaN gives 0 — and `& 3` masks whatever it returns to a valid quadrant; q is no loop bound and no index
   const int q = (int)k & 3;
+#endif
   const float s0 = (q & 1) ? pc : ps, c0 = (q & 1) ? ps : pc;
   *sn = (q & 2) ? -s0 : s0;
   *cs = ((q + 1) & 2) ? -c0 : c0;
@@ -264,7 +271,7 @@ MZ_HD void kin_item(const AntDev& K, AntScratchT<NB>& s, int l) {
       const MazeDev& z = K.maze;
       const float reach = 1.25f;
       float x = s.qpos[0] + z.tx, y = s.qpos[1] + z.ty, inv = 1.0f / z.scale;
-      int jc = (int)floorf(x * inv + 0.5f), ic = (int)floorf(y * inv + 0.5f);
+      int jc = mz_cell(x * inv + 0.5f), ic = mz_cell(y * inv + 0.5f);
       float fx = x - jc * z.scale, fy = y - ic * z.scale;  // offset from the centre of the torso's own cell
       bool inside = ic >= 0 && ic < z.rows && jc >= 0 && jc < z.cols;
       // torso inside a wall cell / off the grid: keep testing; cells smaller than the reach: more than one ring could matter
@@ -995,8 +1002,8 @@ MZ_HD void geom_contacts(const AntDev& K, const AntScratchCoreT<NB>& s, int e, E
       }
     float reach = sqrtf(hb[0] * hb[0] + hb[1] * hb[1] + hb[2] * hb[2]) + K.wall.margin;
     float gx = s.qpos[0] + bc[0], gy = s.qpos[1] + bc[1];
-    int j0 = (int)floorf((gx - reach + z.tx) * inv + 0.5f), j1 = (int)floorf((gx + reach + z.tx) * inv + 0.5f);
-    int i0 = (int)floorf((gy - reach + z.ty) * inv + 0.5f), i1 = (int)floorf((gy + reach + z.ty) * inv + 0.5f);
+    int j0 = mz_cell((gx - reach + z.tx) * inv + 0.5f), j1 = mz_cell((gx + reach + z.tx) * inv + 0.5f);
+    int i0 = mz_cell((gy - reach + z.ty) * inv + 0.5f), i1 = mz_cell((gy + reach + z.ty) * inv + 0.5f);
     // parts 1..9: cell (i0 + (sub - 1) / 3, j0 + (sub - 1) % 3) — a block is one cell wide (or less), its bounding square with the
     // margin spans at most three cells per axis (ant_dev_from_model checks the sizes); row-major like the loop it replaces
     const int ci_ = i0 + (sub - 1) / 3, cj_ = j0 + (sub - 1) % 3;
@@ -1101,8 +1108,8 @@ MZ_HD void geom_contacts(const AntDev& K, const AntScratchCoreT<NB>& s, int e, E
       const float reach = rb + K.ball_wall.margin;
       const float gx = s.qpos[0] + s.bc[0], gy = s.qpos[1] + s.bc[1], gz = s.cz + s.bc[2];
       if (gz - reach > z.center_z + z.half_z) return;
-      const int j0 = (int)floorf((gx - reach + z.tx) * inv + 0.5f), j1 = (int)floorf((gx + reach + z.tx) * inv + 0.5f);
-      const int i0 = (int)floorf((gy - reach + z.ty) * inv + 0.5f), i1 = (int)floorf((gy + reach + z.ty) * inv + 0.5f);
+      const int j0 = mz_cell((gx - reach + z.tx) * inv + 0.5f), j1 = mz_cell((gx + reach + z.tx) * inv + 0.5f);
+      const int i0 = mz_cell((gy - reach + z.ty) * inv + 0.5f), i1 = mz_cell((gy + reach + z.ty) * inv + 0.5f);
       const float zero[3] = {0.f, 0.f, 0.f};
       for (int i = i0; i <= i1; i++)
         for (int j = j0; j <= j1; j++) {
@@ -1173,8 +1180,23 @@ MZ_HD void geom_contacts(const AntDev& K, const AntScratchCoreT<NB>& s, int e, E
   float reach = r + hl + K.wall.margin;
   float gx = s.qpos[0] + ctr[0], gy = s.qpos[1] + ctr[1], gz = s.cz + ctr[2];
   if (gz - reach > z.center_z + z.half_z) return;
-  int j0 = (int)floorf((gx - reach + z.tx) * inv + 0.5f), j1 = (int)floorf((gx + reach + z.tx) * inv + 0.5f);
-  int i0 = (int)floorf((gy - reach + z.ty) * inv + 0.5f), i1 = (int)floorf((gy + reach + z.ty) * inv + 0.5f);
+  int j0, j1, i0, i1;
+#if defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (NB == 0) {
+    // device form kept as it is for the plain ant (this enumerator is the staging-overflow path of the benchmark kernel, whose
+    // instruction stream stays): the device's conversion is defined for every input — it saturates, NaN gives 0.  A coordinate
+    // large enough to saturate is far beyond the point where fp32 still resolves `reach`, so i0 == i1 (j0 == j1) there, and the
+    // 2 x 2 test below leaves: maze_row_lds checks its index, a saturated row reads as empty.  Every registered maze has cells wider
+    // than a geom's bounding square (j1 - j0 <= 1, i1 - i0 <= 1 always), so the cell loop is not reached with a saturated bound;
+    // a maze with cells narrower than 2 reach would need mz_cell here as well.
+    j0 = (int)floorf((gx - reach + z.tx) * inv + 0.5f); j1 = (int)floorf((gx + reach + z.tx) * inv + 0.5f);
+    i0 = (int)floorf((gy - reach + z.ty) * inv + 0.5f); i1 = (int)floorf((gy + reach + z.ty) * inv + 0.5f);
+  } else
+#endif
+  {
+    j0 = mz_cell((gx - reach + z.tx) * inv + 0.5f); j1 = mz_cell((gx + reach + z.tx) * inv + 0.5f);
+    i0 = mz_cell((gy - reach + z.ty) * inv + 0.5f); i1 = mz_cell((gy + reach + z.ty) * inv + 0.5f);
+  }
   if constexpr (NB == 0) {
     // Most geoms of an ant that stands near a wall are still clear of it: both grid rows under the bounding square are read
     // at once (one LDS wait instead of one per cell) and the geom leaves when none of its <= 2 x 2 cells is a wall.

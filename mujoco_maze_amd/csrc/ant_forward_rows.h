@@ -110,8 +110,20 @@ __device__ __forceinline__ void robot_geom_contacts(const AntDev& K, const AntU&
   const bool elevated = NB > 0 && z.elevated;
   const float gx = x0 + ctr[0], gy = y0 + ctr[1], gz = cz + ctr[2];
   if (gz - reach > z.center_z + z.half_z) return;
+#if !defined(__HIP_DEVICE_COMPILE__)
+  const int j0 = mz_cell((gx - reach + z.tx) * inv + 0.5f), j1 = mz_cell((gx + reach + z.tx) * inv + 0.5f);
+  const int i0 = mz_cell((gy - reach + z.ty) * inv + 0.5f), i1 = mz_cell((gy + reach + z.ty) * inv + 0.5f);
+#else
+  // device form kept as it is (the benchmark kernel's instruction stream) instead of mz_cell: the device's conversion is defined for
+  // every input (it saturates, NaN gives 0), and nothing below depends on the range of what it returns — the cell loop is bounded
+  // by itself (i < i0 + 8, j < j0 + 4: at most 32 passes), the 2 x 2 path has none, `candidate` and the 2 x 2 path test every cell
+  // against the grid (iin / jin), maze_row_lds / plat_row_lds check the row index they read, and shifts take j & 31 or a j in the
+  // grid.  (No integer overflow either: i1 >= i0 always — both come from coordinates 2 reach apart, monotonically; both NaN give
+  // 0 —, and an i0 within 8 of INT_MAX is the saturated one, which forces i1 == i0 and so the 2 x 2 path: fp32 cells beyond 2^24
+  // are multiples of their ulp.)
   const int j0 = (int)floorf((gx - reach + z.tx) * inv + 0.5f), j1 = (int)floorf((gx + reach + z.tx) * inv + 0.5f);
   const int i0 = (int)floorf((gy - reach + z.ty) * inv + 0.5f), i1 = (int)floorf((gy + reach + z.ty) * inv + 0.5f);
+#endif
   const float lim2 = (r + wall_margin) * (r + wall_margin) * 1.0001f;
   // can the box of cell (i, j) — layer 1: the wall, layer 0: the platform of an elevated maze — give a contact at all?  In the grid
   // and present; the geom's z extent meets the box's; and the geom's axis segment — its bounding box, axis by axis — comes within

@@ -943,8 +943,8 @@ MZ_HD void gen_collide_item(const GenDev& K, GenScratch& s, int it) {
   const double sc = m.maze_scale, reach = m.geom_rbound[g] + margin;
   if (gp[2] - reach > m.wall_center_z + m.wall_half_z) return;
   if (!m.elevated && gp[2] + reach < m.wall_center_z - m.wall_half_z) return;
-  const int j0 = (int)floor((gp[0] - reach + m.torso_x) / sc + 0.5), j1 = (int)floor((gp[0] + reach + m.torso_x) / sc + 0.5);
-  const int i0 = (int)floor((gp[1] - reach + m.torso_y) / sc + 0.5), i1 = (int)floor((gp[1] + reach + m.torso_y) / sc + 0.5);
+  const int j0 = mz_cell((gp[0] - reach + m.torso_x) / sc + 0.5), j1 = mz_cell((gp[0] + reach + m.torso_x) / sc + 0.5);
+  const int i0 = mz_cell((gp[1] - reach + m.torso_y) / sc + 0.5), i1 = mz_cell((gp[1] + reach + m.torso_y) / sc + 0.5);
   const double bs[3] = {m.wall_half_xy, m.wall_half_xy, m.wall_half_z};
   for (int i = i0; i <= i1; i++)
     for (int j = j0; j <= j1; j++) {
@@ -1613,7 +1613,7 @@ MZ_HD void gen_env_step(const C& cx, const GenDev& K, GenScratch& s, const float
       s.qpos[0] += cos(th) * (double)action[0];
       s.qpos[1] += sin(th) * (double)action[0];
     }
-    MZ_FOR(i, m.nv) s.qvel[i] = fmin(fmax(s.qvel[i], -m.velocity_limit), m.velocity_limit);
+    MZ_FOR(i, m.nv) s.qvel[i] = pt_clip(s.qvel[i], m.velocity_limit);
   } else {
     MZ_FOR(one, 1)
       for (int u = 0; u < m.nu; u++) {

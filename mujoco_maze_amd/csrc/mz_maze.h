@@ -35,6 +35,24 @@ static inline void maze_dev_from_model(MazeDev* z, const mz_model* m) {
   z->half_xy = (float)m->wall_half_xy; z->half_z = (float)m->wall_half_z; z->center_z = (float)m->wall_center_z;
 }
 
+// Cell index of a floating cell coordinate (world coordinate / scale + 0.5, from an env's STATE): floor, clamped in floating
+// point to [-2, MZ_MAX_GRID + 1] before the conversion, NaN -> -2.  A diverged state (NaN, Inf, 1e30) must not reach the
+// float -> int conversion: in C++ a value outside int's range is undefined, x86 returns INT_MIN, the device's conversion
+// saturates (Inf -> INT_MAX, NaN -> 0) — and a cell loop `for (i = i0; i <= i1; i++)` with i1 == INT_MAX never ends.  With
+// this every cell range is at most MZ_MAX_GRID + 4 long on any platform.  Cells outside the grid are skipped by every caller
+// (two cells of room on each side: the 3 x 3 neighbourhoods of a cell just outside the grid still reach into it), so for a
+// state in range nothing changes by a bit.
+MZ_HD int mz_cell(double f) {
+  f = floor(f);
+  if (!(f >= -2.0)) return -2;
+  return f > (double)(MZ_MAX_GRID + 1) ? MZ_MAX_GRID + 1 : (int)f;
+}
+MZ_HD int mz_cell(float f) {
+  f = floorf(f);
+  if (!(f >= -2.0f)) return -2;
+  return f > (float)(MZ_MAX_GRID + 1) ? MZ_MAX_GRID + 1 : (int)f;
+}
+
 // Row bitmask of the cell grid for a per-lane row index.  The grid lives in the kernel-argument block
 // (scalar registers); a select chain keeps it there — indexing the array with a vector index would make the
 // compiler spill it to scratch memory.

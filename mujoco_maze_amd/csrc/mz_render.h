@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include "../../include/mazestep.h"
+#include "mz_maze.h"  // mz_cell
 
 #if defined(__HIPCC__)
 #define MZR_HD __host__ __device__ inline
@@ -309,7 +310,7 @@ MZR_HD bool mzr_meets(const RenderPrim& P, const RenderCanvas& c, int c0, int c1
 // neighbours), or -4 far outside the maze / for NaN
 MZR_HD int mzr_cell_near(double v, double t, double sc, int n) {
   const double f = (v + t) / sc + 0.5;
-  return f > -2.0 && f < (double)n + 2.0 ? (int)floor(f) : -4;
+  return f > -2.0 && f < (double)n + 2.0 ? mz_cell(f) : -4;
 }
 
 // BLOCK / CHASM cells: the last cell in row-major order whose inclusive square (render.py's rect) covers (X, Y), or FLOOR.

@@ -410,7 +410,7 @@ MZP_HD void pl_box_box_aligned(const double* c1, const double* h1, const double*
 
 // wall cell (di, dj) of the 3 x 3 neighbourhood of the cell under (x, y): centre in wc; false when not a BLOCK cell
 MZP_HD bool pl_wall_cell(const MazeDev& z, double x, double y, int k9, double* wc) {
-  int jc = (int)floor((x + z.tx) / z.scale + 0.5), ic = (int)floor((y + z.ty) / z.scale + 0.5);
+  int jc = mz_cell((x + z.tx) / z.scale + 0.5), ic = mz_cell((y + z.ty) / z.scale + 0.5);
   int i = ic + k9 / 3 - 1, j = jc + k9 % 3 - 1;
   if (i < 0 || j < 0 || i >= z.rows || j >= z.cols) return false;
   if (!((maze_row(z, i) >> j) & 1u)) return false;
@@ -420,7 +420,7 @@ MZP_HD bool pl_wall_cell(const MazeDev& z, double x, double y, int k9, double* w
 
 // platform cell of an elevated maze in the 3 x 3 neighbourhood of the cell under (x, y): every cell that is not a chasm
 MZP_HD bool pl_platform_cell(const MazeDev& z, double x, double y, int k9, double* wc) {
-  int jc = (int)floor((x + z.tx) / z.scale + 0.5), ic = (int)floor((y + z.ty) / z.scale + 0.5);
+  int jc = mz_cell((x + z.tx) / z.scale + 0.5), ic = mz_cell((y + z.ty) / z.scale + 0.5);
   int i = ic + k9 / 3 - 1, j = jc + k9 % 3 - 1;
   if (!z.elevated || i < 0 || j < 0 || i >= z.rows || j >= z.cols) return false;
   uint32_t row = 0u;
@@ -908,7 +908,7 @@ MZP_HD void planar_env_step(const C& cx, const PointDev& P, PlanarScratch<NB, NS
     s.q[1] += sin(th) * action[0];
     s.status = 0;
   }
-  MZ_FOR(i, NV) s.v[i] = fmin(fmax(s.v[i], -P.vel_limit), P.vel_limit);  // the clip covers the whole qvel (point.py:54-55)
+  MZ_FOR(i, NV) s.v[i] = pt_clip(s.v[i], P.vel_limit);  // the clip covers the whole qvel (point.py:54-55)
   cx.sync();
   for (int f = 0; f < P.frame_skip; f++) {  // mj_step, RK4 (point.xml:3)
     const double h = P.h;

@@ -71,7 +71,7 @@ struct alignas(16) PlanarScratch<0, 0> {
 
 // BLOCK cell (di, dj) of the 3 x 3 neighbourhood of the cell under (x, y): its centre, or false
 MZP_HD bool pb_wall_cell(const MazeDev& z, double x, double y, int k9, double* wcx, double* wcy) {
-  const int jc = (int)floor((x + z.tx) / z.scale + 0.5), ic = (int)floor((y + z.ty) / z.scale + 0.5);
+  const int jc = mz_cell((x + z.tx) / z.scale + 0.5), ic = mz_cell((y + z.ty) / z.scale + 0.5);
   const int i = ic + k9 / 3 - 1, j = jc + k9 % 3 - 1;
   if (i < 0 || j < 0 || i >= z.rows || j >= z.cols) return false;
   if (!((z.rowmask[i] >> j) & 1u)) return false;
@@ -442,7 +442,7 @@ MZP_HD void point_env_step_bare(const C& cx, const PointDev& P, PlanarScratch<0,
     pt_sincos(th, &sn, &cs);
     q[2] = th; q[0] += cs * action[0]; q[1] += sn * action[0];
 #pragma unroll
-    for (int i = 0; i < 3; i++) v[i] = fmin(fmax(v[i], -P.vel_limit), P.vel_limit);
+    for (int i = 0; i < 3; i++) v[i] = pt_clip(v[i], P.vel_limit);
   }
   for (int f = 0; f < P.frame_skip; f++) {  // mj_step, RK4 (point.xml:3)
     const double h = P.h;

@@ -178,6 +178,11 @@ static inline int point_dev_from_model(PointDev* p, const mz_model* m, char* err
 #define MZP_HD inline
 #endif
 
+// The Point's velocity clip (point.py:54-56, np.clip) — NaN stays NaN, as in numpy and in the oracle: fmin(fmax(v, -lim), lim) would
+// turn a NaN velocity into -lim, a diverged env into one that drives on at full speed with MZ_STATUS_BAD_STATE never set
+// (tests/test_gpu_env_isolation.py).  For every other value the same bits as the fmin / fmax form.
+MZP_HD double pt_clip(double v, double lim) { return v < -lim ? -lim : (v > lim ? lim : v); }
+
 // ---- the manual wall detector: float64 arithmetic of the reference, operation for operation.
 // The reference computes with Python complex numbers and floats (maze_env_utils.py:84-123): every product, sum and
 // quotient is a separately rounded IEEE double operation and abs(complex) is C hypot().  The functions below keep that:
@@ -285,8 +290,8 @@ MZP_HD int point_bounce(const PD& P, const double* old_xy, const double* new_xy,
 MZP_HD bool point_near_wall(const PointDev& P, double x, double y) {
   const MazeDev& z = P.maze;
   double inv = 1.0 / z.scale, reach = P.reach;
-  int j0 = (int)floor((x - reach + z.tx) * inv + 0.5), j1 = (int)floor((x + reach + z.tx) * inv + 0.5);
-  int i0 = (int)floor((y - reach + z.ty) * inv + 0.5), i1 = (int)floor((y + reach + z.ty) * inv + 0.5);
+  int j0 = mz_cell((x - reach + z.tx) * inv + 0.5), j1 = mz_cell((x + reach + z.tx) * inv + 0.5);
+  int i0 = mz_cell((y - reach + z.ty) * inv + 0.5), i1 = mz_cell((y + reach + z.ty) * inv + 0.5);
   for (int i = i0; i <= i1; i++)
     for (int j = j0; j <= j1; j++) {
       if (i < 0 || j < 0 || i >= z.rows || j >= z.cols) continue;
@@ -305,7 +310,7 @@ MZP_HD bool point_near_wall(const PointDev& P, double x, double y) {
 MZP_HD bool point_near_wall3(const PointDev& P, double x, double y, double reach) {
   const MazeDev& z = P.maze;
   const double s = z.scale, inv = 1.0 / s;
-  const int jc = (int)floor((x + z.tx) * inv + 0.5), ic = (int)floor((y + z.ty) * inv + 0.5);
+  const int jc = mz_cell((x + z.tx) * inv + 0.5), ic = mz_cell((y + z.ty) * inv + 0.5);
   double dx2[3], dy2[3];
   unsigned bits[3];
 #pragma unroll

@@ -891,6 +891,15 @@ static void collide_plane(const mz_model* m, mzo_data* d, int gp, int g) {
   }
 }
 
+/* cell index of a floating cell coordinate taken from the state: floor, clamped in floating point to [-2, MZ_MAX_GRID + 1] before the
+ * conversion, NaN -> -2 (the oracle's own copy of csrc/mz_maze.h mz_cell: a diverged state must not reach a float -> int conversion,
+ * undefined outside int's range; cells outside the grid are skipped below, so nothing changes for a state in range) */
+static int cell_index(double f) {
+  f = floor(f);
+  if (!(f >= -2.0)) return -2;
+  return f > (double)(MZ_MAX_GRID + 1) ? MZ_MAX_GRID + 1 : (int)f;
+}
+
 static void collide_walls(const mz_model* m, mzo_data* d, int g) {
   /* implicit maze boxes (world body): only cells overlapping the geom's bounding square can touch */
   if (!((m->geom_contype[g] & m->wall_conaffinity) || (m->wall_contype & m->geom_conaffinity[g]))) return;
@@ -902,8 +911,8 @@ static void collide_walls(const mz_model* m, mzo_data* d, int g) {
   const double* gp = d->geom_xpos[g];
   if (gp[2] - reach > m->wall_center_z + m->wall_half_z) return;
   if (!m->elevated && gp[2] + reach < m->wall_center_z - m->wall_half_z) return;
-  int j0 = (int)floor((gp[0] - reach + m->torso_x) / s + 0.5), j1 = (int)floor((gp[0] + reach + m->torso_x) / s + 0.5);
-  int i0 = (int)floor((gp[1] - reach + m->torso_y) / s + 0.5), i1 = (int)floor((gp[1] + reach + m->torso_y) / s + 0.5);
+  int j0 = cell_index((gp[0] - reach + m->torso_x) / s + 0.5), j1 = cell_index((gp[0] + reach + m->torso_x) / s + 0.5);
+  int i0 = cell_index((gp[1] - reach + m->torso_y) / s + 0.5), i1 = cell_index((gp[1] + reach + m->torso_y) / s + 0.5);
   static const double ident[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
   double bsize[3] = {m->wall_half_xy, m->wall_half_xy, m->wall_half_z};
   for (int i = i0; i <= i1; i++)
