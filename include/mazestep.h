@@ -409,6 +409,42 @@ int32_t mz_rollout_policy(mz_handle* h, int32_t n_steps, const float* params_dev
                           int32_t squash, double action_scale, float* obs_dev, float* reward_dev, uint8_t* done_dev,
                           int32_t* goal_idx_dev, float* info_dev, float* obs_seq_dev, float* actions_seq_dev, void* stream);
 
+/* Stochastic device-side policies (on-policy data collection, exploration with action noise): a diagonal Gaussian around the
+ * policy above, sampled where the observation sits, with the log-probability of what was drawn.
+ *
+ * Parameters: the packed vector above followed by log_std[nu] — npar_s = npar + nu fp32 numbers; params_dev [npar_s]
+ * (param_env_stride == 0) or [N, npar_s] (param_env_stride == npar_s); any other stride is MZ_ERR_ARG.
+ * Noise: eps(noise_seed, noise_step, slot, u) is a pure function of four integers — slot is the GLOBAL env slot ("env_index_offset"
+ * + i), u the action index — and of nothing else: not of N, nu, hidden, lanes per env, the engine or the kernel that computes it,
+ * so a shard of a batch draws what the whole batch would.  In uint64 arithmetic with wrap-around (csrc/mz_rng.h, csrc/mz_policy.h):
+ *     key = mix64(noise_seed ^ (0xA24BAED4963EE407 * (noise_step + 1)))
+ *     x1 = rng_u32(key, slot, 2u), x2 = rng_u32(key, slot, 2u + 1)                         (the words of the reset stream's generator)
+ *     u1 = ((x1 >> 8) + 1) * 2^-24, u2 = (x2 >> 8) * 2^-24, eps = sqrtf(-2 logf(u1)) * cosf(6.2831855f * u2)       |eps| <= 5.77
+ * Sample: with m_u the pre-squash sum of output unit u, z_u = m_u + expf(log_std[u]) * eps_u (product and sum rounded separately);
+ * the action is z_u (squash == 0) or (float)action_scale * tanhf(z_u) (squash == 1).
+ * Log-prob: logp = sum_u (-0.5 * eps_u^2 - log_std[u] - 0.9189385), the density of z under the Gaussian, in fp32, u in order, every
+ * operation rounded separately.  With squash it is the PRE-tanh density: the caller applies the tanh correction from the returned
+ * actions.  NaN in log_std reaches that env's action and logp only.
+ *
+ * mz_policy_sample: one draw for the N rows of obs_dev [N, obs_dim] -> actions_dev [N, nu], logp_dev [N] (nullable).
+ *
+ * mz_rollout_policy_sample: n_steps times a ~ policy(obs); step(a); step k draws with noise_step + k.  The call leaves the handle
+ * and every output exactly as this loop on the same stream would:
+ *     for k in 0 .. n_steps - 1:
+ *         mz_policy_sample(noise_seed, noise_step + k, obs_dev -> a_k, row k of logp_seq_dev)
+ *         mz_step(a_k -> obs_dev, row k of reward_dev / done_dev / goal_idx_dev / info_dev)
+ * Arrays as in mz_rollout_policy; actions_seq_dev [n_steps, N, nu] (nullable) gets the sampled actions, logp_seq_dev [n_steps, N]
+ * (nullable) their log-probs.  Handles with "rollout_fused" = 1 sample inside the fused rollout kernels (launches of at most 256
+ * steps; the next launch continues at noise_step + the steps done so far), every other handle runs the loop above inside the call.
+ * Both return MZ_OK, MZ_ERR_ARG (as the two entries above, with npar_s for npar) or MZ_ERR_HIP. */
+int32_t mz_policy_sample(mz_handle* h, const float* params_dev, int64_t param_env_stride, int32_t hidden, int32_t squash,
+                         double action_scale, uint64_t noise_seed, uint64_t noise_step, const float* obs_dev, float* actions_dev,
+                         float* logp_dev, void* stream);
+int32_t mz_rollout_policy_sample(mz_handle* h, int32_t n_steps, const float* params_dev, int64_t param_env_stride, int32_t hidden,
+                                 int32_t squash, double action_scale, uint64_t noise_seed, uint64_t noise_step, float* obs_dev,
+                                 float* reward_dev, uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev, float* obs_seq_dev,
+                                 float* actions_seq_dev, float* logp_seq_dev, void* stream);
+
 /* Per-env status words accumulated since the last call (then cleared). [N] i32. */
 int32_t mz_get_status(mz_handle* h, int32_t* status_dev, void* stream);
 

@@ -22,7 +22,7 @@ SYMBOLS = [
     "mz_nv", "mz_nu", "mz_set_option", "mz_reset", "mz_set_state", "mz_get_state", "mz_step", "mz_get_status",
     "mz_debug_forward", "mz_last_kernel_ms", "mz_read_phase_cycles", "mz_bind_final_obs", "mz_debug_task_eval", "mz_debug_detect", "mz_read_wave_cycles", "mz_bind_record",
     "mz_set_goals", "mz_read_wave_phase_cycles", "mz_get_info", "mz_bind_env_goals", "mz_render", "mz_rollout",
-    "mz_policy_act", "mz_rollout_policy",
+    "mz_policy_act", "mz_rollout_policy", "mz_policy_sample", "mz_rollout_policy_sample",
 ]
 
 _lib = None
@@ -82,6 +82,10 @@ def load():
     lib.mz_policy_act.argtypes = [vp, vp, C.c_int64, i32, i32, C.c_double, vp, vp, vp]
     lib.mz_rollout_policy.restype = i32
     lib.mz_rollout_policy.argtypes = [vp, i32, vp, C.c_int64, i32, i32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.mz_policy_sample.restype = i32
+    lib.mz_policy_sample.argtypes = [vp, vp, C.c_int64, i32, i32, C.c_double, u64, u64, vp, vp, vp, vp]
+    lib.mz_rollout_policy_sample.restype = i32
+    lib.mz_rollout_policy_sample.argtypes = [vp, i32, vp, C.c_int64, i32, i32, C.c_double, u64, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mz_get_status.restype = i32
     lib.mz_get_status.argtypes = [vp, vp, vp]
     lib.mz_debug_forward.restype = i32

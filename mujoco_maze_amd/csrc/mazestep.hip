@@ -47,6 +47,22 @@ __global__ __launch_bounds__(256) void policy_act_kernel(int n, int obs_dim, int
                  actions + row * nu, live);
 }
 
+// policy_act_kernel for a stochastic policy (mz_policy_sample; mz_rollout_policy_sample where it steps launch by launch): the same
+// groups, lanes 0 .. nu - 1 own the outputs and their eps, lane 0 the row's log-prob (logp nullable).  key: mzp_noise_key of the
+// draw; row r is global env slot env0 + r.
+__global__ __launch_bounds__(256) void policy_sample_kernel(int n, int obs_dim, int nu, int hidden, int squash, float action_scale,
+                                                            const float* __restrict__ params, long pstride, uint64_t key, uint64_t env0,
+                                                            const float* __restrict__ obs, float* __restrict__ actions,
+                                                            float* __restrict__ logp) {
+  __shared__ float hid[256 / MZ_POLICY_LANES][MZ_POLICY_MAX_HIDDEN];
+  const int l = (int)threadIdx.x % MZ_POLICY_LANES, grp = (int)threadIdx.x / MZ_POLICY_LANES;
+  size_t row = (size_t)blockIdx.x * (256 / MZ_POLICY_LANES) + grp;
+  const bool live = row < (size_t)n;
+  if (!live) row = (size_t)n - 1;
+  mzp_group_sample(l, MZ_POLICY_LANES, params + row * pstride, obs_dim, nu, hidden, squash, action_scale, key, env0 + row, obs + row * obs_dim,
+                   hid[grp], actions + row * nu, live, live && logp ? logp + row : nullptr);
+}
+
 static int set_err(mz_handle* h, int code, const char* what, hipError_t e) {
   if (h) snprintf(h->err, sizeof(h->err), "%s: %s", what, e == hipSuccess ? "" : hipGetErrorString(e));
   return code;
@@ -444,15 +460,18 @@ int32_t mz_rollout(mz_handle* h, int32_t n_steps, const float* actions_dev, int6
   return MZ_OK;
 }
 
-// the checks mz_policy_act and mz_rollout_policy share; MZ_OK or MZ_ERR_ARG with the message set
-static int policy_args(mz_handle* h, const char* who, const float* params_dev, int64_t param_env_stride, int32_t hidden, int32_t squash) {
+// the checks the four policy entries share (stochastic: the vector carries log_std[nu] behind the network); MZ_OK or MZ_ERR_ARG with
+// the message set
+static int policy_args(mz_handle* h, const char* who, const float* params_dev, int64_t param_env_stride, int32_t hidden, int32_t squash,
+                       bool stochastic = false) {
   char msg[160];
   const char* why = nullptr;
   if (!params_dev) why = "null params_dev";
   else if (hidden < 0 || hidden > MZ_POLICY_MAX_HIDDEN) why = "hidden must be 0 .. MZ_POLICY_MAX_HIDDEN (64)";
   else if (squash != 0 && squash != 1) why = "squash must be 0 or 1";
-  else if (param_env_stride != 0 && param_env_stride != (int64_t)mzp_param_count(h->model.obs_dim, h->model.nu, hidden))
-    why = "param_env_stride must be 0 (one shared policy) or npar (one policy per env)";
+  else if (param_env_stride != 0 && param_env_stride != (int64_t)mzp_param_count(h->model.obs_dim, h->model.nu, hidden) + (stochastic ? h->model.nu : 0))
+    why = stochastic ? "param_env_stride must be 0 (one shared policy) or npar_s = npar + nu (one policy per env, log_std behind the network)"
+                     : "param_env_stride must be 0 (one shared policy) or npar (one policy per env)";
   if (!why) return MZ_OK;
   snprintf(msg, sizeof(msg), "%s: %s", who, why);
   return set_err(h, MZ_ERR_ARG, msg, hipSuccess);
@@ -505,6 +524,66 @@ int32_t mz_rollout_policy(mz_handle* h, int32_t n_steps, const float* params_dev
     for (size_t k = 0; k < (size_t)n_steps; k++) {
       float* a = actions_seq_dev ? actions_seq_dev + k * n * nu : h->policy_act;
       policy_act_launch(h, st, params_dev, param_env_stride, hidden, squash, scale, obs_dev, a);
+      HIPCHK(h, hipGetLastError());
+      rc = step_launches(h, st, a, obs_dev, reward_dev + k * n, done_dev + k * n, goal_idx_dev ? goal_idx_dev + k * n : NULL,
+                         info_dev ? info_dev + k * n * 4 : NULL);
+      if (rc != MZ_OK) return rc;
+      if (obs_seq_dev) HIPCHK(h, hipMemcpyAsync(obs_seq_dev + k * n * od, obs_dev, n * od * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
+  }
+  h->nsteps += n_steps;
+  return MZ_OK;
+}
+
+static void policy_sample_launch(mz_handle* h, hipStream_t st, const float* params_dev, int64_t pstride, int hidden, int squash, float scale,
+                                 uint64_t noise_seed, uint64_t noise_step, const float* obs_dev, float* actions_dev, float* logp_dev) {
+  const int rows = 256 / MZ_POLICY_LANES;
+  hipLaunchKernelGGL(policy_sample_kernel, dim3((unsigned)((h->n + rows - 1) / rows)), dim3(256), 0, st, h->n, h->model.obs_dim, h->model.nu, hidden,
+                     squash, scale, params_dev, (long)pstride, mzp_noise_key(noise_seed, noise_step), h->env0, obs_dev, actions_dev, logp_dev);
+}
+
+int32_t mz_policy_sample(mz_handle* h, const float* params_dev, int64_t param_env_stride, int32_t hidden, int32_t squash, double action_scale,
+                         uint64_t noise_seed, uint64_t noise_step, const float* obs_dev, float* actions_dev, float* logp_dev, void* stream) {
+  if (!h) return MZ_ERR_ARG;
+  if (!obs_dev || !actions_dev) return set_err(h, MZ_ERR_ARG, "mz_policy_sample: null array", hipSuccess);
+  const int rc = policy_args(h, "mz_policy_sample", params_dev, param_env_stride, hidden, squash, true);
+  if (rc != MZ_OK) return rc;
+  DeviceScope scope(h->device);
+  policy_sample_launch(h, (hipStream_t)stream, params_dev, param_env_stride, hidden, squash, (float)action_scale, noise_seed, noise_step, obs_dev,
+                       actions_dev, logp_dev);
+  HIPCHK(h, hipGetLastError());
+  return MZ_OK;
+}
+
+// n_steps times a ~ policy(obs); step(a) in one call, step k with the noise of noise_step + k (include/mazestep.h).  Fused handles
+// sample inside the rollout kernels (planar_kernels.hip); every other handle runs the defining loop itself, as mz_rollout_policy does.
+int32_t mz_rollout_policy_sample(mz_handle* h, int32_t n_steps, const float* params_dev, int64_t param_env_stride, int32_t hidden, int32_t squash,
+                                 double action_scale, uint64_t noise_seed, uint64_t noise_step, float* obs_dev, float* reward_dev,
+                                 uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev, float* obs_seq_dev, float* actions_seq_dev,
+                                 float* logp_seq_dev, void* stream) {
+  if (!h) return MZ_ERR_ARG;
+  if (!obs_dev || !reward_dev || !done_dev) return set_err(h, MZ_ERR_ARG, "mz_rollout_policy_sample: null array", hipSuccess);
+  if (n_steps < 1 || n_steps > 65536) return set_err(h, MZ_ERR_ARG, "mz_rollout_policy_sample: n_steps must be 1 .. 65536", hipSuccess);
+  int rc = policy_args(h, "mz_rollout_policy_sample", params_dev, param_env_stride, hidden, squash, true);
+  if (rc != MZ_OK) return rc;
+  const size_t n = (size_t)h->n, od = (size_t)h->model.obs_dim, nu = (size_t)h->model.nu;
+  const float scale = (float)action_scale;
+  DeviceScope scope(h->device);
+  hipStream_t st = (hipStream_t)stream;
+  if (mzk_planar_rollout_fused(h)) {
+    HIPCHK(h, mzk_planar_rollout_policy_sample(h, st, n_steps, params_dev, (long)param_env_stride, hidden, squash, scale, noise_seed, noise_step, obs_dev,
+                                               reward_dev, done_dev, goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, logp_seq_dev));
+    if (h->record) {  // the last step's row
+      const size_t tot = n * (od + 2), last = (size_t)(n_steps - 1) * n;
+      hipLaunchKernelGGL(pack_record_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, h->n, h->model.obs_dim, obs_dev, reward_dev + last, done_dev + last, h->record);
+      HIPCHK(h, hipGetLastError());
+    }
+  } else {
+    if (!actions_seq_dev && !h->policy_act) HIPCHK(h, hipMalloc(&h->policy_act, n * nu * sizeof(float)));
+    for (size_t k = 0; k < (size_t)n_steps; k++) {
+      float* a = actions_seq_dev ? actions_seq_dev + k * n * nu : h->policy_act;
+      policy_sample_launch(h, st, params_dev, param_env_stride, hidden, squash, scale, noise_seed, noise_step + k, obs_dev, a,
+                           logp_seq_dev ? logp_seq_dev + k * n : NULL);
       HIPCHK(h, hipGetLastError());
       rc = step_launches(h, st, a, obs_dev, reward_dev + k * n, done_dev + k * n, goal_idx_dev ? goal_idx_dev + k * n : NULL,
                          info_dev ? info_dev + k * n * 4 : NULL);

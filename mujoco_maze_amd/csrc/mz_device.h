@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mz_rng.h"
+
 // Index of base-layout observation element i (0 .. base_dim - 1: the observation without a top-down view, whose last element
 // is t * 0.001) in a row of `ostride` floats: with a view (ostride = base_dim + MZ_VIEW_DIM) the time entry moves behind it
 // (maze_env.py:369); the view's own entries are filled by mzk_view_fill, which finds the movable blocks' x, y parked at
@@ -149,17 +151,8 @@ struct DevCtx {
   }
 };
 
-// ------------------------------------------------------------------ RNG (same definition as the oracle's mzo_rng_u32)
-__host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-  return z ^ (z >> 31);
-}
-__host__ __device__ __forceinline__ uint32_t rng_u32(uint64_t seed, uint64_t env, uint32_t counter) {
-  uint64_t z = mix64(seed + 0x9E3779B97F4A7C15ULL * (env + 1));
-  z = mix64(z + 0x9E3779B97F4A7C15ULL * ((uint64_t)counter + 1));
-  return (uint32_t)(z >> 32);
-}
+// ------------------------------------------------------------------ RNG (mix64, rng_u32: mz_rng.h; same definition as the oracle's
+// mzo_rng_u32)
 __device__ __forceinline__ float rng_u01(uint64_t seed, uint64_t env, uint32_t c) { return (float)(rng_u32(seed, env, c) >> 8) * (1.0f / 16777216.0f); }
 __device__ __forceinline__ float rng_normal(uint64_t seed, uint64_t env, uint32_t c) {
   float u1 = ((float)(rng_u32(seed, env, c) >> 8) + 1.0f) * (1.0f / 16777216.0f);

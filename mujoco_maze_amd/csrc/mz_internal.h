@@ -96,6 +96,11 @@ hipError_t mzk_planar_rollout(mz_handle* h, hipStream_t st, int nsteps, const fl
 hipError_t mzk_planar_rollout_policy(mz_handle* h, hipStream_t st, int nsteps, const float* params, long pstride, int hidden, int squash,
                                      float action_scale, float* obs, float* reward, uint8_t* done, int* goal_idx, float* info, float* obs_seq,
                                      float* actions_seq);
+// mz_rollout_policy_sample on the same handles: the same launches, every step's actions drawn from the policy's Gaussian with the
+// noise of (noise_seed, noise_step + k); logp_seq [nsteps][n] nullable
+hipError_t mzk_planar_rollout_policy_sample(mz_handle* h, hipStream_t st, int nsteps, const float* params, long pstride, int hidden, int squash,
+                                            float action_scale, uint64_t noise_seed, uint64_t noise_step, float* obs, float* reward, uint8_t* done,
+                                            int* goal_idx, float* info, float* obs_seq, float* actions_seq, float* logp_seq);
 int mzk_planar_state_width(const mz_handle* h);  // coordinates per env of the state (NV)
 int mzk_planar_record_width(const mz_handle* h); // Point: floats per env-major record; 0 for the chains (SoA)
 

@@ -1,6 +1,7 @@
-// mz_policy.h — the device-side policy of mz_policy_act / mz_rollout_policy (include/mazestep.h): one fp32 observation row in, one
-// fp32 action row out.  Shared by the stand-alone kernel (mazestep.hip policy_act_kernel), the fused closed-loop rollout kernels
-// (planar_kernels.hip) and a host build (tests/policy_host) that pins it against mujoco_maze_amd/policy.py.
+// mz_policy.h — the device-side policy of mz_policy_act / mz_rollout_policy and of their sampling twins mz_policy_sample /
+// mz_rollout_policy_sample (include/mazestep.h): one fp32 observation row in, one fp32 action row out.  Shared by the stand-alone
+// kernels (mazestep.hip policy_act_kernel, policy_sample_kernel), the fused closed-loop rollout kernels (planar_kernels.hip) and two
+// host builds (tests/policy_host, tests/policy_sample_host) that pin it against mujoco_maze_amd/policy.py.
 //
 // One policy is `npar` floats, weights input-major (nn.Linear.weight.T), so that adjacent lanes — which own adjacent output units —
 // read adjacent addresses:
@@ -14,12 +15,33 @@
 // reproduces the affine path bit for bit in float32, operation by operation; the tanh paths carry the tanhf of whichever library
 // runs them and are bit-equal only between kernels built from this header under the same flags (mazestep.hip and planar_kernels.hip:
 // STRICT in csrc/Makefile) — which is what makes the fused rollout equal the loop of mz_policy_act and mz_step.
+//
+// Stochastic policies (mz_policy_sample / mz_rollout_policy_sample): a diagonal Gaussian around the same network.  The packed vector
+// is followed by log_std[nu]: npar_s = mzp_param_count(obs_dim, nu, H) + nu floats.
+//   noise    eps(noise_seed, noise_step, slot, u) is a pure function of four integers — slot: the GLOBAL env slot (env_index_offset + i),
+//            u: the action index — and of nothing else (not N, nu, H, lanes per env, engine or kernel).  In uint64 arithmetic with
+//            wrap-around (mix64, rng_u32: mz_rng.h):
+//              key = mix64(noise_seed ^ (0xA24BAED4963EE407 * (noise_step + 1)))                                      mzp_noise_key
+//              x1 = rng_u32(key, slot, 2u), x2 = rng_u32(key, slot, 2u + 1)
+//              u1 = ((float)(x1 >> 8) + 1.0f) * 2^-24,  u2 = (float)(x2 >> 8) * 2^-24         (both exact: 24-bit integers)
+//              eps = sqrtf(-2.0f * logf(u1)) * cosf(6.2831855f * u2)                          (the Box-Muller of mz_device.h rng_normal)
+//            |eps| <= sqrt(48 ln 2) ~ 5.77, always finite.                                                            mzp_eps
+//   sample   m_u = the pre-squash sum of output unit u (mzp_output_pre), s_u = expf(log_std[u]), p = s_u * eps_u, z_u = m_u + p — the
+//            product and the sum rounded separately; the action is z_u (squash == 0) or action_scale * tanhf(z_u).    mzp_sample_unit
+//   log-prob the density of z under N(m, diag(s^2)) — with squash the PRE-tanh density: the caller applies the tanh correction
+//            sum_u log(action_scale * (1 - tanh(z_u)^2)) from the returned actions.  From eps itself, not from (z - m) / s; ONE lane,
+//            serially in u order, fp32, every operation rounded separately:
+//              acc = 0.0f;  for u = 0 .. nu - 1:  q = eps_u * eps_u;  h = -0.5f * q;  t = h - log_std[u];  t = t - 0.9189385f;
+//              acc = acc + t                                                                                           mzp_logp
+// NaN in log_std propagates to that unit's action and to the row's logp; log_std = -inf gives s = 0, z = m + (+-0) and logp = +inf.
+// mujoco_maze_amd/policy.py mirrors all of it operation by operation (noise, sample_reference).
 #pragma once
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/mazestep.h"
+#include "mz_rng.h"
 
 #if defined(__HIPCC__)
 #define MZP_HD __host__ __device__ __forceinline__
@@ -47,11 +69,16 @@ MZP_HD float mzp_hidden_unit(const float* par, int obs_dim, int H, const float* 
   return tanhf(mzp_dot(par + j, H, par[(size_t)obs_dim * H + j], x, obs_dim));
 }
 
-// output unit u from its input row `in`: the observation (H == 0) or the hidden vector (H >= 1)
-MZP_HD float mzp_output_unit(const float* par, int obs_dim, int nu, int H, int squash, float action_scale, const float* in, int u) {
+// pre-squash sum of output unit u from its input row `in`: the observation (H == 0) or the hidden vector (H >= 1)
+MZP_HD float mzp_output_pre(const float* par, int obs_dim, int nu, int H, const float* in, int u) {
   const float* W = H > 0 ? par + (size_t)obs_dim * H + H : par;
   const int nin = H > 0 ? H : obs_dim;
-  const float acc = mzp_dot(W + u, nu, W[(size_t)nin * nu + u], in, nin);
+  return mzp_dot(W + u, nu, W[(size_t)nin * nu + u], in, nin);
+}
+
+// output unit u
+MZP_HD float mzp_output_unit(const float* par, int obs_dim, int nu, int H, int squash, float action_scale, const float* in, int u) {
+  const float acc = mzp_output_pre(par, obs_dim, nu, H, in, u);
   return squash ? action_scale * tanhf(acc) : acc;
 }
 
@@ -60,6 +87,56 @@ MZP_HD void mzp_policy_row(const float* par, int obs_dim, int nu, int H, int squ
   float hid[MZ_POLICY_MAX_HIDDEN];
   for (int j = 0; j < H; j++) hid[j] = mzp_hidden_unit(par, obs_dim, H, x, j);
   for (int u = 0; u < nu; u++) act[u] = mzp_output_unit(par, obs_dim, nu, H, squash, action_scale, H > 0 ? hid : x, u);
+}
+
+// ------------------------------------------------------------------ stochastic policies (definitions: the head of this file)
+MZP_HD uint64_t mzp_noise_key(uint64_t noise_seed, uint64_t noise_step) {
+  return mix64(noise_seed ^ (0xA24BAED4963EE407ULL * (noise_step + 1)));
+}
+
+MZP_HD float mzp_eps(uint64_t key, uint64_t slot, int u) {
+#pragma clang fp contract(off) reassociate(off)
+  const uint32_t x1 = rng_u32(key, slot, 2u * (uint32_t)u), x2 = rng_u32(key, slot, 2u * (uint32_t)u + 1u);
+  const float u1 = ((float)(x1 >> 8) + 1.0f) * (1.0f / 16777216.0f);
+  const float u2 = (float)(x2 >> 8) * (1.0f / 16777216.0f);
+  const float r = sqrtf(-2.0f * logf(u1)), c = cosf(6.2831855f * u2);
+  return r * c;
+}
+
+// the action of output unit u from its pre-squash mean m
+MZP_HD float mzp_sample_unit(float m, float log_std, float eps, int squash, float action_scale) {
+#pragma clang fp contract(off) reassociate(off)
+  const float s = expf(log_std);
+  const float p = s * eps;
+  const float z = m + p;
+  return squash ? action_scale * tanhf(z) : z;
+}
+
+// log-prob of a row: one lane, u = 0 .. nu - 1 in order (the nu values of eps are computed again here)
+MZP_HD float mzp_logp(const float* log_std, int nu, uint64_t key, uint64_t slot) {
+#pragma clang fp contract(off) reassociate(off)
+  float acc = 0.0f;
+  for (int u = 0; u < nu; u++) {
+    const float e = mzp_eps(key, slot, u);
+    const float q = e * e;
+    const float h = -0.5f * q;
+    float t = h - log_std[u];
+    t = t - 0.9189385f;
+    acc = acc + t;
+  }
+  return acc;
+}
+
+// THE stochastic policy: act[nu] ~ N(mean(x), diag(exp(log_std))^2) with the noise of (noise_seed, noise_step, slot); *logp (nullable)
+MZP_HD void mzp_sample_row(const float* par, int obs_dim, int nu, int H, int squash, float action_scale, uint64_t noise_seed,
+                           uint64_t noise_step, uint64_t slot, const float* x, float* act, float* logp) {
+  float hid[MZ_POLICY_MAX_HIDDEN];
+  const float* ls = par + mzp_param_count(obs_dim, nu, H);
+  const uint64_t key = mzp_noise_key(noise_seed, noise_step);
+  for (int j = 0; j < H; j++) hid[j] = mzp_hidden_unit(par, obs_dim, H, x, j);
+  for (int u = 0; u < nu; u++)
+    act[u] = mzp_sample_unit(mzp_output_pre(par, obs_dim, nu, H, H > 0 ? hid : x, u), ls[u], mzp_eps(key, slot, u), squash, action_scale);
+  if (logp) *logp = mzp_logp(ls, nu, key, slot);
 }
 
 #if defined(__HIPCC__)
@@ -87,5 +164,22 @@ __device__ __forceinline__ void mzp_group_eval(int l, int G, const float* par, i
                           : mzp_output_unit(par, obs_dim, nu, H, squash, action_scale, x, u);
     if (store) act[u] = a;
   }
+}
+
+// mzp_group_eval for a stochastic policy: lanes 0 .. nu - 1 own the outputs and their eps, the group's first lane the row's log-prob,
+// which it stores to *logp unless that is NULL.  key: mzp_noise_key of the step; slot: the row's global env slot.
+__device__ __forceinline__ void mzp_group_sample(int l, int G, const float* par, int obs_dim, int nu, int H, int squash, float action_scale,
+                                                 uint64_t key, uint64_t slot, const float* x, float* hid, float* act, bool store, float* logp) {
+  if (H > 0) {
+    for (int j = l; j < H; j += G) hid[j] = mzp_hidden_unit(par, obs_dim, H, x, j);
+    mzp_wave_sync();
+  }
+  const float* ls = par + mzp_param_count(obs_dim, nu, H);
+  for (int u = l; u < nu; u += G) {
+    const float m = H > 0 ? mzp_output_pre(par, obs_dim, nu, H, hid, u) : mzp_output_pre(par, obs_dim, nu, H, x, u);
+    const float a = mzp_sample_unit(m, ls[u], mzp_eps(key, slot, u), squash, action_scale);
+    if (store) act[u] = a;
+  }
+  if (l == 0 && logp) *logp = mzp_logp(ls, nu, key, slot);
 }
 #endif

@@ -1,0 +1,22 @@
+// mz_rng.h — the integer part of the counter-based RNG, ONE definition for the device kernels (through mz_device.h: the reset
+// distribution; through mz_policy.h: the policy noise) and for host builds (tests/policy_sample_host compiles it with g++).  Same
+// definition as the oracle's mzo_rng_u32.  No floating point here: what a stream makes of the words is its own business.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define MZ_RNG_HD __host__ __device__ __forceinline__
+#else
+#define MZ_RNG_HD inline
+#endif
+
+MZ_RNG_HD uint64_t mix64(uint64_t z) {
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+  return z ^ (z >> 31);
+}
+MZ_RNG_HD uint32_t rng_u32(uint64_t seed, uint64_t env, uint32_t counter) {
+  uint64_t z = mix64(seed + 0x9E3779B97F4A7C15ULL * (env + 1));
+  z = mix64(z + 0x9E3779B97F4A7C15ULL * ((uint64_t)counter + 1));
+  return (uint32_t)(z >> 32);
+}

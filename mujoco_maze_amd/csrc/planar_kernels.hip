@@ -5,7 +5,8 @@
 //   swimmer_step_kernel<NL,NB,G> one MazeEnv.step for the Swimmer (NL = 3) / Reacher (NL = 2): G = 4 lanes per env (lane b = link b), fp64.
 //   planar_rollout_kernel / swimmer_rollout_kernel  up to MZ_ROLLOUT_CHUNK steps of the same on a state that stays on chip (mz_rollout).
 //   planar_policy_rollout_kernel / swimmer_policy_rollout_kernel  the same with the actions of every step computed on chip by the policy
-//                                of mz_policy.h from the step's observation row (mz_rollout_policy).
+//                                of mz_policy.h from the step's observation row (mz_rollout_policy), or sampled from its Gaussian
+//                                (SMP instantiations: mz_rollout_policy_sample).
 //   reset / state copy kernels; debug kernels for the parity tests (task predicates, the Point's wall detector).
 //
 // HBM layout: SoA  q_0..q_{NV-1} | v_0..v_{NV-1}, each [N] fp32; t[N], episode[N] i32.  API arrays are row-major [N, k].
@@ -238,12 +239,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && 
 // mz_policy_act and mz_step bit for bit.  Lanes l, l + G, .. own hidden units (phid), lanes 0 and 1 the two outputs (pact); `obs` is
 // written at the launch's last step, always: the next launch of the same rollout reads its first row there.  Idle groups shadow the
 // last env through every hand-off and store nothing.  A kernel of its own beside planar_rollout_kernel, whose code stays what it was.
-template <int NB, int NS, int G>
+// SMP (mz_rollout_policy_sample): the policy is the diagonal Gaussian of mz_policy.h — the lane that owns output u draws eps_u for
+// (ns.seed, ns.step + step, env0 + env, u) and forms the action, the group's first lane writes the row of ns.logp_seq, actions_seq
+// gets the sampled actions — with the unit functions policy_sample_kernel (mazestep.hip) runs: equal to the loop of mz_policy_sample
+// and mz_step bit for bit.  SMP == false compiles the deterministic kernel's source unchanged and never reads `ns`.
+struct PolicyNoise {
+  uint64_t seed, step;  // noise_seed; noise_step of the launch's first step
+  float* logp_seq;      // [nsteps][n] rows of the launch (nullable)
+};
+template <int NB, int NS, int G, bool SMP = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && NS == 0 && G == 32) ? 2 : 1))) void planar_policy_rollout_kernel(
     const PointDev* __restrict__ Pp, int n, PointState S, int nsteps, const float* __restrict__ params, long pstride, int hidden, int squash,
     float action_scale, float* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ done, int* __restrict__ goal_idx,
     float* __restrict__ info, float* __restrict__ obs_seq, float* __restrict__ actions_seq, int* __restrict__ status, int auto_reset,
-    uint64_t seed, uint64_t env0, float* __restrict__ final_obs) {
+    uint64_t seed, uint64_t env0, float* __restrict__ final_obs, PolicyNoise ns) {
   using D = PlanarDims<NB, NS>;
   constexpr int NV = D::NV, NOBS = D::NOBS, EPW = 64 / G;
   constexpr bool BARE = NB == 0 && NS == 0;
@@ -270,7 +279,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && 
   for (int step = 0; step < nsteps; step++) {
     const size_t row = (size_t)step * n + env;
     cx.sync();  // the row in o is complete
-    mzp_group_eval(cx.l, G, par, NOBS, 2, hidden, squash, action_scale, o, phid[grp], pact[grp], true);
+    if constexpr (SMP)
+      mzp_group_sample(cx.l, G, par, NOBS, 2, hidden, squash, action_scale, mzp_noise_key(ns.seed, ns.step + (uint64_t)step), env0 + (uint64_t)env, o,
+                       phid[grp], pact[grp], true, live && ns.logp_seq ? ns.logp_seq + row : nullptr);
+    else
+      mzp_group_eval(cx.l, G, par, NOBS, 2, hidden, squash, action_scale, o, phid[grp], pact[grp], true);
     cx.sync();
     const float a0 = pact[grp][0], a1 = pact[grp][1];
     if (live && cx.l == 0 && actions_seq) { actions_seq[row * 2] = a0; actions_seq[row * 2 + 1] = a1; }
@@ -566,14 +579,15 @@ __global__ __launch_bounds__(256) void swimmer_rollout_kernel(const SwimmerDev* 
 // swimmer_rollout_kernel with the actions computed on chip (mz_rollout_policy; see planar_policy_rollout_kernel).  The observation
 // row lives in registers, redundantly in every lane of the group; the group's first lane puts it into LDS (px), the G lanes split the
 // hidden units (phid) and the outputs (pact) over themselves and every lane reads the NH actions back.  Surplus groups shadow the
-// last env through every hand-off and shuffle and store nothing.
-template <int NL, int NB, int G>
+// last env through every hand-off and shuffle and store nothing.  SMP: as in planar_policy_rollout_kernel.
+template <int NL, int NB, int G, bool SMP = false>
 __global__ __launch_bounds__(256) void swimmer_policy_rollout_kernel(const SwimmerDev* __restrict__ Pp, int n, PointState S, int nsteps,
                                                                       const float* __restrict__ params, long pstride, int hidden, int squash,
                                                                       float action_scale, float* __restrict__ obs, float* __restrict__ reward,
                                                                       uint8_t* __restrict__ done, int* __restrict__ goal_idx, float* __restrict__ info,
                                                                       float* __restrict__ obs_seq, float* __restrict__ actions_seq, int* __restrict__ status,
-                                                                      int auto_reset, uint64_t seed, uint64_t env0, float* __restrict__ final_obs) {
+                                                                      int auto_reset, uint64_t seed, uint64_t env0, float* __restrict__ final_obs,
+                                                                      PolicyNoise ns) {
   constexpr int NR = NL + 2, NV = NR + NB, NH = NL - 1, NOMAX = 2 * NV + 4, GPB = 256 / G;
   __shared__ float px[GPB][NOMAX];
   __shared__ float phid[GPB][MZ_POLICY_MAX_HIDDEN];
@@ -598,7 +612,11 @@ __global__ __launch_bounds__(256) void swimmer_policy_rollout_kernel(const Swimm
   for (int step = 0; step < nsteps; step++) {
     const size_t row = (size_t)step * n + env;
     mzp_wave_sync();  // the row in x is complete
-    mzp_group_eval(cx.l, G, par, NO, NH, hidden, squash, action_scale, x, phid[grp], pact[grp], true);
+    if constexpr (SMP)
+      mzp_group_sample(cx.l, G, par, NO, NH, hidden, squash, action_scale, mzp_noise_key(ns.seed, ns.step + (uint64_t)step), env0 + (uint64_t)env, x,
+                       phid[grp], pact[grp], true, live && ns.logp_seq ? ns.logp_seq + row : nullptr);
+    else
+      mzp_group_eval(cx.l, G, par, NO, NH, hidden, squash, action_scale, x, phid[grp], pact[grp], true);
     mzp_wave_sync();
     for (int k = 0; k < NH; k++) af[k] = pact[grp][k];
     if (live && actions_seq) for (int k = 0; k < NH; k++) actions_seq[row * NH + k] = af[k];
@@ -854,11 +872,13 @@ hipError_t mzk_planar_rollout(mz_handle* h, hipStream_t st, int nsteps, const fl
   return hipSuccess;
 }
 
-// mz_rollout_policy on the fused handles: mzk_planar_rollout's launches with the policy in place of the action tensor.  Every launch
-// writes obs_dev at its last step, and the next one reads its first observation there.
-hipError_t mzk_planar_rollout_policy(mz_handle* h, hipStream_t st, int nsteps, const float* params_dev, long pstride, int hidden, int squash,
-                                     float action_scale, float* obs_dev, float* reward_dev, uint8_t* done_dev, int* goal_idx_dev, float* info_dev,
-                                     float* obs_seq_dev, float* actions_seq_dev) {
+// mz_rollout_policy (SMP false) / mz_rollout_policy_sample (SMP true: `noise` holds the call's seed, first step and logp_seq) on
+// the fused handles: mzk_planar_rollout's launches with the policy in place of the action tensor.  Every launch writes obs_dev at
+// its last step, and the next one reads its first observation there — and continues at noise_step + the steps done so far.
+template <bool SMP>
+static hipError_t planar_rollout_policy_launches(mz_handle* h, hipStream_t st, int nsteps, const float* params_dev, long pstride, int hidden,
+                                                 int squash, float action_scale, float* obs_dev, float* reward_dev, uint8_t* done_dev,
+                                                 int* goal_idx_dev, float* info_dev, float* obs_seq_dev, float* actions_seq_dev, PolicyNoise noise) {
   PointState S{h->state, h->pt_t, h->pt_ep, h->pt_rec};
   const size_t n = (size_t)h->n, od = (size_t)h->model.obs_dim, nu = (size_t)h->model.nu;
   for (int k0 = 0; k0 < nsteps; k0 += MZ_ROLLOUT_CHUNK) {
@@ -869,11 +889,12 @@ hipError_t mzk_planar_rollout_policy(mz_handle* h, hipStream_t st, int nsteps, c
     float* inf = info_dev ? info_dev + k0 * n * 4 : nullptr;
     float* oseq = obs_seq_dev ? obs_seq_dev + k0 * n * od : nullptr;
     float* aseq = actions_seq_dev ? actions_seq_dev + k0 * n * nu : nullptr;
+    const PolicyNoise ns{noise.seed, noise.step + (uint64_t)k0, noise.logp_seq ? noise.logp_seq + k0 * n : nullptr};
     if (h->robot == MZ_ROBOT_SWIMMER) {
 #define MZ_SW_ROLL(NL, NB)                                                                                                          \
-  hipLaunchKernelGGL((swimmer_policy_rollout_kernel<NL, NB, (NL <= 4 ? 4 : 8)>), dim3((unsigned)((n * (NL <= 4 ? 4 : 8) + sw_bd - 1) / sw_bd)), dim3(sw_bd), 0, st, \
+  hipLaunchKernelGGL((swimmer_policy_rollout_kernel<NL, NB, (NL <= 4 ? 4 : 8), SMP>), dim3((unsigned)((n * (NL <= 4 ? 4 : 8) + sw_bd - 1) / sw_bd)), dim3(sw_bd), 0, st, \
                      h->swimmer_dev, h->n, S, ks, params_dev, pstride, hidden, squash, action_scale, obs_dev, rew, dn, gi, inf, oseq, aseq, h->status,         \
-                     h->auto_reset, h->seed, h->env0, h->final_obs)
+                     h->auto_reset, h->seed, h->env0, h->final_obs, ns)
       const int bd = h->swimmer.nblock ? h->swimmer.nbdof : 0;
       const unsigned sw_bd = 64u * (unsigned)(h->wpb_set ? h->waves_per_block : 4);
       if (h->swimmer.nlink == 3) { if (bd == 3) MZ_SW_ROLL(3, 3); else if (bd == 2) MZ_SW_ROLL(3, 2); else MZ_SW_ROLL(3, 0); }
@@ -884,8 +905,8 @@ hipError_t mzk_planar_rollout_policy(mz_handle* h, hipStream_t st, int nsteps, c
 #undef MZ_SW_ROLL
     } else {
 #define MZ_PLANAR_ROLL(NB, NS, G)                                                                                                      \
-  hipLaunchKernelGGL((planar_policy_rollout_kernel<NB, NS, G>), dim3((h->n + 64 / G - 1) / (64 / G)), dim3(64), 0, st, h->point_dev, h->n, S, ks, params_dev, \
-                     pstride, hidden, squash, action_scale, obs_dev, rew, dn, gi, inf, oseq, aseq, h->status, h->auto_reset, h->seed, h->env0, h->final_obs)
+  hipLaunchKernelGGL((planar_policy_rollout_kernel<NB, NS, G, SMP>), dim3((h->n + 64 / G - 1) / (64 / G)), dim3(64), 0, st, h->point_dev, h->n, S, ks, params_dev, \
+                     pstride, hidden, squash, action_scale, obs_dev, rew, dn, gi, inf, oseq, aseq, h->status, h->auto_reset, h->seed, h->env0, h->final_obs, ns)
       if (h->point.nball) MZ_PLANAR_ROLL(0, 1, 32);
       else switch (h->point.nblock) {
         case 0: {
@@ -905,6 +926,21 @@ hipError_t mzk_planar_rollout_policy(mz_handle* h, hipStream_t st, int nsteps, c
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+
+hipError_t mzk_planar_rollout_policy(mz_handle* h, hipStream_t st, int nsteps, const float* params_dev, long pstride, int hidden, int squash,
+                                     float action_scale, float* obs_dev, float* reward_dev, uint8_t* done_dev, int* goal_idx_dev, float* info_dev,
+                                     float* obs_seq_dev, float* actions_seq_dev) {
+  return planar_rollout_policy_launches<false>(h, st, nsteps, params_dev, pstride, hidden, squash, action_scale, obs_dev, reward_dev, done_dev,
+                                               goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, PolicyNoise{0, 0, nullptr});
+}
+
+hipError_t mzk_planar_rollout_policy_sample(mz_handle* h, hipStream_t st, int nsteps, const float* params_dev, long pstride, int hidden, int squash,
+                                            float action_scale, uint64_t noise_seed, uint64_t noise_step, float* obs_dev, float* reward_dev,
+                                            uint8_t* done_dev, int* goal_idx_dev, float* info_dev, float* obs_seq_dev, float* actions_seq_dev,
+                                            float* logp_seq_dev) {
+  return planar_rollout_policy_launches<true>(h, st, nsteps, params_dev, pstride, hidden, squash, action_scale, obs_dev, reward_dev, done_dev,
+                                              goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, PolicyNoise{noise_seed, noise_step, logp_seq_dev});
 }
 
 hipError_t mzk_planar_reset(mz_handle* h, hipStream_t st, const uint8_t* mask_dev, uint64_t seed, float* obs_dev) {

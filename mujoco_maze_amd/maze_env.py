@@ -185,6 +185,8 @@ class VecMazeEnv:
         self._goal = torch.empty(n, dtype=torch.int32, device=dev)
         self._info = torch.empty((n, 4), dtype=torch.float32, device=dev)
         self._seed = int(seed)
+        self._noise_seed = int(seed)  # default noise_seed of policy_sample / rollout_policy_sample: the last reset(seed=...), else this
+        self._noise_step = 0          # their counter: +1 per policy_sample, +K per rollout_policy_sample (explicit arguments leave it alone)
         self._host_rewards = not self.model.device_rewards
         self._final_obs = None
         self._host_mask = None
@@ -363,6 +365,7 @@ class VecMazeEnv:
         does.  Tasks whose goals never move keep the one shared table."""
         if seed is not None:
             self._seed = int(seed)
+            self._noise_seed, self._noise_step = int(seed), 0  # a reseeded env draws the same policy noise again
         if mask is None and self._task.sample_goals():
             self._resampled_goals = True
             self._sync_goals_across_ranks()
@@ -456,15 +459,16 @@ class VecMazeEnv:
             info["final_observation"] = self._final_obs
         return self._obs, buf["reward"], buf["done"], info
 
-    def _policy_params(self, params, hidden: int):
-        """params as a contiguous float32 device tensor [npar] or [N, npar]; returns (tensor, param_env_stride)."""
+    def _policy_params(self, params, hidden: int, stochastic: bool = False):
+        """params as a contiguous float32 device tensor [npar] or [N, npar] (stochastic: npar_s = npar + nu, log_std behind the
+        network); returns (tensor, param_env_stride)."""
         from mujoco_maze_amd import policy
 
         torch = self._torch
         hidden = int(hidden)
         if not 0 <= hidden <= policy.MAX_HIDDEN:
             raise ValueError(f"hidden must be 0 .. {policy.MAX_HIDDEN}, got {hidden}")
-        npar = policy.param_count(self.obs_dim, self.nu, hidden)
+        npar = policy.param_count(self.obs_dim, self.nu, hidden, stochastic)
         p = params if torch.is_tensor(params) else torch.as_tensor(np.asarray(params, dtype=np.float32), device=self.device)
         if p.dtype != torch.float32 or not p.is_contiguous() or p.device != self.device:
             p = p.to(device=self.device, dtype=torch.float32).contiguous()
@@ -538,6 +542,89 @@ class VecMazeEnv:
             _capi.check(self._lib, self._h, rc, "mz_rollout_policy")
         info = {"position": buf["info"][:, :, :2], "reward_forward": buf["info"][:, :, 2], "reward_ctrl": buf["info"][:, :, 3],
                 "goal_index": buf["goal"]}
+        if return_obs:
+            info["observations"] = buf["obs_seq"]
+        if return_actions:
+            info["actions"] = buf["actions"]
+        if self._auto_reset:
+            info["final_observation"] = self._final_obs
+        return self._obs, buf["reward"], buf["done"], info
+
+    def _noise_args(self, noise_seed, noise_step, advance: int):
+        """(noise_seed, noise_step) of a draw as uint64: the env's own seed and counter where the caller gives none; the counter
+        advances by `advance` only when it was used."""
+        seed = self._noise_seed if noise_seed is None else int(noise_seed)
+        if noise_step is None:
+            step = self._noise_step
+            self._noise_step += advance
+        else:
+            step = int(noise_step)
+        return C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), C.c_uint64(step & 0xFFFFFFFFFFFFFFFF)
+
+    def policy_sample(self, params, obs=None, hidden: int = 0, squash: bool = False, action_scale: float = 1.0, noise_seed: Optional[int] = None,
+                      noise_step: Optional[int] = None):
+        """One draw from a diagonal-Gaussian policy on the device (mz_policy_sample): (actions [N, nu], logp [N]).  params: float32
+        [npar_s] or [N, npar_s], the vector of `policy_act` followed by log_std [nu] (`policy.pack(..., log_std=)`).  With m the
+        network's pre-squash output, a = m + exp(log_std) * eps, or action_scale * tanh(.) of that with `squash`; logp is the density
+        of the PRE-tanh sample, sum_u (-0.5 eps_u^2 - log_std_u - 0.9189385): apply the tanh correction from the actions yourself.
+
+        eps is a pure function of (noise_seed, noise_step, global env slot, action index) — `policy.noise` —, so a draw does not
+        depend on the batch size or on how a batch is sharded.  noise_seed defaults to the seed of the last `reset(seed=...)`, else the
+        constructor's; noise_step to an env-held counter that starts at 0 (again after `reset(seed=...)`) and advances by 1 per call
+        and by K per `rollout_policy_sample`.  Explicit values are used as given and leave the counter alone."""
+        p, stride = self._policy_params(params, hidden, stochastic=True)
+        o = self._obs if obs is None else self._policy_obs(obs)
+        torch = self._torch
+        out = torch.empty((self.num_envs, self.nu), dtype=torch.float32, device=self.device)
+        logp = torch.empty(self.num_envs, dtype=torch.float32, device=self.device)
+        seed, step = self._noise_args(noise_seed, noise_step, 1)
+        rc = self._lib.mz_policy_sample(self._h, _ptr(p), stride, int(hidden), 1 if squash else 0, float(action_scale), seed, step, _ptr(o), _ptr(out),
+                                        _ptr(logp), self._stream())
+        _capi.check(self._lib, self._h, rc, "mz_policy_sample")
+        return out, logp
+
+    def rollout_policy_sample(self, params, steps: int, hidden: int = 0, squash: bool = False, action_scale: float = 1.0, obs=None,
+                              noise_seed: Optional[int] = None, noise_step: Optional[int] = None, return_obs: bool = False,
+                              return_actions: bool = False):
+        """K = `steps` closed-loop steps with a sampled action each, in one call: exactly what K times (`policy_sample` with
+        noise_step + k, `step`) give, state and outputs bit for bit.  Everything as in `rollout_policy`, plus info["logp"] [K, N], the
+        log-probabilities of the draws (see `policy_sample`); info["actions"] [K, N, nu] with `return_actions` holds the sampled
+        actions.  noise_seed / noise_step as in `policy_sample`; the env's counter advances by K.
+
+        One mz_rollout_policy_sample call — sampled inside the fused rollout kernels of the Point, Swimmer and Reacher — except
+        where the host has work between steps (as in `rollout_policy`): there this method loops `policy_sample` + `step` itself."""
+        torch, n = self._torch, self.num_envs
+        p, stride = self._policy_params(params, hidden, stochastic=True)
+        K = int(steps)
+        if not 1 <= K <= 65536:
+            raise ValueError(f"a rollout takes 1 .. 65536 steps, got {K}")
+        if obs is not None:
+            o = self._policy_obs(obs)
+            if o.data_ptr() != self._obs.data_ptr():
+                self._obs.copy_(o)
+        buf = self._rollout_buffers(K, return_obs)
+        if return_actions and "actions" not in buf:
+            buf["actions"] = torch.empty((K, n, self.nu), dtype=torch.float32, device=self.device)
+        if "logp" not in buf:
+            buf["logp"] = torch.empty((K, n), dtype=torch.float32, device=self.device)
+        seed, step = self._noise_args(noise_seed, noise_step, K)
+        if self._host_rewards or (self._env_goals is not None and self._auto_reset):
+            for k in range(K):
+                a, lp = self.policy_sample(p, None, hidden, squash, action_scale, seed.value, step.value + k)
+                o, rew, done, inf = self.step(a)
+                buf["reward"][k], buf["done"][k], buf["goal"][k], buf["info"][k], buf["logp"][k] = rew, done, inf["goal_index"], self._info, lp
+                if return_obs:
+                    buf["obs_seq"][k] = o
+                if return_actions:
+                    buf["actions"][k] = a
+        else:
+            rc = self._lib.mz_rollout_policy_sample(self._h, K, _ptr(p), stride, int(hidden), 1 if squash else 0, float(action_scale), seed, step,
+                                                    _ptr(self._obs), _ptr(buf["reward"]), _ptr(buf["done"]), _ptr(buf["goal"]), _ptr(buf["info"]),
+                                                    _ptr(buf["obs_seq"]) if return_obs else None,
+                                                    _ptr(buf["actions"]) if return_actions else None, _ptr(buf["logp"]), self._stream())
+            _capi.check(self._lib, self._h, rc, "mz_rollout_policy_sample")
+        info = {"position": buf["info"][:, :, :2], "reward_forward": buf["info"][:, :, 2], "reward_ctrl": buf["info"][:, :, 3],
+                "goal_index": buf["goal"], "logp": buf["logp"]}
         if return_obs:
             info["observations"] = buf["obs_seq"]
         if return_actions:

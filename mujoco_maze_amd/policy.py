@@ -11,17 +11,34 @@ csrc/mz_policy.h in numpy float32, operation by operation: every unit starts fro
 order, the product and the sum rounded separately; hidden units are tanh of that, an output is the sum or
 float32(action_scale) * tanh(sum).  For the affine, unsquashed case it equals the device's result bit for bit; with a tanh it
 differs by what numpy's float32 tanh and the device's tanhf differ.
+
+Stochastic policies (VecMazeEnv.policy_sample / rollout_policy_sample, mz_policy_sample / mz_rollout_policy_sample) are a diagonal
+Gaussian around the same network: the vector carries `log_std [nu]` behind it (`param_count(..., stochastic=True)`, the `log_std=`
+argument of `pack` / `pack_linear`).  `noise` is the device's eps(noise_seed, noise_step, slot, u) — a pure function of four integers,
+slot being the global env slot —, `sample_reference` the draw and its log-probability:
+
+    key = mix64(noise_seed ^ (0xA24BAED4963EE407 * (noise_step + 1)))                    uint64, wrap-around
+    x1, x2 = rng_u32(key, slot, 2u), rng_u32(key, slot, 2u + 1)
+    u1 = ((x1 >> 8) + 1) * 2^-24, u2 = (x2 >> 8) * 2^-24, eps = sqrt(-2 log(u1)) * cos(float32(6.2831855) * u2)
+    z_u = m_u + exp(log_std_u) * eps_u           (m_u: the pre-squash sum; product and sum rounded separately, float32)
+    action_u = z_u, or float32(action_scale) * tanh(z_u) with squash
+    logp = sum_u (-0.5 * eps_u^2 - log_std_u - 0.9189385), u in order, float32, every operation rounded separately
+
+logp is the density of z; with squash it is the PRE-tanh density, and the caller applies the tanh correction from the actions.
+The integer part is exact; the float part runs float64 libm on the float32 u1, u2 and the float32 angle and rounds the factors to
+float32, so it differs from the device by libm ulps only.
 """
 import numpy as np
 
 MAX_HIDDEN = 64  # MZ_POLICY_MAX_HIDDEN (include/mazestep.h)
 
 
-def param_count(obs_dim: int, nu: int, hidden: int = 0) -> int:
+def param_count(obs_dim: int, nu: int, hidden: int = 0, stochastic: bool = False) -> int:
+    """Floats of one policy; with `stochastic` the network's count plus log_std [nu]."""
     obs_dim, nu, hidden = int(obs_dim), int(nu), int(hidden)
     if not 0 <= hidden <= MAX_HIDDEN:
         raise ValueError(f"hidden must be 0 .. {MAX_HIDDEN}, got {hidden}")
-    return obs_dim * hidden + hidden + hidden * nu + nu if hidden else obs_dim * nu + nu
+    return (obs_dim * hidden + hidden + hidden * nu + nu if hidden else obs_dim * nu + nu) + (nu if stochastic else 0)
 
 
 def _np(x):
@@ -30,22 +47,33 @@ def _np(x):
     return np.asarray(x, dtype=np.float32)
 
 
-def pack_linear(W, b):
-    """Affine policy a = W @ obs + b: W [nu, obs_dim], b [nu] (nn.Linear's weight and bias) -> float32 [obs_dim * nu + nu]."""
+def _with_log_std(parts, nu, log_std):
+    if log_std is None:
+        return np.concatenate(parts)
+    ls = _np(log_std)
+    if ls.shape != (nu,):
+        raise ValueError(f"log_std must be [nu] = {(nu,)}, got {ls.shape}")
+    return np.concatenate(parts + [ls])
+
+
+def pack_linear(W, b, log_std=None):
+    """Affine policy a = W @ obs + b: W [nu, obs_dim], b [nu] (nn.Linear's weight and bias) -> float32 [obs_dim * nu + nu]; with
+    `log_std` [nu] the stochastic policy's vector, nu numbers longer."""
     W, b = _np(W), _np(b)
     if W.ndim != 2 or b.shape != (W.shape[0],):
         raise ValueError(f"W must be [nu, obs_dim] and b [nu], got {W.shape} and {b.shape}")
-    return np.concatenate([W.T.ravel(), b])
+    return _with_log_std([W.T.ravel(), b], W.shape[0], log_std)
 
 
-def pack(W1, b1, W2, b2):
-    """One tanh hidden layer, a = W2 @ tanh(W1 @ obs + b1) + b2: W1 [H, obs_dim], b1 [H], W2 [nu, H], b2 [nu] -> float32 [npar]."""
+def pack(W1, b1, W2, b2, log_std=None):
+    """One tanh hidden layer, a = W2 @ tanh(W1 @ obs + b1) + b2: W1 [H, obs_dim], b1 [H], W2 [nu, H], b2 [nu] -> float32 [npar];
+    with `log_std` [nu] the stochastic policy's vector, nu numbers longer."""
     W1, b1, W2, b2 = _np(W1), _np(b1), _np(W2), _np(b2)
     if W1.ndim != 2 or W2.ndim != 2 or b1.shape != (W1.shape[0],) or W2.shape[1] != W1.shape[0] or b2.shape != (W2.shape[0],):
         raise ValueError(f"want W1 [H, obs_dim], b1 [H], W2 [nu, H], b2 [nu], got {W1.shape}, {b1.shape}, {W2.shape}, {b2.shape}")
     if not 1 <= W1.shape[0] <= MAX_HIDDEN:
         raise ValueError(f"the hidden layer has 1 .. {MAX_HIDDEN} units, got {W1.shape[0]}")
-    return np.concatenate([W1.T.ravel(), b1, W2.T.ravel(), b2])
+    return _with_log_std([W1.T.ravel(), b1, W2.T.ravel(), b2], W2.shape[0], log_std)
 
 
 def _layer(x, Wt, b):
@@ -55,6 +83,20 @@ def _layer(x, Wt, b):
         p = (Wt[..., i, :] * x[:, i: i + 1]).astype(np.float32)
         acc = (acc + p).astype(np.float32)
     return acc
+
+
+def _pre_squash(x, p, nu, H):
+    """The output units' sums before the squash: x [R, obs_dim], p [npar] or [R, npar] -> float32 [R, nu]."""
+    od, lead = x.shape[1], p.shape[:-1]
+    if H:
+        o1, o2, o3 = od * H, od * H + H, od * H + H + H * nu
+        h = np.tanh(_layer(x, p[..., :o1].reshape(lead + (od, H)), p[..., o1:o2])).astype(np.float32)
+        return _layer(h, p[..., o2:o3].reshape(lead + (H, nu)), p[..., o3:])
+    return _layer(x, p[..., : od * nu].reshape(lead + (od, nu)), p[..., od * nu:])
+
+
+def _squashed(acc, squash, action_scale):
+    return (np.float32(action_scale) * np.tanh(acc).astype(np.float32)).astype(np.float32) if squash else acc
 
 
 def reference(params, obs, nu: int, hidden: int = 0, squash: bool = False, action_scale: float = 1.0):
@@ -68,12 +110,79 @@ def reference(params, obs, nu: int, hidden: int = 0, squash: bool = False, actio
     npar = param_count(od, nu, H)
     if p.shape not in ((npar,), (R, npar)):
         raise ValueError(f"params must have shape {(npar,)} or {(R, npar)}, got {p.shape}")
-    lead = p.shape[:-1]
-    if H:
-        o1, o2, o3 = od * H, od * H + H, od * H + H + H * nu
-        h = np.tanh(_layer(x, p[..., :o1].reshape(lead + (od, H)), p[..., o1:o2])).astype(np.float32)
-        acc = _layer(h, p[..., o2:o3].reshape(lead + (H, nu)), p[..., o3:])
-    else:
-        acc = _layer(x, p[..., : od * nu].reshape(lead + (od, nu)), p[..., od * nu:])
-    out = (np.float32(action_scale) * np.tanh(acc).astype(np.float32)).astype(np.float32) if squash else acc
+    out = _squashed(_pre_squash(x, p, nu, H), squash, action_scale)
     return out[0] if single else out
+
+
+_M64 = (1 << 64) - 1
+_GOLDEN, _STEP_MUL = np.uint64(0x9E3779B97F4A7C15), 0xA24BAED4963EE407
+
+
+def _mix64(z):
+    """csrc/mz_rng.h mix64 on a uint64 array (numpy's uint64 arithmetic wraps around)."""
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def noise_key(noise_seed: int, noise_step: int) -> int:
+    """The key of one step's noise (csrc/mz_policy.h mzp_noise_key), a Python int in [0, 2^64)."""
+    k = (int(noise_seed) & _M64) ^ ((_STEP_MUL * ((int(noise_step) + 1) & _M64)) & _M64)
+    with np.errstate(over="ignore"):
+        return int(_mix64(np.array([k], dtype=np.uint64))[0])
+
+
+def noise_words(noise_seed: int, noise_step: int, slots, nu: int):
+    """The integer stream behind `noise`: uint32 [len(slots), nu, 2], words rng_u32(key, slot, 2u) and rng_u32(key, slot, 2u + 1)."""
+    key = np.uint64(noise_key(noise_seed, noise_step))
+    sl = np.array([int(s) & _M64 for s in np.atleast_1d(np.asarray(slots, dtype=object)).ravel()], dtype=np.uint64)
+    c = np.arange(2 * int(nu), dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        z = _mix64(key + _GOLDEN * (sl + np.uint64(1)))
+        z = _mix64(z[:, None] + _GOLDEN * (c[None, :] + np.uint64(1)))
+    return (z >> np.uint64(32)).astype(np.uint32).reshape(len(sl), int(nu), 2)
+
+
+def noise(noise_seed: int, noise_step: int, slots, nu: int):
+    """eps(noise_seed, noise_step, slot, u) of csrc/mz_policy.h for the global env slots `slots` and u = 0 .. nu - 1: float32
+    [len(slots), nu].  A value depends on its four integers only."""
+    w = noise_words(noise_seed, noise_step, slots, nu)
+    u1 = (((w[..., 0] >> np.uint32(8)).astype(np.float32) + np.float32(1.0)) * np.float32(1.0 / 16777216.0)).astype(np.float32)
+    u2 = ((w[..., 1] >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)).astype(np.float32)
+    t = (np.float32(-2.0) * np.log(u1.astype(np.float64)).astype(np.float32)).astype(np.float32)
+    r = np.sqrt(t.astype(np.float64)).astype(np.float32)
+    ang = (np.float32(6.2831855) * u2).astype(np.float32)
+    c = np.cos(ang.astype(np.float64)).astype(np.float32)
+    return (r * c).astype(np.float32)
+
+
+def sample_reference(params, obs, nu: int, hidden: int = 0, squash: bool = False, action_scale: float = 1.0, noise_seed: int = 0,
+                     noise_step: int = 0, slots=None):
+    """The stochastic policy of csrc/mz_policy.h on rows of observations: obs [R, obs_dim] (or [obs_dim]); params [npar_s] shared by
+    the rows or [R, npar_s]; slots: the rows' global env slots, default 0 .. R - 1.  Returns (actions float32 [R, nu], logp float32
+    [R]) — or ([nu], scalar) for a single row."""
+    x = np.asarray(obs, dtype=np.float32)
+    single = x.ndim == 1
+    x = np.atleast_2d(x)
+    p = np.asarray(params, dtype=np.float32)
+    R, od, nu, H = x.shape[0], x.shape[1], int(nu), int(hidden)
+    npar = param_count(od, nu, H)
+    if p.shape not in ((npar + nu,), (R, npar + nu)):
+        raise ValueError(f"params must have shape {(npar + nu,)} or {(R, npar + nu)} (the network, then log_std [nu]), got {p.shape}")
+    sl = np.arange(R) if slots is None else np.atleast_1d(np.asarray(slots, dtype=object)).ravel()
+    if len(sl) != R:
+        raise ValueError(f"slots must name one global env slot per row ({R}), got {len(sl)}")
+    ls = np.broadcast_to(p[..., npar:], (R, nu))
+    m = _pre_squash(x, p[..., :npar], nu, H)
+    eps = noise(noise_seed, noise_step, sl, nu)
+    with np.errstate(over="ignore", invalid="ignore"):
+        s = np.exp(ls.astype(np.float64)).astype(np.float32)
+        z = (m + (s * eps).astype(np.float32)).astype(np.float32)
+        act = _squashed(z, squash, action_scale)
+        logp = np.zeros(R, dtype=np.float32)
+        for u in range(nu):
+            q = (eps[:, u] * eps[:, u]).astype(np.float32)
+            t = ((np.float32(-0.5) * q).astype(np.float32) - ls[:, u]).astype(np.float32)
+            t = (t - np.float32(0.9189385)).astype(np.float32)
+            logp = (logp + t).astype(np.float32)
+    return (act[0], logp[0]) if single else (act, logp)

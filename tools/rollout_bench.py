@@ -6,6 +6,9 @@ at least `--seconds` of work has passed, with a device synchronise around the ho
 With --policy H the three closed-loop ways to run the same K steps of one shared policy (H = 0: affine; else one tanh hidden layer of H
 units) are timed instead, same protocol: K x (torch policy + env.step), K x (env.policy_act + env.step), one env.rollout_policy.
     python tools/rollout_bench.py --policy 32 [--ids PointUMaze-v0,SwimmerUMaze-v0,AntUMaze-v0]
+With --policy H --sample the same K steps with a sampled action each (log_std = -0.5 on every unit): K x (env.policy_sample + env.step),
+one env.rollout_policy_sample, and the deterministic env.rollout_policy at the same shape beside them.
+    python tools/rollout_bench.py --policy 32 --sample
 Kernel durations come from a run of their own:  rocprofv3 --kernel-trace --stats -d <dir> -- python tools/rollout_bench.py --seconds 0.2"""
 import argparse
 import json
@@ -118,6 +121,72 @@ def bench_policy(env_id, n, K, H, seconds, repeats):
             **{name + "_env_steps_per_s": v for name, v in res.items()}}
 
 
+def bench_sample(env_id, n, K, H, seconds, repeats):
+    """K closed-loop steps of one shared Gaussian policy: policy_sample + step, one rollout_policy_sample; the deterministic
+    rollout_policy of the same network as the yardstick."""
+    from mujoco_maze_amd import policy
+
+    dev = torch.device("cuda", 0)
+    env = mm.make(env_id, num_envs=n, auto_reset=True, device=dev, force_vec=True)
+    env.reset(seed=20260928)
+    g = torch.Generator(device=dev).manual_seed(1234)
+
+    def lin(out, fan_in):
+        k = fan_in ** -0.5
+        return (2 * torch.rand((out, fan_in), device=dev, generator=g) - 1) * k, (2 * torch.rand(out, device=dev, generator=g) - 1) * k
+
+    log_std = torch.full((env.nu,), -0.5)
+    if H:
+        (W1, b1), (W2, b2) = lin(H, env.obs_dim), lin(env.nu, H)
+        params = torch.as_tensor(policy.pack(W1, b1, W2, b2, log_std=log_std), device=dev)
+    else:
+        params = torch.as_tensor(policy.pack_linear(*lin(env.nu, env.obs_dim), log_std=log_std), device=dev)
+    det = params[: -env.nu].contiguous()
+
+    def sample_step():
+        for k in range(K):
+            env.step(env.policy_sample(params, hidden=H)[0])
+
+    def fused():
+        env.rollout_policy_sample(params, K, hidden=H)
+
+    def fused_det():
+        env.rollout_policy(det, K, hidden=H)
+
+    legs = (("sample_step", sample_step), ("rollout_policy_sample", fused), ("rollout_policy", fused_det))
+    for _ in range(4):
+        for _, fn in legs:
+            fn()
+    res = {name: [] for name, _ in legs}
+    for _ in range(repeats):
+        for name, fn in legs:
+            w, dt = leg(fn, 4, seconds, dev)
+            res[name].append(n * K * w / dt)
+    bad = int((env.status() & 3).ne(0).sum())
+    fused_flag = env.launch_info()["rollout_fused"]
+    env.close()
+    return {"env": env_id, "envs": n, "steps_per_window": K, "hidden": H, "sample": True, "fused": fused_flag, "flagged_envs": bad,
+            **{name + "_env_steps_per_s": v for name, v in res.items()}}
+
+
+def main_sample(args):
+    out = []
+    med = lambda v: sorted(v)[len(v) // 2]
+    print(f"closed loop, one shared Gaussian policy (hidden {args.policy}, log_std -0.5), {args.steps} steps per window, {args.envs} envs, auto-reset, "
+          f">= {args.seconds} s per leg, {args.repeats} alternating repeats; M env-steps/s, median (max - min)")
+    print("%-18s %5s %24s %24s %24s" % ("env", "fused", "policy_sample + step", "rollout_policy_sample", "rollout_policy (det.)"))
+    for env_id in args.ids.split(","):
+        r = bench_sample(env_id, args.envs, args.steps, args.policy, args.seconds, args.repeats)
+        out.append(r)
+        cell = lambda v: "%10.3f (%6.3f)" % (med(v) / 1e6, (max(v) - min(v)) / 1e6)
+        print("%-18s %5d %24s %24s %24s" % (env_id, r["fused"], cell(r["sample_step_env_steps_per_s"]), cell(r["rollout_policy_sample_env_steps_per_s"]),
+                                            cell(r["rollout_policy_env_steps_per_s"])), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            for r in out:
+                f.write(json.dumps(r) + "\n")
+
+
 def main_policy(args):
     out = []
     med = lambda v: sorted(v)[len(v) // 2]
@@ -145,10 +214,13 @@ def main():
     ap.add_argument("--ids", type=str, default=",".join(IDS))
     ap.add_argument("--out", type=str, default=None, help="also write the rows as JSON lines")
     ap.add_argument("--policy", type=int, default=None, metavar="H", help="closed-loop mode: hidden units of the policy (0 = affine)")
+    ap.add_argument("--sample", action="store_true", help="with --policy: Gaussian policies, a sampled action every step")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "rollout_bench.py measures on the GPU only"
+    if args.sample and args.policy is None:
+        ap.error("--sample goes with --policy H")
     if args.policy is not None:
-        return main_policy(args)
+        return main_sample(args) if args.sample else main_policy(args)
     out = []
     print(f"{args.steps} x env.step against one env.rollout, {args.envs} envs, auto-reset, >= {args.seconds} s per leg, {args.repeats} alternating repeats")
     print("%-18s %5s %14s %10s %14s %10s %7s" % ("env", "fused", "step M/s", "spread", "rollout M/s", "spread", "ratio"))
