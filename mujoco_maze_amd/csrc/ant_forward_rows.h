@@ -523,9 +523,17 @@ __device__ __forceinline__ float ant_forward_rows(const DevCtx<G, PROF>& cx_step
       if (p == 0) s.ncon_true = s.ncon;  // (nothing is merged on this path)
       cx.sync();
     }
+    // the one case where the registers and LDS disagree about the counts: the two-pass enumeration wrote its own.  The whole wave
+    // reads them back (the envs that did not fall back read what their lane 0 stored above, in front of a hand-off)
+    ncon = s.ncon; nblk = NB ? s.nblkcon : 0;
+    // (the wait for them stays in here — behind the join every wave would pay it; the comment marks the fall-back's end in the
+    // kernel's text for tests/test_ant_setup_isa.py)
+    asm volatile("; fall-back counts read back" : "+v"(ncon), "+v"(nblk));
   }
   cx.tick(s, 11);
-  return ant_solve_rows_core<NB, G, PROF, true>(cx, K, s, first, Mrow, qfs, Sax, bsel(m0, qh, qa), bsel(m0, qdh, qda));  // qacc of this lane's dof
+  // the solver takes the contact counts in registers: every lane of the row holds them since the slot compaction.  Read back
+  // from LDS right after the store they were a full round trip (two for the one-block ant) at the head of each of the 20 solves
+  return ant_solve_rows_core<NB, G, PROF, true>(cx, K, s, first, Mrow, qfs, Sax, bsel(m0, qh, qa), bsel(m0, qdh, qda), ncon, nblk);  // qacc of this lane's dof
 }
 
 // One mj_step with RK4 (ant_mj_step of ant_dyn.h) on the quad layout: every dof lane keeps its own velocity, the RK4

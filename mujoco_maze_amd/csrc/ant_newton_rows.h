@@ -463,6 +463,8 @@ __device__ __forceinline__ void contact_record(const AntDev& K, const float* pos
   if (NB == 1 && kind == 2) tran += K.block_bw_tran;
   const float Rr = fmaxf(1e-15f, omi / imp * (tran + P.mu * P.mu * tran));
   rec[7] = 1.0f / (2.f * P.mu * P.mu * Rr);  // [ASSUME-3]
+  // (wr_col's table indexes five bits of this word: legs 0 .. 3 and 7, body classes 0 .. 3 — `cls` of ant_forward_rows.h.  Leg 4 is
+  // WMETA_NONE, the empty slot.  A fifth class or another leg needs a wider table there.)
   rec[15] = __int_as_float((leg < 0 ? 7 : leg) | (cls << 3) | ((NB == 1 && kind == 2) ? 64 : 0));
   rec[23] = 0.f;
 #pragma unroll
@@ -642,10 +644,13 @@ __device__ __forceinline__ void block_rows_direct(const AntDev& K, const AntScra
 // that the wave executes anyway as long as ONE of its lanes needs them.  With one wave per SIMD nobody fills those bubbles: the
 // conditions are gone (the arithmetic adds its zeros), round 4: 0.2941 -> 0.2813 ms.  MZ_IF_OWNER marks the places.
 #define MZ_IF_OWNER(c) if (true)
+enum { WMETA_NONE = 4 };  // wmeta of a slot without a contact: leg 4, which no geom has (wr_col)
 template <int NB, int G, bool PROF, bool WR = false, class SCR>
 __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, const AntDev& K, SCR& s, bool compare,
-                                                    const float (&Mrow)[14 + 2 * NB], const float qfs, const float (&Sax)[6], const float hq, const float hv) {
-  // (hq, hv: angle and velocity of this lane's own hinge, from the forward pass's registers — the limit row reads no LDS)
+                                                    const float (&Mrow)[14 + 2 * NB], const float qfs, const float (&Sax)[6], const float hq, const float hv,
+                                                    const int ncon_in, const int nblk_in) {
+  // (hq, hv: angle and velocity of this lane's own hinge, from the forward pass's registers — the limit row reads no LDS;
+  //  ncon_in, nblk_in: the env's contact counts, what s.ncon / s.nblkcon hold, in the registers of every lane of the row)
   static_assert(G >= 16, "one DPP row per env at least");
   static_assert(NB <= 1, "one 16-lane row holds 14 dofs + one block's two slides");
   using namespace rows;
@@ -668,9 +673,12 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
   const int r = cx.l & 15;                       // position of this lane (rows::pos2dof); beyond NR: spare lanes (zero rows, never pivots)
   const bool isdof = r < NR, ishinge = (r & 3) < 2 && r < 14;
   const int leg = r >> 2, d = r & 1;              // hinge lanes: own leg, 0 hip / 1 ankle
-  const int nB = NB ? s.nblkcon : 0;             // block-own contacts: slots [0, nB)
-  int nA = s.ncon - nB;                          // robot contacts: slots [nB, ncon), owned by the lanes 0 .. nA - 1 of the row
-  if (nA > 16 * MA) { nA = 16 * MA; if (cx.l == 0) s.status |= MZ_STATUS_CONTACT_OVERFLOW; }
+  const int nB = NB ? nblk_in : 0;               // block-own contacts: slots [0, nB)
+  int nA = ncon_in - nB;                         // robot contacts: slots [nB, ncon), owned by the lanes 0 .. nA - 1 of the row
+  // (every writer of s.ncon caps it at NC — the slot compaction of ant_forward_rows.h, con_count_item / con_fill_item of the fall-back
+  // — so with NC <= 16 MA, which holds for both robots that come here, no robot contact is without an owner lane and the test
+  // compiles away: compare, exec-mask region and the status word's read-modify-write, at the head of every solve)
+  if (D::NC > 16 * MA && nA > 16 * MA) { nA = 16 * MA; if (cx.l == 0) s.status |= MZ_STATUS_CONTACT_OVERFLOW; }
   if (NB && MB * BW < nB && cx.l == 0) s.status |= MZ_STATUS_CONTACT_OVERFLOW;  // block contacts without an owner lane (robot slots still start at nB)
   auto bsum = [&](float x) { if constexpr (WR) return rsum(x); else return cx.gsum(x); };
   const int ncon = nA;
@@ -698,7 +706,7 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
       laref = -K.lim_B * (lsign * hv) - K.lim_K * imp * pos;  // (the limit's constants held in registers as well, tried: 0.2453 -> 0.2477 ms)
     }
   }
-  const bool has = s.ncon > 0 || cx.gany(lsign != 0.f);
+  const bool has = ncon_in > 0 || cx.gany(lsign != 0.f);
   // qacc_smooth = M^-1 qfrc_smooth by the same row elimination — only where it is used: on the first evaluation of a step
   // (MuJoCo's warm-start rule compares against it) and for an env without any constraint (then it is the answer).  The
   // Newton iteration itself works on M qacc - qfrc_smooth and never needs it.  (Round 5, tried: an unconstrained env through the
@@ -716,9 +724,9 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
   // own robot contact: 3 x (NHC + 2) Jacobian rows stay in LDS (row-major, read as needed); constants in registers
   float cD[MA], ar[MA][3];
   float wr[MA][3][6];  // WR: the own contacts' three wrenches each
-  int wmeta[MA];       // WR: leg (7: none) | body class << 3 | 64 if the touching geom's partner is the movable block
+  int wmeta[MA];       // WR: leg (7: none) | body class << 3 | 64 if the touching geom's partner is the movable block; WMETA_NONE: no contact in the slot
 #pragma unroll
-  for (int m = 0; m < MA; m++) wmeta[m] = 0;
+  for (int m = 0; m < MA; m++) wmeta[m] = WR ? WMETA_NONE : 0;
   if constexpr (WR) {
 #pragma unroll
     for (int m = 0; m < MA; m++) {
@@ -731,6 +739,9 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
       cD[m] = 0.f;
       if (m == 1 && !any2) continue;
       // the slot's staged contact (contact_raw_store) -> its 24-float record, here on the lane that owns it
+      // (Issuing these reads at the top of the set-up, under the limit row, was built and measured: 0.2172 -> 0.2129 ms, but the
+      // compiler then packs and contracts contact_record's cross products differently, through opaque registers as well, and
+      // every env's result moves in the last bits.  Not taken: profiles/solve_setup/ab.md.)
       const float4* q = reinterpret_cast<const float4*>(wr_record(s, cr[m]));
       float raw[20];
 #pragma unroll
@@ -747,7 +758,7 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
         ar[m][a] = __int_as_float(__float_as_int(rec[8 * a + 6]) & on);
       }
       cD[m] = __int_as_float(__float_as_int(rec[7]) & on);
-      wmeta[m] = __float_as_int(rec[15]) & on;
+      wmeta[m] = (__float_as_int(rec[15]) & on) | (WMETA_NONE & ~on);
     }
   } else {
 #pragma unroll
@@ -822,15 +833,25 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
   // owner's wrenches where they are used (own_col below)
   constexpr int NJ = WR ? 16 : 16 * MA;
   float jown[NJ][3];
+  // Which contacts this lane's dof sees, as a bit per (leg | class << 3) of the touching geom (classes 0 .. 3: five index bits): a
+  // hip the geoms of its own leg below it (classes 2 aux, 3 ankle), an ankle its own ankle body, a root dof every geom (legs 0 .. 3
+  // and 7: none), the spare and the block's slide lanes none (the latter see, through seesblk, the contacts whose partner is the
+  // block).  No real record has leg 4, so WMETA_NONE — what an empty slot's owner broadcasts — reads a zero bit in every table
+  // and stands for `C < ncon`.  Lane constants: the compiler builds them once per step.
+  const unsigned seestab = ishinge ? ((1u << (24 + leg)) | (d == 0 ? 1u << (16 + leg) : 0u)) : (r < 12 ? 0xefefefefu : 0u);
+  const int seesblk = -(int)(NB == 1 && r >= 14 && r < 16);
   auto wr_col = [&](auto Cc, float (&o)[3]) {  // S_p . wrench_a of contact C, masked by "dof p moves the touching body"
     constexpr int C = decltype(Cc)::value;
     // S_p . wrench_a of contact C (its owner: lane C of the row), for the dofs that move the touching body: the root always, a hip
     // when the geom sits on its leg below it (aux, ankle body), an ankle for its own ankle body.  (The movable block's two slide
     // lanes carry MINUS their axis in Sax: a robot -> block contact pushes the block with the reaction of what the record holds
     // for the robot.)
-    const int mc = bcast_i<(C & 15)>(wmeta[C / 16]), lc = mc & 7, cc = (mc >> 3) & 7;
-    const bool sees = C < ncon && (ishinge ? (leg == lc && (d == 0 ? cc >= 2 : cc == 3)) : (r < 12 || (NB == 1 && r >= 14 && (mc & 64) != 0)));
-    const int on = -(int)sees;
+    // `sees` is one bit of the lane's table (seestab above), picked by the owner's leg | class << 3: a shift and a sign extension.
+    // (As the condition spelled out — C < ncon && (ishinge ? leg == lc && (d == 0 ? cc >= 2 : cc == 3) : r < 12 || block) — it was
+    // an exec-mask region per slot: 23 scalar and vector instructions and two branches around the 20 of the products.)
+    const int mc = bcast_i<(C & 15)>(wmeta[C / 16]);
+    int on = -(int)((seestab >> (mc & 31)) & 1u);
+    if constexpr (NB == 1) on |= seesblk & -((mc >> 6) & 1);
     float dots[3];
     dot6x3_from<(C & 15)>(wr[C / 16], Sax, dots);
 #pragma unroll
