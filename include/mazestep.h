@@ -320,7 +320,10 @@ int32_t mz_bind_env_goals(mz_handle* h, const double* goal_pos_dev, void* stream
  * from the reference's reset distribution (counter-based RNG keyed by seed and
  * env slot; streams differ from numpy's — distributional parity only).
  * obs_dev [N, obs_dim] may be NULL.  Rows of envs the mask leaves alone are written too, from their present state and t: with an
- * all-zero mask the call resets nothing and returns every env's current observation (e.g. after mz_set_state). */
+ * all-zero mask the call resets nothing and returns every env's current observation (e.g. after mz_set_state).
+ * The call stores `seed` in the handle for ALL envs and zeroes the episode count of the masked ones only.  So from here on the k-th
+ * in-step auto-reset of a masked env draws from episode_seed(seed, k) (csrc/mz_rng.h), and an env the mask left alone keeps its
+ * episode count e and draws its next one from episode_seed(seed, e + 1): the new seed with the old count. */
 int32_t mz_reset(mz_handle* h, const uint8_t* mask_dev, uint64_t seed, float* obs_dev, void* stream);
 
 /* State injection / read-back (row-major [N, nq], [N, nv], [N, nv], [N]).

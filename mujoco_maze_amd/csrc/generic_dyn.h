@@ -1553,9 +1553,11 @@ template <class Q>
 MZ_HD double gen_body_origin(const mz_model& m, const Q* qpos, int body, int c) {
   const int j0 = m.body_jntadr[body], jn = m.body_jntnum[body];
   if (jn == 1 && m.jnt_type[j0] == MZ_JNT_FREE) return (double)qpos[m.jnt_qposadr[j0] + c];
+  // the slide as the fp32 state record keeps it, also where the step holds it in float64: the row a step returns is a function of the
+  // state it stores, and generic_reset_kernel, which has only the record, writes the same bits for an env its mask leaves alone
   double p = m.body_pos[body][c];
   for (int j = j0; j < j0 + jn; j++)
-    if (m.jnt_type[j] == MZ_JNT_SLIDE) p += m.jnt_axis[j][c] * ((double)qpos[m.jnt_qposadr[j]] - m.qpos0[m.jnt_qposadr[j]]);
+    if (m.jnt_type[j] == MZ_JNT_SLIDE) p += m.jnt_axis[j][c] * ((double)(float)qpos[m.jnt_qposadr[j]] - m.qpos0[m.jnt_qposadr[j]]);
   return p;
 }
 // element i of the observation WITHOUT the view: robot qpos[:3] | object balls' xpos | movable blocks' xpos (3 each, if observed) |

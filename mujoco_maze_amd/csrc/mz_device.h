@@ -167,6 +167,4 @@ __device__ __forceinline__ float reset_qvel(int kind, int nq, uint64_t seed, uin
   if (kind == 1) return 0.1f * rng_u01(seed, env, c);
   return -0.1f + 0.2f * rng_u01(seed, env, c);
 }
-__host__ __device__ __forceinline__ uint64_t episode_seed(uint64_t seed, uint32_t episode) {
-  return episode == 0 ? seed : mix64(seed ^ (0xD6E8FEB86659FD93ULL * (uint64_t)episode));
-}
+// episode_seed: mz_rng.h

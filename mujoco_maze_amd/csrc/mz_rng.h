@@ -20,3 +20,8 @@ MZ_RNG_HD uint32_t rng_u32(uint64_t seed, uint64_t env, uint32_t counter) {
   z = mix64(z + 0x9E3779B97F4A7C15ULL * ((uint64_t)counter + 1));
   return (uint32_t)(z >> 32);
 }
+// the seed an env's episode draws its reset state from: the handle's seed for episode 0 (what mz_reset draws), a mix of seed and
+// episode count for every in-step auto-reset after it
+MZ_RNG_HD uint64_t episode_seed(uint64_t seed, uint32_t episode) {
+  return episode == 0 ? seed : mix64(seed ^ (0xD6E8FEB86659FD93ULL * (uint64_t)episode));
+}

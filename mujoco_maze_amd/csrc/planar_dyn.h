@@ -942,13 +942,17 @@ MZP_HD void planar_env_step(const C& cx, const PointDev& P, PlanarScratch<NB, NS
   }
 }
 
+// A body origin as it is observed: spawn coordinate + slide, with the slide rounded to fp32 first — the value the state record
+// keeps.  So the row a step returns is a function of the state it stores, and point_reset_kernel, which has only that record,
+// writes the same bits for an env its mask leaves alone (tests/test_gpu_reset_parity.py).
+MZP_HD float planar_origin_coord(double pos0, double slide) { return (float)(pos0 + (double)(float)slide); }
+
 // coordinate c of movable block b's body origin (get_body_com, maze_env.py:364-368): spawn position + its two slides
 template <int NB, int NS>
 MZP_HD float planar_block_coord(const PointDev& P, const PlanarScratch<NB, NS>& s, int b, int c) {
-  double v = P.block_pos0[b][c];
-  if (c == P.block_axis[0]) v += s.q[3 + 2 * b];
-  if (c == P.block_axis[1]) v += s.q[4 + 2 * b];
-  return (float)v;
+  if (c == P.block_axis[0]) return planar_origin_coord(P.block_pos0[b][c], s.q[3 + 2 * b]);
+  if (c == P.block_axis[1]) return planar_origin_coord(P.block_pos0[b][c], s.q[4 + 2 * b]);
+  return (float)P.block_pos0[b][c];
 }
 
 // observation element i of the returned row: qpos[:3] | ball xyz | block xyz ... | qvel[:3] | t * 0.001  (maze_env.py:351-369)
@@ -957,7 +961,7 @@ MZP_HD float planar_obs_elem(const PointDev& P, const PlanarScratch<NB, NS>& s, 
   int nb3 = (P.observe_blocks ? 3 * NB : 0) + (P.observe_balls ? 3 * NS : 0);
   if (i < 3) return (float)s.q[i];
   if constexpr (NS > 0) {
-    if (i < 3 + nb3) return (float)(i == 5 ? P.ball_pos0[2] : P.ball_pos0[i - 3] + s.q[i]);  // body frame origin: z = 0
+    if (i < 3 + nb3) return i == 5 ? (float)P.ball_pos0[2] : planar_origin_coord(P.ball_pos0[i - 3], s.q[i]);  // body frame origin: z = 0
   }
   if (i < 3 + nb3) return planar_block_coord<NB, NS>(P, s, (i - 3) / 3, (i - 3) % 3);
   if (i < 6 + nb3) return (float)s.v[i - 3 - nb3];

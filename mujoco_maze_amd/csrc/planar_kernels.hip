@@ -373,21 +373,21 @@ __global__ void point_reset_kernel(const PointDev* Pp, int n, PointState S, cons
     const int nb3 = (Pp->observe_blocks ? 3 * NB : 0) + (Pp->observe_balls ? 3 * NS : 0);
     float* o = obs + (size_t)env * ostride;
     for (int k = 0; k < 3; k++) { o[k] = st_q(S, n, NV, k, env); o[3 + nb3 + k] = st_v(S, n, NV, k, env); }
+    // body origins exactly as the step kernels observe them (planar_origin_coord): the row of an env the mask leaves alone keeps
+    // the bits the last step wrote
     if (NS > 0 && nb3) {
-      o[3] = (float)Pp->ball_pos0[0] + st_q(S, n, NV, 3, env); o[4] = (float)Pp->ball_pos0[1] + st_q(S, n, NV, 4, env);
+      o[3] = planar_origin_coord(Pp->ball_pos0[0], st_q(S, n, NV, 3, env)); o[4] = planar_origin_coord(Pp->ball_pos0[1], st_q(S, n, NV, 4, env));
       o[5] = (float)Pp->ball_pos0[2];
     }
     for (int b = 0; b < NB && nb3; b++) {
       float p3[3] = {(float)Pp->block_pos0[b][0], (float)Pp->block_pos0[b][1], (float)Pp->block_pos0[b][2]};
-      p3[Pp->block_axis[0]] += st_q(S, n, NV, 3 + 2 * b, env);
-      p3[Pp->block_axis[1]] += st_q(S, n, NV, 4 + 2 * b, env);
+      for (int a = 0; a < 2; a++) p3[Pp->block_axis[a]] = planar_origin_coord(Pp->block_pos0[b][Pp->block_axis[a]], st_q(S, n, NV, 3 + a + 2 * b, env));
       o[3 + 3 * b] = p3[0]; o[4 + 3 * b] = p3[1]; o[5 + 3 * b] = p3[2];
     }
     if (ostride != NOBS)  // top-down view: block x, y parked for mzk_view_fill, time entry behind the view
       for (int b = 0; b < NB; b++) {
         float p3[3] = {(float)Pp->block_pos0[b][0], (float)Pp->block_pos0[b][1], (float)Pp->block_pos0[b][2]};
-        p3[Pp->block_axis[0]] += st_q(S, n, NV, 3 + 2 * b, env);
-        p3[Pp->block_axis[1]] += st_q(S, n, NV, 4 + 2 * b, env);
+        for (int a = 0; a < 2; a++) p3[Pp->block_axis[a]] = planar_origin_coord(Pp->block_pos0[b][Pp->block_axis[a]], st_q(S, n, NV, 3 + a + 2 * b, env));
         o[NOBS - 1 + 2 * b] = p3[0]; o[NOBS + 2 * b] = p3[1];
       }
     o[ostride - 1] = (float)st_t(S, NV, env) * 0.001f;

@@ -13,6 +13,9 @@ void mzp_host_noise_words(unsigned long long key, unsigned long long slot, int u
   words[1] = rng_u32(key, slot, 2u * (uint32_t)u + 1u);
 }
 
+// the seed of an env's episode (mz_rng.h): what every reset kernel and every in-step auto-reset keys its draws by
+unsigned long long mzp_host_episode_seed(unsigned long long seed, unsigned int episode) { return episode_seed(seed, episode); }
+
 float mzp_host_eps(unsigned long long noise_seed, unsigned long long noise_step, unsigned long long slot, int u) {
   return mzp_eps(mzp_noise_key(noise_seed, noise_step), slot, u);
 }
