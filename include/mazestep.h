@@ -448,6 +448,61 @@ int32_t mz_rollout_policy_sample(mz_handle* h, int32_t n_steps, const float* par
                                  float* reward_dev, uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev, float* obs_seq_dev,
                                  float* actions_seq_dev, float* logp_seq_dev, void* stream);
 
+/* A critic on the device, and generalised advantage estimation (actor-critic data collection: PPO, A2C, REINFORCE with a baseline).
+ *
+ * A critic is a policy as above with nu = 1, never squashed, in a parameter vector of its own: hidden == 0 affine, 1 <= hidden <=
+ * MZ_POLICY_MAX_HIDDEN one tanh hidden layer, nvpar = obs_dim * Hv + Hv + Hv + 1 (or obs_dim + 1) fp32 numbers, input-major;
+ * vparams_dev [nvpar] (env_stride == 0) or [N, nvpar] (env_stride == nvpar); any other stride is MZ_ERR_ARG.  The value of a row is
+ * the pre-squash sum of its one output unit, in the arithmetic of the policies (one lane per unit, serially, fp32, no contraction):
+ * numpy reproduces the affine case bit for bit.  NaN in one env's critic parameters reaches that env's values only.
+ *
+ * mz_value: values_dev [N] = V(obs_dev [N, obs_dim]).
+ *
+ * mz_rollout_actor_critic: mz_rollout_policy (sample == 0: noise_seed, noise_step and logp_seq_dev are ignored) or
+ * mz_rollout_policy_sample (sample == 1) with the critic evaluated where the observation rows sit.  The defining loop — the call leaves
+ * the handle and every output as these calls on the same stream would leave them, bit for bit:
+ *     for k in 0 .. n_steps - 1:
+ *         value_seq[k]      = mz_value(obs_dev)
+ *         a_k               = sample ? mz_policy_sample(noise_step + k, obs_dev) : mz_policy_act(obs_dev)
+ *         mz_step(a_k -> obs_dev, row k of the outputs)
+ *         next_value_seq[k][i] = (auto_reset && done[k][i]) ? mz_value(row i of the bound final_obs) : mz_value(row i of obs_dev)
+ * so next_value_seq[k] is the value of the row step k produced BEFORE any auto-reset — for an env that finished, of its terminal
+ * observation, which a learner needs to bootstrap a time-limit truncation (done & 2) —, and equals value_seq[k + 1] wherever
+ * done[k] == 0.  With critic == NULL the call IS mz_rollout_policy / mz_rollout_policy_sample.  A critic cannot influence the
+ * rollout: actions, state, rewards, dones and status words are those of the call without it.  Handles with "rollout_fused" = 1
+ * evaluate the critic inside the fused rollout kernels (on the terminal row before the auto-reset overwrites it, once more on the new
+ * episode's first row); every other handle runs the loop above inside the call.
+ * MZ_ERR_ARG, with a message that names the argument: sample outside {0, 1}; with a non-NULL critic: NULL critic->params_dev,
+ * critic->hidden outside 0 .. MZ_POLICY_MAX_HIDDEN, critic->env_stride neither 0 nor nvpar, critic->reserved != 0, and
+ * critic->next_value_seq_dev requested with auto-reset on and no final_obs buffer bound (mz_bind_final_obs) — on every handle, so
+ * that the contract does not depend on the engine; and everything mz_rollout_policy / mz_rollout_policy_sample refuse.
+ *
+ * mz_gae: advantages and returns from the [n_steps, N] rows of a rollout, one backward scan per env, k from n_steps - 1 down to 0,
+ * carry = 0 at the start; fp32 throughout, every operation rounded separately; selects, not multiplications by a mask, so a NaN
+ * bootstrap value behind a true termination cannot leak (csrc/mz_gae.h):
+ *     g = (float)gamma;  gl = g * (float)lam
+ *     b     = (done & 1) ? 0.0f : g * next_value       true termination: no bootstrap; a time limit alone (done == 2) bootstraps from
+ *     delta = (reward + b) - value                     the terminal observation's value
+ *     c     = done ? 0.0f : gl * carry                 any episode end cuts the recursion
+ *     adv   = delta + c;  carry = adv;  ret = adv + value
+ * adv_dev [n_steps, N]; ret_dev [n_steps, N] (nullable).  n_steps 1 .. 65536.  Returns MZ_OK, MZ_ERR_ARG or MZ_ERR_HIP. */
+typedef struct mz_critic {
+  const float* params_dev;
+  int64_t env_stride;
+  int32_t hidden;
+  int32_t reserved;          /* 0 */
+  float* value_seq_dev;      /* [n_steps, N]  V(the row the policy acted on at step k)            (nullable) */
+  float* next_value_seq_dev; /* [n_steps, N]  V(the row step k produced, BEFORE any auto-reset)   (nullable) */
+} mz_critic;
+int32_t mz_value(mz_handle* h, const float* vparams_dev, int64_t env_stride, int32_t hidden, const float* obs_dev, float* values_dev,
+                 void* stream);
+int32_t mz_rollout_actor_critic(mz_handle* h, int32_t n_steps, const float* params_dev, int64_t param_env_stride, int32_t hidden,
+                                int32_t squash, double action_scale, int32_t sample, uint64_t noise_seed, uint64_t noise_step,
+                                const mz_critic* critic, float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t* goal_idx_dev,
+                                float* info_dev, float* obs_seq_dev, float* actions_seq_dev, float* logp_seq_dev, void* stream);
+int32_t mz_gae(mz_handle* h, int32_t n_steps, const float* reward_dev, const uint8_t* done_dev, const float* value_dev,
+               const float* next_value_dev, double gamma, double lam, float* adv_dev, float* ret_dev, void* stream);
+
 /* Per-env status words accumulated since the last call (then cleared). [N] i32. */
 int32_t mz_get_status(mz_handle* h, int32_t* status_dev, void* stream);
 

@@ -23,7 +23,15 @@ SYMBOLS = [
     "mz_debug_forward", "mz_last_kernel_ms", "mz_read_phase_cycles", "mz_bind_final_obs", "mz_debug_task_eval", "mz_debug_detect", "mz_read_wave_cycles", "mz_bind_record",
     "mz_set_goals", "mz_read_wave_phase_cycles", "mz_get_info", "mz_bind_env_goals", "mz_render", "mz_rollout",
     "mz_policy_act", "mz_rollout_policy", "mz_policy_sample", "mz_rollout_policy_sample",
+    "mz_value", "mz_rollout_actor_critic", "mz_gae",
 ]
+
+
+class MzCritic(C.Structure):
+    """`mz_critic` of include/mazestep.h: the critic of one mz_rollout_actor_critic call."""
+    _fields_ = [("params_dev", C.c_void_p), ("env_stride", C.c_int64), ("hidden", C.c_int32), ("reserved", C.c_int32),
+                ("value_seq_dev", C.c_void_p), ("next_value_seq_dev", C.c_void_p)]
+
 
 _lib = None
 
@@ -86,6 +94,13 @@ def load():
     lib.mz_policy_sample.argtypes = [vp, vp, C.c_int64, i32, i32, C.c_double, u64, u64, vp, vp, vp, vp]
     lib.mz_rollout_policy_sample.restype = i32
     lib.mz_rollout_policy_sample.argtypes = [vp, i32, vp, C.c_int64, i32, i32, C.c_double, u64, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.mz_value.restype = i32
+    lib.mz_value.argtypes = [vp, vp, C.c_int64, i32, vp, vp, vp]
+    lib.mz_rollout_actor_critic.restype = i32
+    lib.mz_rollout_actor_critic.argtypes = [vp, i32, vp, C.c_int64, i32, i32, C.c_double, i32, u64, u64, C.POINTER(MzCritic), vp, vp, vp, vp, vp, vp,
+                                            vp, vp, vp]
+    lib.mz_gae.restype = i32
+    lib.mz_gae.argtypes = [vp, i32, vp, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp]
     lib.mz_get_status.restype = i32
     lib.mz_get_status.argtypes = [vp, vp, vp]
     lib.mz_debug_forward.restype = i32

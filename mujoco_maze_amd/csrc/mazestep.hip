@@ -8,6 +8,7 @@
 
 #include <new>
 
+#include "mz_gae.h"
 #include "mz_internal.h"
 #include "mz_policy.h"
 #include "mz_render.h"
@@ -61,6 +62,56 @@ __global__ __launch_bounds__(256) void policy_sample_kernel(int n, int obs_dim, 
   if (!live) row = (size_t)n - 1;
   mzp_group_sample(l, MZ_POLICY_LANES, params + row * pstride, obs_dim, nu, hidden, squash, action_scale, key, env0 + row, obs + row * obs_dim,
                    hid[grp], actions + row * nu, live, live && logp ? logp + row : nullptr);
+}
+
+// values[r] = V(obs[r]) for n rows (mz_value; mz_rollout_actor_critic where it steps launch by launch): the critic of mz_policy.h on
+// the groups of policy_act_kernel — lanes l, l + 16, .. own hidden units, the group's first lane the output.  With `done` (the step
+// under auto-reset) row r is taken from final_obs where done[r] != 0: the terminal row, which obs no longer holds.
+__global__ __launch_bounds__(256) void value_kernel(int n, int obs_dim, int hidden, const float* __restrict__ vparams, long vstride,
+                                                    const float* __restrict__ obs, const float* __restrict__ final_obs,
+                                                    const uint8_t* __restrict__ done, float* __restrict__ values) {
+  __shared__ float hid[256 / MZ_POLICY_LANES][MZ_POLICY_MAX_HIDDEN];
+  const int l = (int)threadIdx.x % MZ_POLICY_LANES, grp = (int)threadIdx.x / MZ_POLICY_LANES;
+  size_t row = (size_t)blockIdx.x * (256 / MZ_POLICY_LANES) + grp;
+  const bool live = row < (size_t)n;
+  if (!live) row = (size_t)n - 1;
+  const float* x = (done && done[row] ? final_obs : obs) + row * obs_dim;
+  const float v = mzp_group_value(l, MZ_POLICY_LANES, vparams + row * vstride, obs_dim, hidden, x, hid[grp]);
+  if (live && l == 0) values[row] = v;
+}
+
+// mz_gae: one lane per env, rows [k][env] coalesced across the lanes; the scan of mz_gae.h (mzg_step) from the last step back.  The
+// four loads of a step do not depend on the carry: a block of MZ_GAE_DEPTH steps is loaded before its dependent chain runs.
+constexpr int MZ_GAE_DEPTH = 8;
+__global__ __launch_bounds__(64) void gae_kernel(int n, int nsteps, const float* __restrict__ reward, const uint8_t* __restrict__ done,
+                                                 const float* __restrict__ value, const float* __restrict__ next_value, float g, float gl,
+                                                 float* __restrict__ adv, float* __restrict__ ret) {
+  const int env = blockIdx.x * blockDim.x + threadIdx.x;
+  if (env >= n) return;
+  float carry = 0.0f;
+  for (int k1 = nsteps - 1; k1 >= 0; k1 -= MZ_GAE_DEPTH) {
+    float r[MZ_GAE_DEPTH], v[MZ_GAE_DEPTH], nv[MZ_GAE_DEPTH];
+    uint8_t d[MZ_GAE_DEPTH];
+#pragma unroll
+    for (int j = 0; j < MZ_GAE_DEPTH; j++) {
+      const int k = k1 - j;
+      if (k >= 0) {
+        const size_t i = (size_t)k * n + env;
+        r[j] = reward[i]; d[j] = done[i]; v[j] = value[i]; nv[j] = next_value[i];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < MZ_GAE_DEPTH; j++) {
+      const int k = k1 - j;
+      if (k >= 0) {
+        const size_t i = (size_t)k * n + env;
+        float rt;
+        carry = mzg_step(r[j], d[j], v[j], nv[j], g, gl, carry, &rt);
+        adv[i] = carry;
+        if (ret) ret[i] = rt;
+      }
+    }
+  }
 }
 
 static int set_err(mz_handle* h, int code, const char* what, hipError_t e) {
@@ -592,6 +643,117 @@ int32_t mz_rollout_policy_sample(mz_handle* h, int32_t n_steps, const float* par
     }
   }
   h->nsteps += n_steps;
+  return MZ_OK;
+}
+
+// the checks mz_value and mz_rollout_actor_critic share: a critic is a policy with nu = 1 in a vector of its own
+static int critic_args(mz_handle* h, const char* who, const float* vparams_dev, int64_t env_stride, int32_t hidden) {
+  char msg[160];
+  const char* why = nullptr;
+  if (!vparams_dev) why = "null critic parameters (params_dev)";
+  else if (hidden < 0 || hidden > MZ_POLICY_MAX_HIDDEN) why = "the critic's hidden must be 0 .. MZ_POLICY_MAX_HIDDEN (64)";
+  else if (env_stride != 0 && env_stride != (int64_t)mzp_param_count(h->model.obs_dim, 1, hidden))
+    why = "the critic's env_stride must be 0 (one shared critic) or nvpar (one critic per env)";
+  if (!why) return MZ_OK;
+  snprintf(msg, sizeof(msg), "%s: %s", who, why);
+  return set_err(h, MZ_ERR_ARG, msg, hipSuccess);
+}
+
+static void value_launch(mz_handle* h, hipStream_t st, const float* vparams_dev, int64_t vstride, int hidden, const float* obs_dev,
+                         const float* final_obs_dev, const uint8_t* done_dev, float* values_dev) {
+  const int rows = 256 / MZ_POLICY_LANES;
+  hipLaunchKernelGGL(value_kernel, dim3((unsigned)((h->n + rows - 1) / rows)), dim3(256), 0, st, h->n, h->model.obs_dim, hidden, vparams_dev,
+                     (long)vstride, obs_dev, final_obs_dev, done_dev, values_dev);
+}
+
+int32_t mz_value(mz_handle* h, const float* vparams_dev, int64_t env_stride, int32_t hidden, const float* obs_dev, float* values_dev,
+                 void* stream) {
+  if (!h) return MZ_ERR_ARG;
+  if (!obs_dev || !values_dev) return set_err(h, MZ_ERR_ARG, "mz_value: null array", hipSuccess);
+  const int rc = critic_args(h, "mz_value", vparams_dev, env_stride, hidden);
+  if (rc != MZ_OK) return rc;
+  DeviceScope scope(h->device);
+  value_launch(h, (hipStream_t)stream, vparams_dev, env_stride, hidden, obs_dev, NULL, NULL, values_dev);
+  HIPCHK(h, hipGetLastError());
+  return MZ_OK;
+}
+
+// mz_rollout_policy / mz_rollout_policy_sample with a critic evaluated where the rows sit (include/mazestep.h).  Without a critic the
+// call IS one of those two.  Fused handles evaluate the critic inside the rollout kernels (planar_kernels.hip, CRT); every other
+// handle runs the defining loop itself: value_kernel, the policy's kernel, the step's own launches — mzk_view_fill among them, so the
+// view entries of both rows are in place —, then value_kernel again with the final_obs row where the env finished under auto-reset.
+int32_t mz_rollout_actor_critic(mz_handle* h, int32_t n_steps, const float* params_dev, int64_t param_env_stride, int32_t hidden, int32_t squash,
+                                double action_scale, int32_t sample, uint64_t noise_seed, uint64_t noise_step, const mz_critic* critic,
+                                float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev, float* obs_seq_dev,
+                                float* actions_seq_dev, float* logp_seq_dev, void* stream) {
+  if (!h) return MZ_ERR_ARG;
+  if (sample != 0 && sample != 1) return set_err(h, MZ_ERR_ARG, "mz_rollout_actor_critic: sample must be 0 or 1", hipSuccess);
+  if (!critic)
+    return sample ? mz_rollout_policy_sample(h, n_steps, params_dev, param_env_stride, hidden, squash, action_scale, noise_seed, noise_step, obs_dev,
+                                             reward_dev, done_dev, goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, logp_seq_dev, stream)
+                  : mz_rollout_policy(h, n_steps, params_dev, param_env_stride, hidden, squash, action_scale, obs_dev, reward_dev, done_dev,
+                                      goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, stream);
+  if (!obs_dev || !reward_dev || !done_dev) return set_err(h, MZ_ERR_ARG, "mz_rollout_actor_critic: null array", hipSuccess);
+  if (n_steps < 1 || n_steps > 65536) return set_err(h, MZ_ERR_ARG, "mz_rollout_actor_critic: n_steps must be 1 .. 65536", hipSuccess);
+  int rc = policy_args(h, "mz_rollout_actor_critic", params_dev, param_env_stride, hidden, squash, sample != 0);
+  if (rc != MZ_OK) return rc;
+  if (critic->reserved != 0) return set_err(h, MZ_ERR_ARG, "mz_rollout_actor_critic: critic->reserved must be 0", hipSuccess);
+  rc = critic_args(h, "mz_rollout_actor_critic", critic->params_dev, critic->env_stride, critic->hidden);
+  if (rc != MZ_OK) return rc;
+  if (critic->next_value_seq_dev && h->auto_reset && !h->final_obs)
+    return set_err(h, MZ_ERR_ARG, "mz_rollout_actor_critic: critic->next_value_seq_dev under auto-reset needs a bound final_obs buffer "
+                                  "(mz_bind_final_obs): the terminal rows are valued there", hipSuccess);
+  const size_t n = (size_t)h->n, od = (size_t)h->model.obs_dim, nu = (size_t)h->model.nu;
+  const float scale = (float)action_scale;
+  if (!sample) logp_seq_dev = NULL;
+  DeviceScope scope(h->device);
+  hipStream_t st = (hipStream_t)stream;
+  if (mzk_planar_rollout_fused(h)) {
+    HIPCHK(h, mzk_planar_rollout_actor_critic(h, st, n_steps, params_dev, (long)param_env_stride, hidden, squash, scale, sample, noise_seed, noise_step,
+                                              critic, obs_dev, reward_dev, done_dev, goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, logp_seq_dev));
+    if (h->record) {  // the last step's row
+      const size_t tot = n * (od + 2), last = (size_t)(n_steps - 1) * n;
+      hipLaunchKernelGGL(pack_record_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, h->n, h->model.obs_dim, obs_dev, reward_dev + last, done_dev + last, h->record);
+      HIPCHK(h, hipGetLastError());
+    }
+  } else {
+    if (!actions_seq_dev && !h->policy_act) HIPCHK(h, hipMalloc(&h->policy_act, n * nu * sizeof(float)));
+    for (size_t k = 0; k < (size_t)n_steps; k++) {
+      float* a = actions_seq_dev ? actions_seq_dev + k * n * nu : h->policy_act;
+      if (critic->value_seq_dev)
+        value_launch(h, st, critic->params_dev, critic->env_stride, critic->hidden, obs_dev, NULL, NULL, critic->value_seq_dev + k * n);
+      if (sample)
+        policy_sample_launch(h, st, params_dev, param_env_stride, hidden, squash, scale, noise_seed, noise_step + k, obs_dev, a,
+                             logp_seq_dev ? logp_seq_dev + k * n : NULL);
+      else
+        policy_act_launch(h, st, params_dev, param_env_stride, hidden, squash, scale, obs_dev, a);
+      HIPCHK(h, hipGetLastError());
+      rc = step_launches(h, st, a, obs_dev, reward_dev + k * n, done_dev + k * n, goal_idx_dev ? goal_idx_dev + k * n : NULL,
+                         info_dev ? info_dev + k * n * 4 : NULL);
+      if (rc != MZ_OK) return rc;
+      if (critic->next_value_seq_dev) {
+        value_launch(h, st, critic->params_dev, critic->env_stride, critic->hidden, obs_dev, h->auto_reset ? h->final_obs : NULL,
+                     h->auto_reset ? done_dev + k * n : NULL, critic->next_value_seq_dev + k * n);
+        HIPCHK(h, hipGetLastError());
+      }
+      if (obs_seq_dev) HIPCHK(h, hipMemcpyAsync(obs_seq_dev + k * n * od, obs_dev, n * od * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
+  }
+  h->nsteps += n_steps;
+  return MZ_OK;
+}
+
+int32_t mz_gae(mz_handle* h, int32_t n_steps, const float* reward_dev, const uint8_t* done_dev, const float* value_dev,
+               const float* next_value_dev, double gamma, double lam, float* adv_dev, float* ret_dev, void* stream) {
+  if (!h) return MZ_ERR_ARG;
+  if (!reward_dev || !done_dev || !value_dev || !next_value_dev || !adv_dev) return set_err(h, MZ_ERR_ARG, "mz_gae: null array", hipSuccess);
+  if (n_steps < 1 || n_steps > 65536) return set_err(h, MZ_ERR_ARG, "mz_gae: n_steps must be 1 .. 65536", hipSuccess);
+  float g, gl;
+  mzg_coeffs(gamma, lam, &g, &gl);
+  DeviceScope scope(h->device);
+  hipLaunchKernelGGL(gae_kernel, dim3((unsigned)((h->n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, h->n, n_steps, reward_dev, done_dev, value_dev,
+                     next_value_dev, g, gl, adv_dev, ret_dev);
+  HIPCHK(h, hipGetLastError());
   return MZ_OK;
 }
 

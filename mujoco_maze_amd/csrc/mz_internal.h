@@ -101,6 +101,12 @@ hipError_t mzk_planar_rollout_policy(mz_handle* h, hipStream_t st, int nsteps, c
 hipError_t mzk_planar_rollout_policy_sample(mz_handle* h, hipStream_t st, int nsteps, const float* params, long pstride, int hidden, int squash,
                                             float action_scale, uint64_t noise_seed, uint64_t noise_step, float* obs, float* reward, uint8_t* done,
                                             int* goal_idx, float* info, float* obs_seq, float* actions_seq, float* logp_seq);
+// mz_rollout_actor_critic with a critic on the same handles: the same launches (sample: the Gaussian policy), the critic of `critic`
+// (checked by the caller) evaluated on the on-chip row at every step and on the terminal row before an auto-reset overwrites it
+hipError_t mzk_planar_rollout_actor_critic(mz_handle* h, hipStream_t st, int nsteps, const float* params, long pstride, int hidden, int squash,
+                                           float action_scale, int sample, uint64_t noise_seed, uint64_t noise_step, const mz_critic* critic,
+                                           float* obs, float* reward, uint8_t* done, int* goal_idx, float* info, float* obs_seq, float* actions_seq,
+                                           float* logp_seq);
 int mzk_planar_state_width(const mz_handle* h);  // coordinates per env of the state (NV)
 int mzk_planar_record_width(const mz_handle* h); // Point: floats per env-major record; 0 for the chains (SoA)
 

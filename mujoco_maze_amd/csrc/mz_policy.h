@@ -35,6 +35,10 @@
 //              acc = acc + t                                                                                           mzp_logp
 // NaN in log_std propagates to that unit's action and to the row's logp; log_std = -inf gives s = 0, z = m + (+-0) and logp = +inf.
 // mujoco_maze_amd/policy.py mirrors all of it operation by operation (noise, sample_reference).
+//
+// Critics (mz_value / mz_rollout_actor_critic; value_kernel in mazestep.hip, the CRT instantiations of the fused kernels, the host
+// build tests/critic_host): the same unit functions with nu = 1 and no squash — mzp_value_row, mzp_group_value below;
+// policy.py value_reference.
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -139,6 +143,15 @@ MZP_HD void mzp_sample_row(const float* par, int obs_dim, int nu, int H, int squ
   if (logp) *logp = mzp_logp(ls, nu, key, slot);
 }
 
+// ------------------------------------------------------------------ critics (mz_value / mz_rollout_actor_critic)
+// A critic is a policy with nu = 1, never squashed, in a parameter vector of its own: mzp_param_count(obs_dim, 1, Hv) floats, Hv == 0
+// affine, 1 <= Hv <= MZ_POLICY_MAX_HIDDEN one tanh hidden layer.  THE value of a row: the pre-squash sum of its one output unit.
+MZP_HD float mzp_value_row(const float* vpar, int obs_dim, int Hv, const float* x) {
+  float hid[MZ_POLICY_MAX_HIDDEN];
+  for (int j = 0; j < Hv; j++) hid[j] = mzp_hidden_unit(vpar, obs_dim, Hv, x, j);
+  return mzp_output_pre(vpar, obs_dim, 1, Hv, Hv > 0 ? hid : x, 0);
+}
+
 #if defined(__HIPCC__)
 // hand-off between the lanes of a group inside one wavefront (the DevCtx::sync of mz_device.h: LDS operations of a wavefront
 // execute in order, so a wavefront-scope fence that pins the compiler's ordering is a complete phase boundary)
@@ -181,5 +194,20 @@ __device__ __forceinline__ void mzp_group_sample(int l, int G, const float* par,
     if (store) act[u] = a;
   }
   if (l == 0 && logp) *logp = mzp_logp(ls, nu, key, slot);
+}
+
+// mzp_value_row on a group: lanes l, l + G, ... each own one hidden unit, the group's first lane owns the output and returns the
+// value (every other lane returns 0).  `hid` may be the row mzp_group_eval / mzp_group_sample used, once the actor's outputs have
+// been handed over: on entry no lane of the group may still read it, and the caller hands it (and x) over again (mzp_wave_sync)
+// before anything rewrites either.  Every lane of the group must make the call.
+__device__ __forceinline__ float mzp_group_value(int l, int G, const float* vpar, int obs_dim, int Hv, const float* x, float* hid) {
+  if (Hv > 0) {
+    for (int j = l; j < Hv; j += G) hid[j] = mzp_hidden_unit(vpar, obs_dim, Hv, x, j);
+    mzp_wave_sync();
+  }
+  float v = 0.0f;
+  // (two calls, not a select of the pointers: hid is LDS, x may be global memory)
+  if (l == 0) v = Hv > 0 ? mzp_output_pre(vpar, obs_dim, 1, Hv, hid, 0) : mzp_output_pre(vpar, obs_dim, 1, Hv, x, 0);
+  return v;
 }
 #endif

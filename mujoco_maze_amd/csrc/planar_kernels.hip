@@ -6,7 +6,8 @@
 //   planar_rollout_kernel / swimmer_rollout_kernel  up to MZ_ROLLOUT_CHUNK steps of the same on a state that stays on chip (mz_rollout).
 //   planar_policy_rollout_kernel / swimmer_policy_rollout_kernel  the same with the actions of every step computed on chip by the policy
 //                                of mz_policy.h from the step's observation row (mz_rollout_policy), or sampled from its Gaussian
-//                                (SMP instantiations: mz_rollout_policy_sample).
+//                                (SMP instantiations: mz_rollout_policy_sample); CRT instantiations also evaluate a critic on the rows
+//                                (mz_rollout_actor_critic).
 //   reset / state copy kernels; debug kernels for the parity tests (task predicates, the Point's wall detector).
 //
 // HBM layout: SoA  q_0..q_{NV-1} | v_0..v_{NV-1}, each [N] fp32; t[N], episode[N] i32.  API arrays are row-major [N, k].
@@ -247,12 +248,25 @@ struct PolicyNoise {
   uint64_t seed, step;  // noise_seed; noise_step of the launch's first step
   float* logp_seq;      // [nsteps][n] rows of the launch (nullable)
 };
-template <int NB, int NS, int G, bool SMP = false>
+// CRT (mz_rollout_actor_critic with a critic): the group also evaluates the critic of mz_policy.h (mzp_group_value: the unit functions
+// value_kernel, mazestep.hip, runs) on the rows in `o` — at the launch's start on its first row; after every step on the row the step
+// produced, which is the terminal row when the env is about to reset (next_value_seq[k]); if the env did not reset that same number
+// is value_seq[k + 1] (one evaluation, stored twice), if it did the new episode's first row is valued once more.  The hidden units go
+// through phid, which is free between the hand-over of the actor's outputs and the next evaluation of the actor; the group's first
+// lane holds the value.  CRT == false compiles the source without it and never reads `cr`.
+struct PolicyCritic {
+  const float* params;    // [nvpar], or [n][nvpar] with stride = nvpar
+  long stride;
+  int hidden;
+  float* value_seq;       // [nsteps][n] rows of the launch (nullable)
+  float* next_value_seq;  // [nsteps][n] rows of the launch (nullable)
+};
+template <int NB, int NS, int G, bool SMP = false, bool CRT = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && NS == 0 && G == 32) ? 2 : 1))) void planar_policy_rollout_kernel(
     const PointDev* __restrict__ Pp, int n, PointState S, int nsteps, const float* __restrict__ params, long pstride, int hidden, int squash,
     float action_scale, float* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ done, int* __restrict__ goal_idx,
     float* __restrict__ info, float* __restrict__ obs_seq, float* __restrict__ actions_seq, int* __restrict__ status, int auto_reset,
-    uint64_t seed, uint64_t env0, float* __restrict__ final_obs, PolicyNoise ns) {
+    uint64_t seed, uint64_t env0, float* __restrict__ final_obs, PolicyNoise ns, PolicyCritic cr) {
   using D = PlanarDims<NB, NS>;
   constexpr int NV = D::NV, NOBS = D::NOBS, EPW = 64 / G;
   constexpr bool BARE = NB == 0 && NS == 0;
@@ -276,9 +290,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && 
   for (int i = cx.l; i < NOBS; i += G) o[i] = obs[(size_t)env * NOBS + i];  // the observation the policy acts on first
   int t = st_t(S, NV, env), stacc = 0;
   uint32_t ep = st_ep(S, NV, env);
+  const float* vpar = nullptr;
+  float vcur = 0.0f;  // the group's first lane: V(the row in o)
+  if constexpr (CRT) {
+    vpar = cr.params + (size_t)env * cr.stride;
+    cx.sync();  // the row in o is complete
+    vcur = mzp_group_value(cx.l, G, vpar, NOBS, cr.hidden, o, phid[grp]);
+  }
   for (int step = 0; step < nsteps; step++) {
     const size_t row = (size_t)step * n + env;
-    cx.sync();  // the row in o is complete
+    cx.sync();  // the row in o is complete (CRT: and the critic is done with phid)
+    if constexpr (CRT) { if (live && cx.l == 0 && cr.value_seq) cr.value_seq[row] = vcur; }
     if constexpr (SMP)
       mzp_group_sample(cx.l, G, par, NOBS, 2, hidden, squash, action_scale, mzp_noise_key(ns.seed, ns.step + (uint64_t)step), env0 + (uint64_t)env, o,
                        phid[grp], pact[grp], true, live && ns.logp_seq ? ns.logp_seq + row : nullptr);
@@ -319,6 +341,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && 
       }
     }
     cx.sync();  // lane 0 has read the whole state and the terminal row
+    if constexpr (CRT) {  // V(the row this step produced), before a reset overwrites it; the actor's outputs were handed over above
+      vcur = mzp_group_value(cx.l, G, vpar, NOBS, cr.hidden, o, phid[grp]);
+      if (live && cx.l == 0 && cr.next_value_seq) cr.next_value_seq[row] = vcur;
+    }
     if (rst) {
       ep += 1;
       const uint64_t es = episode_seed(seed, ep);
@@ -333,7 +359,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && 
         if (oseq) for (int i = cx.l; i < NOBS; i += G) oseq[i] = o[i];
         if (olast) for (int i = cx.l; i < NOBS; i += G) olast[i] = o[i];
       }
-      cx.sync();
+      cx.sync();  // the new row is complete (CRT: and the group's first lane has read the terminal value's hidden units)
+      if constexpr (CRT) vcur = mzp_group_value(cx.l, G, vpar, NOBS, cr.hidden, o, phid[grp]);
     }
     t = rst ? 0 : t_new;
     // the state as the next launch of planar_step_kernel would load it
@@ -580,14 +607,17 @@ __global__ __launch_bounds__(256) void swimmer_rollout_kernel(const SwimmerDev* 
 // row lives in registers, redundantly in every lane of the group; the group's first lane puts it into LDS (px), the G lanes split the
 // hidden units (phid) and the outputs (pact) over themselves and every lane reads the NH actions back.  Surplus groups shadow the
 // last env through every hand-off and shuffle and store nothing.  SMP: as in planar_policy_rollout_kernel.
-template <int NL, int NB, int G, bool SMP = false>
+// CRT: as in planar_policy_rollout_kernel, on the rows in px — after every step the group's first lane puts the row the step produced
+// there (the fp32 row swimmer_store_row writes to final_obs when the env is about to reset: rows are NO floats apart here, so both
+// are o[0 .. NO - 1]), the group values it, and after a reset the new episode's first row follows and is valued once more.
+template <int NL, int NB, int G, bool SMP = false, bool CRT = false>
 __global__ __launch_bounds__(256) void swimmer_policy_rollout_kernel(const SwimmerDev* __restrict__ Pp, int n, PointState S, int nsteps,
                                                                       const float* __restrict__ params, long pstride, int hidden, int squash,
                                                                       float action_scale, float* __restrict__ obs, float* __restrict__ reward,
                                                                       uint8_t* __restrict__ done, int* __restrict__ goal_idx, float* __restrict__ info,
                                                                       float* __restrict__ obs_seq, float* __restrict__ actions_seq, int* __restrict__ status,
                                                                       int auto_reset, uint64_t seed, uint64_t env0, float* __restrict__ final_obs,
-                                                                      PolicyNoise ns) {
+                                                                      PolicyNoise ns, PolicyCritic cr) {
   constexpr int NR = NL + 2, NV = NR + NB, NH = NL - 1, NOMAX = 2 * NV + 4, GPB = 256 / G;
   __shared__ float px[GPB][NOMAX];
   __shared__ float phid[GPB][MZ_POLICY_MAX_HIDDEN];
@@ -609,9 +639,17 @@ __global__ __launch_bounds__(256) void swimmer_policy_rollout_kernel(const Swimm
   int t = S.t[env], stacc = 0;
   uint32_t ep = S.ep[env];
   const int lane0 = (int)(threadIdx.x & 63u) - cx.l;
+  const float* vpar = nullptr;
+  float vcur = 0.0f;  // the group's first lane: V(the row in x)
+  if constexpr (CRT) {
+    vpar = cr.params + (size_t)env * cr.stride;
+    mzp_wave_sync();  // the row in x is complete
+    vcur = mzp_group_value(cx.l, G, vpar, NO, cr.hidden, x, phid[grp]);
+  }
   for (int step = 0; step < nsteps; step++) {
     const size_t row = (size_t)step * n + env;
-    mzp_wave_sync();  // the row in x is complete
+    mzp_wave_sync();  // the row in x is complete (CRT: and the critic is done with phid)
+    if constexpr (CRT) { if (live && cr.value_seq) cr.value_seq[row] = vcur; }
     if constexpr (SMP)
       mzp_group_sample(cx.l, G, par, NO, NH, hidden, squash, action_scale, mzp_noise_key(ns.seed, ns.step + (uint64_t)step), env0 + (uint64_t)env, x,
                        phid[grp], pact[grp], true, live && ns.logp_seq ? ns.logp_seq + row : nullptr);
@@ -642,6 +680,15 @@ __global__ __launch_bounds__(256) void swimmer_policy_rollout_kernel(const Swimm
       if (goal_idx) goal_idx[row] = gi;
       if (info) for (int k = 0; k < 4; k++) info[row * 4 + k] = (float)inf4[k];
     }
+    if constexpr (CRT) {  // V(the row this step produced), before a reset replaces it; x and phid were handed over with the actions
+      if (lead) {
+#pragma unroll
+        for (int k = 0; k < NOMAX; k++) if (k < NO) x[k] = o[k];
+      }
+      mzp_wave_sync();
+      vcur = mzp_group_value(cx.l, G, vpar, NO, cr.hidden, x, phid[grp]);
+      if (live && cr.next_value_seq) cr.next_value_seq[row] = vcur;
+    }
     if (rst) {
       ep += 1; t_new = 0;
       const uint64_t es = episode_seed(seed, ep);
@@ -656,9 +703,21 @@ __global__ __launch_bounds__(256) void swimmer_policy_rollout_kernel(const Swimm
       }
     }
     t = t_new;
-    if (lead) {
+    if constexpr (CRT) {
+      if (rst) {  // (x already holds the row where the env goes on)
+        mzp_wave_sync();  // the terminal row and its hidden units have been read
+        if (lead) {
 #pragma unroll
-      for (int k = 0; k < NOMAX; k++) if (k < NO) x[k] = o[k];
+          for (int k = 0; k < NOMAX; k++) if (k < NO) x[k] = o[k];
+        }
+        mzp_wave_sync();
+        vcur = mzp_group_value(cx.l, G, vpar, NO, cr.hidden, x, phid[grp]);
+      }
+    } else {
+      if (lead) {
+#pragma unroll
+        for (int k = 0; k < NOMAX; k++) if (k < NO) x[k] = o[k];
+      }
     }
   }
   if (!live) return;
@@ -875,10 +934,12 @@ hipError_t mzk_planar_rollout(mz_handle* h, hipStream_t st, int nsteps, const fl
 // mz_rollout_policy (SMP false) / mz_rollout_policy_sample (SMP true: `noise` holds the call's seed, first step and logp_seq) on
 // the fused handles: mzk_planar_rollout's launches with the policy in place of the action tensor.  Every launch writes obs_dev at
 // its last step, and the next one reads its first observation there — and continues at noise_step + the steps done so far.
-template <bool SMP>
+// CRT (mz_rollout_actor_critic with a critic): `critic` holds the critic's parameters and the call's value_seq / next_value_seq.
+template <bool SMP, bool CRT = false>
 static hipError_t planar_rollout_policy_launches(mz_handle* h, hipStream_t st, int nsteps, const float* params_dev, long pstride, int hidden,
                                                  int squash, float action_scale, float* obs_dev, float* reward_dev, uint8_t* done_dev,
-                                                 int* goal_idx_dev, float* info_dev, float* obs_seq_dev, float* actions_seq_dev, PolicyNoise noise) {
+                                                 int* goal_idx_dev, float* info_dev, float* obs_seq_dev, float* actions_seq_dev, PolicyNoise noise,
+                                                 PolicyCritic critic = PolicyCritic{nullptr, 0, 0, nullptr, nullptr}) {
   PointState S{h->state, h->pt_t, h->pt_ep, h->pt_rec};
   const size_t n = (size_t)h->n, od = (size_t)h->model.obs_dim, nu = (size_t)h->model.nu;
   for (int k0 = 0; k0 < nsteps; k0 += MZ_ROLLOUT_CHUNK) {
@@ -890,11 +951,13 @@ static hipError_t planar_rollout_policy_launches(mz_handle* h, hipStream_t st, i
     float* oseq = obs_seq_dev ? obs_seq_dev + k0 * n * od : nullptr;
     float* aseq = actions_seq_dev ? actions_seq_dev + k0 * n * nu : nullptr;
     const PolicyNoise ns{noise.seed, noise.step + (uint64_t)k0, noise.logp_seq ? noise.logp_seq + k0 * n : nullptr};
+    const PolicyCritic cr{critic.params, critic.stride, critic.hidden, critic.value_seq ? critic.value_seq + k0 * n : nullptr,
+                          critic.next_value_seq ? critic.next_value_seq + k0 * n : nullptr};
     if (h->robot == MZ_ROBOT_SWIMMER) {
 #define MZ_SW_ROLL(NL, NB)                                                                                                          \
-  hipLaunchKernelGGL((swimmer_policy_rollout_kernel<NL, NB, (NL <= 4 ? 4 : 8), SMP>), dim3((unsigned)((n * (NL <= 4 ? 4 : 8) + sw_bd - 1) / sw_bd)), dim3(sw_bd), 0, st, \
+  hipLaunchKernelGGL((swimmer_policy_rollout_kernel<NL, NB, (NL <= 4 ? 4 : 8), SMP, CRT>), dim3((unsigned)((n * (NL <= 4 ? 4 : 8) + sw_bd - 1) / sw_bd)), dim3(sw_bd), 0, st, \
                      h->swimmer_dev, h->n, S, ks, params_dev, pstride, hidden, squash, action_scale, obs_dev, rew, dn, gi, inf, oseq, aseq, h->status,         \
-                     h->auto_reset, h->seed, h->env0, h->final_obs, ns)
+                     h->auto_reset, h->seed, h->env0, h->final_obs, ns, cr)
       const int bd = h->swimmer.nblock ? h->swimmer.nbdof : 0;
       const unsigned sw_bd = 64u * (unsigned)(h->wpb_set ? h->waves_per_block : 4);
       if (h->swimmer.nlink == 3) { if (bd == 3) MZ_SW_ROLL(3, 3); else if (bd == 2) MZ_SW_ROLL(3, 2); else MZ_SW_ROLL(3, 0); }
@@ -905,8 +968,8 @@ static hipError_t planar_rollout_policy_launches(mz_handle* h, hipStream_t st, i
 #undef MZ_SW_ROLL
     } else {
 #define MZ_PLANAR_ROLL(NB, NS, G)                                                                                                      \
-  hipLaunchKernelGGL((planar_policy_rollout_kernel<NB, NS, G, SMP>), dim3((h->n + 64 / G - 1) / (64 / G)), dim3(64), 0, st, h->point_dev, h->n, S, ks, params_dev, \
-                     pstride, hidden, squash, action_scale, obs_dev, rew, dn, gi, inf, oseq, aseq, h->status, h->auto_reset, h->seed, h->env0, h->final_obs, ns)
+  hipLaunchKernelGGL((planar_policy_rollout_kernel<NB, NS, G, SMP, CRT>), dim3((h->n + 64 / G - 1) / (64 / G)), dim3(64), 0, st, h->point_dev, h->n, S, ks, params_dev, \
+                     pstride, hidden, squash, action_scale, obs_dev, rew, dn, gi, inf, oseq, aseq, h->status, h->auto_reset, h->seed, h->env0, h->final_obs, ns, cr)
       if (h->point.nball) MZ_PLANAR_ROLL(0, 1, 32);
       else switch (h->point.nblock) {
         case 0: {
@@ -941,6 +1004,19 @@ hipError_t mzk_planar_rollout_policy_sample(mz_handle* h, hipStream_t st, int ns
                                             float* logp_seq_dev) {
   return planar_rollout_policy_launches<true>(h, st, nsteps, params_dev, pstride, hidden, squash, action_scale, obs_dev, reward_dev, done_dev,
                                               goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, PolicyNoise{noise_seed, noise_step, logp_seq_dev});
+}
+
+hipError_t mzk_planar_rollout_actor_critic(mz_handle* h, hipStream_t st, int nsteps, const float* params_dev, long pstride, int hidden, int squash,
+                                           float action_scale, int sample, uint64_t noise_seed, uint64_t noise_step, const mz_critic* critic,
+                                           float* obs_dev, float* reward_dev, uint8_t* done_dev, int* goal_idx_dev, float* info_dev, float* obs_seq_dev,
+                                           float* actions_seq_dev, float* logp_seq_dev) {
+  const PolicyCritic cr{critic->params_dev, (long)critic->env_stride, critic->hidden, critic->value_seq_dev, critic->next_value_seq_dev};
+  if (sample)
+    return planar_rollout_policy_launches<true, true>(h, st, nsteps, params_dev, pstride, hidden, squash, action_scale, obs_dev, reward_dev, done_dev,
+                                                      goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev,
+                                                      PolicyNoise{noise_seed, noise_step, logp_seq_dev}, cr);
+  return planar_rollout_policy_launches<false, true>(h, st, nsteps, params_dev, pstride, hidden, squash, action_scale, obs_dev, reward_dev, done_dev,
+                                                     goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, PolicyNoise{0, 0, nullptr}, cr);
 }
 
 hipError_t mzk_planar_reset(mz_handle* h, hipStream_t st, const uint8_t* mask_dev, uint64_t seed, float* obs_dev) {

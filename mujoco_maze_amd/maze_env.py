@@ -499,7 +499,7 @@ class VecMazeEnv:
         return out
 
     def rollout_policy(self, params, steps: int, hidden: int = 0, squash: bool = False, action_scale: float = 1.0, obs=None,
-                       return_obs: bool = False, return_actions: bool = False):
+                       return_obs: bool = False, return_actions: bool = False, value_params=None, value_hidden: int = 0, gae=None):
         """K = `steps` closed-loop steps in one call: a = policy(obs); obs, reward, done = step(a) — exactly what K times
         (`policy_act`, `step`) give, state and outputs bit for bit.  params / hidden / squash / action_scale as in `policy_act`.
         The policy acts first on the env's last returned observation (what reset / step / rollout left in the observation buffer),
@@ -512,7 +512,12 @@ class VecMazeEnv:
         One mz_rollout_policy call — the Point, Swimmer and Reacher evaluate the policy inside their fused rollout kernels
         (`launch_info()["rollout_fused"]`), the other handles loop policy kernel + step launches inside the call — except where the
         host has work between steps (Python reward()/termination() overrides; per-env goals under auto-reset): there this method
-        loops `policy_act` + `step` itself."""
+        loops `policy_act` + `step` itself.
+
+        value_params / value_hidden / gae: a critic evaluated along the way and the advantages from it, see `rollout_policy_sample`."""
+        if value_params is not None or gae is not None:
+            return self._rollout_actor_critic(False, params, steps, hidden, squash, action_scale, obs, None, None, return_obs, return_actions,
+                                              value_params, value_hidden, gae)
         torch, n = self._torch, self.num_envs
         p, stride = self._policy_params(params, hidden)
         K = int(steps)
@@ -585,14 +590,26 @@ class VecMazeEnv:
 
     def rollout_policy_sample(self, params, steps: int, hidden: int = 0, squash: bool = False, action_scale: float = 1.0, obs=None,
                               noise_seed: Optional[int] = None, noise_step: Optional[int] = None, return_obs: bool = False,
-                              return_actions: bool = False):
+                              return_actions: bool = False, value_params=None, value_hidden: int = 0, gae=None):
         """K = `steps` closed-loop steps with a sampled action each, in one call: exactly what K times (`policy_sample` with
         noise_step + k, `step`) give, state and outputs bit for bit.  Everything as in `rollout_policy`, plus info["logp"] [K, N], the
         log-probabilities of the draws (see `policy_sample`); info["actions"] [K, N, nu] with `return_actions` holds the sampled
         actions.  noise_seed / noise_step as in `policy_sample`; the env's counter advances by K.
 
         One mz_rollout_policy_sample call — sampled inside the fused rollout kernels of the Point, Swimmer and Reacher — except
-        where the host has work between steps (as in `rollout_policy`): there this method loops `policy_sample` + `step` itself."""
+        where the host has work between steps (as in `rollout_policy`): there this method loops `policy_sample` + `step` itself.
+
+        With `value_params` (a critic as in `value`, `value_hidden` its hidden width) the call also returns info["values"] [K, N], the
+        critic's value of the row the policy acted on at step k, and info["next_values"] [K, N], its value of the row step k produced
+        BEFORE any auto-reset — for an env that finished, of its terminal observation, which is what a time-limit truncation
+        (done & 2) bootstraps from; next_values[k] equals values[k + 1] wherever done[k] == 0.  With `gae=(gamma, lam)` as well,
+        info["advantages"] and info["returns"] [K, N] (`gae`).  One mz_rollout_actor_critic call (the critic runs inside the fused
+        kernels, on the row that is on chip anyway) plus one mz_gae call; the critic changes nothing else the call returns.  Where
+        this method loops itself it loops `value` + `policy_sample` + `step` + `value`, with the terminal rows taken from
+        info["final_observation"]."""
+        if value_params is not None or gae is not None:
+            return self._rollout_actor_critic(True, params, steps, hidden, squash, action_scale, obs, noise_seed, noise_step, return_obs,
+                                              return_actions, value_params, value_hidden, gae)
         torch, n = self._torch, self.num_envs
         p, stride = self._policy_params(params, hidden, stochastic=True)
         K = int(steps)
@@ -625,6 +642,128 @@ class VecMazeEnv:
             _capi.check(self._lib, self._h, rc, "mz_rollout_policy_sample")
         info = {"position": buf["info"][:, :, :2], "reward_forward": buf["info"][:, :, 2], "reward_ctrl": buf["info"][:, :, 3],
                 "goal_index": buf["goal"], "logp": buf["logp"]}
+        if return_obs:
+            info["observations"] = buf["obs_seq"]
+        if return_actions:
+            info["actions"] = buf["actions"]
+        if self._auto_reset:
+            info["final_observation"] = self._final_obs
+        return self._obs, buf["reward"], buf["done"], info
+
+    def _value_params(self, value_params, hidden: int):
+        """A critic's parameters as a contiguous float32 device tensor [nvpar] or [N, nvpar]; returns (tensor, env_stride)."""
+        from mujoco_maze_amd import policy
+
+        torch = self._torch
+        hidden = int(hidden)
+        if not 0 <= hidden <= policy.MAX_HIDDEN:
+            raise ValueError(f"the critic's hidden must be 0 .. {policy.MAX_HIDDEN}, got {hidden}")
+        npar = policy.param_count(self.obs_dim, 1, hidden)
+        p = value_params if torch.is_tensor(value_params) else torch.as_tensor(np.asarray(value_params, dtype=np.float32), device=self.device)
+        if p.dtype != torch.float32 or not p.is_contiguous() or p.device != self.device:
+            p = p.to(device=self.device, dtype=torch.float32).contiguous()
+        if tuple(p.shape) not in ((npar,), (self.num_envs, npar)):
+            raise ValueError(f"value_params must have shape {(npar,)} (one critic) or {(self.num_envs, npar)} (one per env) for obs_dim "
+                             f"{self.obs_dim}, hidden {hidden}, got {tuple(p.shape)}")
+        return p, (npar if p.dim() == 2 else 0)
+
+    def value(self, value_params, obs=None, hidden: int = 0):
+        """Values [N] of a small critic evaluated on the device (mz_value): a policy of `policy_act` with one output, never squashed —
+        affine (`hidden=0`) or one tanh hidden layer of up to 64 units.  value_params: float32 [nvpar] (one critic for all envs) or
+        [N, nvpar] (one per env), nvpar = policy.param_count(obs_dim, 1, hidden), packed by `policy.pack` / `pack_linear` with
+        nu = 1; obs: [N, obs_dim], default the env's last returned observation.  A new tensor per call."""
+        p, stride = self._value_params(value_params, hidden)
+        o = self._obs if obs is None else self._policy_obs(obs)
+        out = self._torch.empty(self.num_envs, dtype=self._torch.float32, device=self.device)
+        rc = self._lib.mz_value(self._h, _ptr(p), stride, int(hidden), _ptr(o), _ptr(out), self._stream())
+        _capi.check(self._lib, self._h, rc, "mz_value")
+        return out
+
+    def gae(self, rewards, dones, values, next_values, gamma: float = 0.99, lam: float = 0.95, out=None):
+        """Generalised advantage estimates of a rollout in one kernel (mz_gae): rewards, values, next_values float32 [K, N], dones
+        uint8 [K, N] as `rollout_policy_sample(..., value_params=)` returns them.  Per env, from the last step back, in float32:
+        delta = reward + (0 if done & 1 else gamma * next_value) - value; adv = delta + (0 if done else gamma * lam * adv of the
+        step after).  A true termination does not bootstrap, a time limit alone bootstraps from the terminal observation's value,
+        any episode end cuts the recursion (`policy.gae_reference` is the numpy model).  Returns (advantages, returns = advantages +
+        values), new [K, N] tensors — or the pair `out`."""
+        torch, n = self._torch, self.num_envs
+
+        def arr(t, dtype, what):
+            t = t if torch.is_tensor(t) else torch.as_tensor(np.asarray(t), device=self.device)
+            if t.dtype != dtype or not t.is_contiguous() or t.device != self.device:
+                t = t.to(device=self.device, dtype=dtype).contiguous()
+            if t.dim() != 2 or t.shape[1] != n:
+                raise ValueError(f"{what} must have shape (K, {n}), got {tuple(t.shape)}")
+            return t
+
+        r, d = arr(rewards, torch.float32, "rewards"), arr(dones, torch.uint8, "dones")
+        v, nv = arr(values, torch.float32, "values"), arr(next_values, torch.float32, "next_values")
+        K = int(r.shape[0])
+        if not (d.shape == v.shape == nv.shape == r.shape) or not 1 <= K <= 65536:
+            raise ValueError(f"rewards, dones, values and next_values must share one (K, {n}) shape with 1 <= K <= 65536, got "
+                             f"{tuple(r.shape)}, {tuple(d.shape)}, {tuple(v.shape)}, {tuple(nv.shape)}")
+        adv, ret = out if out is not None else (torch.empty_like(r), torch.empty_like(r))
+        rc = self._lib.mz_gae(self._h, K, _ptr(r), _ptr(d), _ptr(v), _ptr(nv), float(gamma), float(lam), _ptr(adv), _ptr(ret), self._stream())
+        _capi.check(self._lib, self._h, rc, "mz_gae")
+        return adv, ret
+
+    def _rollout_actor_critic(self, sample: bool, params, steps, hidden, squash, action_scale, obs, noise_seed, noise_step, return_obs,
+                              return_actions, value_params, value_hidden, gae):
+        """rollout_policy (sample False) / rollout_policy_sample (sample True) with a critic: one mz_rollout_actor_critic call, or the
+        defining loop where the host has work between steps."""
+        torch, n = self._torch, self.num_envs
+        if value_params is None:
+            raise ValueError("gae=(gamma, lam) needs a critic: pass value_params")
+        if gae is not None:
+            gamma, lam = (float(x) for x in gae)
+        p, stride = self._policy_params(params, hidden, stochastic=sample)
+        vp, vstride = self._value_params(value_params, value_hidden)
+        K = int(steps)
+        if not 1 <= K <= 65536:
+            raise ValueError(f"a rollout takes 1 .. 65536 steps, got {K}")
+        if obs is not None:
+            o = self._policy_obs(obs)
+            if o.data_ptr() != self._obs.data_ptr():
+                self._obs.copy_(o)
+        buf = self._rollout_buffers(K, return_obs)
+        if return_actions and "actions" not in buf:
+            buf["actions"] = torch.empty((K, n, self.nu), dtype=torch.float32, device=self.device)
+        for key in (("logp",) if sample else ()) + ("values", "next_values") + (("advantages", "returns") if gae is not None else ()):
+            if key not in buf:
+                buf[key] = torch.empty((K, n), dtype=torch.float32, device=self.device)
+        seed, step = self._noise_args(noise_seed, noise_step, K) if sample else (C.c_uint64(0), C.c_uint64(0))
+        if self._host_rewards or (self._env_goals is not None and self._auto_reset):
+            for k in range(K):
+                buf["values"][k] = self.value(vp, None, value_hidden)
+                if sample:
+                    a, buf["logp"][k] = self.policy_sample(p, None, hidden, squash, action_scale, seed.value, step.value + k)
+                else:
+                    a = self.policy_act(p, None, hidden, squash, action_scale)
+                o, rew, done, inf = self.step(a)
+                buf["reward"][k], buf["done"][k], buf["goal"][k], buf["info"][k] = rew, done, inf["goal_index"], self._info
+                nv = self.value(vp, None, value_hidden)
+                if self._auto_reset:  # an env that finished: the value of its terminal row, which `o` no longer holds
+                    nv = torch.where(done != 0, self.value(vp, inf["final_observation"], value_hidden), nv)
+                buf["next_values"][k] = nv
+                if return_obs:
+                    buf["obs_seq"][k] = o
+                if return_actions:
+                    buf["actions"][k] = a
+        else:
+            critic = _capi.MzCritic(_ptr(vp), vstride, int(value_hidden), 0, _ptr(buf["values"]), _ptr(buf["next_values"]))
+            rc = self._lib.mz_rollout_actor_critic(self._h, K, _ptr(p), stride, int(hidden), 1 if squash else 0, float(action_scale), 1 if sample else 0,
+                                                   seed, step, C.byref(critic), _ptr(self._obs), _ptr(buf["reward"]), _ptr(buf["done"]),
+                                                   _ptr(buf["goal"]), _ptr(buf["info"]), _ptr(buf["obs_seq"]) if return_obs else None,
+                                                   _ptr(buf["actions"]) if return_actions else None, _ptr(buf["logp"]) if sample else None,
+                                                   self._stream())
+            _capi.check(self._lib, self._h, rc, "mz_rollout_actor_critic")
+        info = {"position": buf["info"][:, :, :2], "reward_forward": buf["info"][:, :, 2], "reward_ctrl": buf["info"][:, :, 3],
+                "goal_index": buf["goal"], "values": buf["values"], "next_values": buf["next_values"]}
+        if sample:
+            info["logp"] = buf["logp"]
+        if gae is not None:
+            info["advantages"], info["returns"] = self.gae(buf["reward"], buf["done"], buf["values"], buf["next_values"], gamma, lam,
+                                                           out=(buf["advantages"], buf["returns"]))
         if return_obs:
             info["observations"] = buf["obs_seq"]
         if return_actions:

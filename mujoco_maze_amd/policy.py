@@ -27,6 +27,11 @@ slot being the global env slot —, `sample_reference` the draw and its log-prob
 logp is the density of z; with squash it is the PRE-tanh density, and the caller applies the tanh correction from the actions.
 The integer part is exact; the float part runs float64 libm on the float32 u1, u2 and the float32 angle and rounds the factors to
 float32, so it differs from the device by libm ulps only.
+
+Critics (VecMazeEnv.value, the `value_params=` of the rollouts; mz_value / mz_rollout_actor_critic) are policies with nu = 1, never
+squashed, in a vector of their own (`param_count(obs_dim, 1, hidden)`, packed by `pack` / `pack_linear`): `value_reference` is the
+pre-squash sum of the one output unit, bit-equal to the device for hidden == 0.  `gae_reference` is the backward scan of
+VecMazeEnv.gae / mz_gae (csrc/mz_gae.h) in float32, operation by operation: bit-equal to the device.
 """
 import numpy as np
 
@@ -186,3 +191,51 @@ def sample_reference(params, obs, nu: int, hidden: int = 0, squash: bool = False
             t = (t - np.float32(0.9189385)).astype(np.float32)
             logp = (logp + t).astype(np.float32)
     return (act[0], logp[0]) if single else (act, logp)
+
+
+def value_reference(value_params, obs, hidden: int = 0):
+    """The critic of csrc/mz_policy.h (mzp_value_row) on rows of observations: a policy with nu = 1, never squashed, whose value is
+    the pre-squash sum of its one output unit.  obs [R, obs_dim] (or [obs_dim]); value_params [nvpar] shared by the rows or
+    [R, nvpar], nvpar = param_count(obs_dim, 1, hidden).  Returns float32 [R] (or a scalar); bit-equal to the device for hidden == 0."""
+    x = np.asarray(obs, dtype=np.float32)
+    single = x.ndim == 1
+    x = np.atleast_2d(x)
+    p = np.asarray(value_params, dtype=np.float32)
+    R, od, H = x.shape[0], x.shape[1], int(hidden)
+    npar = param_count(od, 1, H)
+    if p.shape not in ((npar,), (R, npar)):
+        raise ValueError(f"value_params must have shape {(npar,)} or {(R, npar)}, got {p.shape}")
+    with np.errstate(over="ignore", invalid="ignore"):
+        v = _pre_squash(x, p, 1, H)[:, 0]
+    return v[0] if single else v
+
+
+def gae_reference(rewards, dones, values, next_values, gamma: float = 0.99, lam: float = 0.95):
+    """The backward scan of csrc/mz_gae.h (mz_gae) on [K, N] rows, float32, every operation rounded separately, k from K - 1 down to
+    0 with carry = 0:
+
+        g = float32(gamma); gl = g * float32(lam)
+        b     = 0 if done & 1 else g * next_value        (true termination: no bootstrap; a time limit alone bootstraps)
+        delta = (reward + b) - value
+        c     = 0 if done else gl * carry                (any episode end cuts the recursion)
+        adv   = delta + c; carry = adv; ret = adv + value
+
+    Selects, not products with a mask: NaN behind a true termination does not leak.  Returns (advantages, returns), float32 [K, N]."""
+    r, v, nv = (np.asarray(a, dtype=np.float32) for a in (rewards, values, next_values))
+    d = np.asarray(dones, dtype=np.uint8)
+    if r.ndim != 2 or not (r.shape == d.shape == v.shape == nv.shape):
+        raise ValueError(f"rewards, dones, values and next_values must share one [K, N] shape, got {r.shape}, {d.shape}, {v.shape}, {nv.shape}")
+    g = np.float32(gamma)
+    gl = np.float32(g * np.float32(lam))
+    adv, ret = np.empty_like(r), np.empty_like(r)
+    carry = np.zeros(r.shape[1], dtype=np.float32)
+    zero = np.float32(0.0)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for k in range(r.shape[0] - 1, -1, -1):
+            b = np.where((d[k] & 1) != 0, zero, (g * nv[k]).astype(np.float32)).astype(np.float32)
+            delta = ((r[k] + b).astype(np.float32) - v[k]).astype(np.float32)
+            c = np.where(d[k] != 0, zero, (gl * carry).astype(np.float32)).astype(np.float32)
+            carry = (delta + c).astype(np.float32)
+            adv[k] = carry
+            ret[k] = (carry + v[k]).astype(np.float32)
+    return adv, ret

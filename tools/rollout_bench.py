@@ -9,6 +9,12 @@ units) are timed instead, same protocol: K x (torch policy + env.step), K x (env
 With --policy H --sample the same K steps with a sampled action each (log_std = -0.5 on every unit): K x (env.policy_sample + env.step),
 one env.rollout_policy_sample, and the deterministic env.rollout_policy at the same shape beside them.
     python tools/rollout_bench.py --policy 32 --sample
+With --policy H --sample --critic HV one actor-critic collection window (a shared critic with HV hidden units, 0 = affine; gamma 0.99,
+lambda 0.95): K x (env.policy_sample + env.step) with the rows kept, a torch critic over the [K, N, obs_dim] rows and a torch GAE loop
+of K iterations; one env.rollout_policy_sample(..., value_params=, gae=); and the one-call rollout without a critic beside them.  (The
+torch leg bootstraps every row from the value of the NEXT row it holds: the terminal rows are gone, which is the gap the one-call path
+closes — its cost is what this compares, not its result.)
+    python tools/rollout_bench.py --policy 32 --sample --critic 32 --steps 128 --ids PointUMaze-v0,SwimmerUMaze-v0,AntUMaze-v0
 Kernel durations come from a run of their own:  rocprofv3 --kernel-trace --stats -d <dir> -- python tools/rollout_bench.py --seconds 0.2"""
 import argparse
 import json
@@ -169,6 +175,95 @@ def bench_sample(env_id, n, K, H, seconds, repeats):
             **{name + "_env_steps_per_s": v for name, v in res.items()}}
 
 
+def bench_critic(env_id, n, K, H, HV, seconds, repeats):
+    """One actor-critic collection window of K steps: policy_sample + step + torch critic + torch GAE loop; one
+    rollout_policy_sample with value_params and gae; the same call without a critic."""
+    from mujoco_maze_amd import policy
+
+    dev = torch.device("cuda", 0)
+    env = mm.make(env_id, num_envs=n, auto_reset=True, device=dev, force_vec=True)
+    env.reset(seed=20260928)
+    g = torch.Generator(device=dev).manual_seed(1234)
+    gamma, lam = 0.99, 0.95
+
+    def lin(out, fan_in):
+        k = fan_in ** -0.5
+        return (2 * torch.rand((out, fan_in), device=dev, generator=g) - 1) * k, (2 * torch.rand(out, device=dev, generator=g) - 1) * k
+
+    log_std = torch.full((env.nu,), -0.5)
+    if H:
+        (W1, b1), (W2, b2) = lin(H, env.obs_dim), lin(env.nu, H)
+        params = torch.as_tensor(policy.pack(W1, b1, W2, b2, log_std=log_std), device=dev)
+    else:
+        params = torch.as_tensor(policy.pack_linear(*lin(env.nu, env.obs_dim), log_std=log_std), device=dev)
+    if HV:
+        (V1, c1), (V2, c2) = lin(HV, env.obs_dim), lin(1, HV)
+        vparams = torch.as_tensor(policy.pack(V1, c1, V2, c2), device=dev)
+        V1t, V2t = V1.T.contiguous(), V2.T.contiguous()
+        torch_critic = lambda obs: torch.addmm(c2, torch.tanh(torch.addmm(c1, obs, V1t)), V2t)
+    else:
+        V, c = lin(1, env.obs_dim)
+        vparams = torch.as_tensor(policy.pack_linear(V, c), device=dev)
+        Vt = V.T.contiguous()
+        torch_critic = lambda obs: torch.addmm(c, obs, Vt)
+    rows = torch.empty((K + 1, n, env.obs_dim), device=dev)
+    rew, done = torch.empty((K, n), device=dev), torch.empty((K, n), dtype=torch.uint8, device=dev)
+    adv = torch.empty((K, n), device=dev)
+
+    def torch_path():
+        rows[0] = env._obs
+        for k in range(K):
+            o, r, d, _ = env.step(env.policy_sample(params, hidden=H)[0])
+            rows[k + 1], rew[k], done[k] = o, r, d
+        v = torch_critic(rows.view((K + 1) * n, env.obs_dim)).view(K + 1, n)
+        carry = torch.zeros(n, device=dev)
+        term, end = (done & 1) != 0, done != 0
+        for k in range(K - 1, -1, -1):
+            delta = rew[k] + torch.where(term[k], 0.0, gamma * v[k + 1]) - v[k]
+            carry = delta + torch.where(end[k], 0.0, gamma * lam * carry)
+            adv[k] = carry
+        return adv, adv + v[:K]
+
+    def one_call():
+        env.rollout_policy_sample(params, K, hidden=H, value_params=vparams, value_hidden=HV, gae=(gamma, lam))
+
+    def no_critic():
+        env.rollout_policy_sample(params, K, hidden=H)
+
+    legs = (("torch_critic_gae", torch_path), ("rollout_actor_critic_gae", one_call), ("rollout_policy_sample", no_critic))
+    for _ in range(4):
+        for _, fn in legs:
+            fn()
+    res = {name: [] for name, _ in legs}
+    for _ in range(repeats):
+        for name, fn in legs:
+            w, dt = leg(fn, 4, seconds, dev)
+            res[name].append(n * K * w / dt)
+    bad = int((env.status() & 3).ne(0).sum())
+    fused_flag = env.launch_info()["rollout_fused"]
+    env.close()
+    return {"env": env_id, "envs": n, "steps_per_window": K, "hidden": H, "critic_hidden": HV, "sample": True, "fused": fused_flag, "flagged_envs": bad,
+            **{name + "_env_steps_per_s": v for name, v in res.items()}}
+
+
+def main_critic(args):
+    out = []
+    med = lambda v: sorted(v)[len(v) // 2]
+    print(f"actor-critic window, shared Gaussian policy (hidden {args.policy}) and critic (hidden {args.critic}), GAE(0.99, 0.95), {args.steps} steps per "
+          f"window, {args.envs} envs, auto-reset, >= {args.seconds} s per leg, {args.repeats} alternating repeats; M env-steps/s, median (max - min)")
+    print("%-18s %5s %26s %26s %26s" % ("env", "fused", "sample+step, torch V, GAE", "one call, critic + gae", "one call, no critic"))
+    for env_id in args.ids.split(","):
+        r = bench_critic(env_id, args.envs, args.steps, args.policy, args.critic, args.seconds, args.repeats)
+        out.append(r)
+        cell = lambda v: "%10.3f (%6.3f)" % (med(v) / 1e6, (max(v) - min(v)) / 1e6)
+        print("%-18s %5d %26s %26s %26s" % (env_id, r["fused"], cell(r["torch_critic_gae_env_steps_per_s"]), cell(r["rollout_actor_critic_gae_env_steps_per_s"]),
+                                            cell(r["rollout_policy_sample_env_steps_per_s"])), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            for r in out:
+                f.write(json.dumps(r) + "\n")
+
+
 def main_sample(args):
     out = []
     med = lambda v: sorted(v)[len(v) // 2]
@@ -215,10 +310,15 @@ def main():
     ap.add_argument("--out", type=str, default=None, help="also write the rows as JSON lines")
     ap.add_argument("--policy", type=int, default=None, metavar="H", help="closed-loop mode: hidden units of the policy (0 = affine)")
     ap.add_argument("--sample", action="store_true", help="with --policy: Gaussian policies, a sampled action every step")
+    ap.add_argument("--critic", type=int, default=None, metavar="HV", help="with --policy H --sample: a critic with HV hidden units (0 = affine) and GAE")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "rollout_bench.py measures on the GPU only"
     if args.sample and args.policy is None:
         ap.error("--sample goes with --policy H")
+    if args.critic is not None and not args.sample:
+        ap.error("--critic goes with --policy H --sample")
+    if args.critic is not None:
+        return main_critic(args)
     if args.policy is not None:
         return main_sample(args) if args.sample else main_policy(args)
     out = []
