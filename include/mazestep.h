@@ -503,6 +503,53 @@ int32_t mz_rollout_actor_critic(mz_handle* h, int32_t n_steps, const float* para
 int32_t mz_gae(mz_handle* h, int32_t n_steps, const float* reward_dev, const uint8_t* done_dev, const float* value_dev,
                const float* next_value_dev, double gamma, double lam, float* adv_dev, float* ret_dev, void* stream);
 
+/* Networks of up to two hidden layers, with tanh or ReLU units (the obs -> 64 -> 64 -> out default of PPO / A2C / ES code): the
+ * policies and critics above, described by a struct.  Additive entries: MZ_ABI_VERSION does not change for them, and the struct
+ * carries its own size (struct_size = sizeof of the struct as the caller compiled it; any other value is MZ_ERR_ARG).
+ *
+ * A network has n_hidden = 0, 1 or 2 hidden layers of hidden[0], hidden[1] = 1 .. MZ_POLICY_MAX_HIDDEN units (entries of layers not
+ * in use: 0) and one activation for both: MZ_ACT_TANH, tanhf(acc), or MZ_ACT_RELU, acc < 0.0f ? 0.0f : acc — a select that adds no
+ * rounding, keeps -0.0f and lets a NaN through.  Packed vector, input-major as above; n_hidden 0 and 1 are the two layouts above, and
+ *   n_hidden == 2     W1t [obs_dim][H1], b1 [H1], W2t [H1][H2], b2 [H2], W3t [H2][nout], b3 [nout]
+ * with nout = nu for an actor and 1 for a critic, then log_std [nu] where the call samples.  count: the floats of one vector, log_std
+ * included where the call samples; params_dev [count] (env_stride == 0) or [N, count] (env_stride == count).  The arithmetic is that
+ * of the policies above (csrc/mz_policy.h: one lane per unit, serially through one dot product, fp32, no contraction; a layer-2 unit
+ * reads the complete layer-1 vector), so a ReLU network without squash is reproduced bit for bit by fp32 arithmetic anywhere, at any
+ * depth (mujoco_maze_amd/policy.py reference), and with n_hidden <= 1 and MZ_ACT_TANH every entry below returns the bits of the
+ * entry above it stands for.  squash and action_scale belong to an actor; a critic has squash == 0 and its action_scale is ignored.
+ *
+ * mz_net_act: mz_policy_act (sample == 0: noise_seed, noise_step and logp_dev are ignored) or mz_policy_sample (sample == 1).
+ * mz_net_value: mz_value.
+ * mz_rollout_net: the loop in the comment of mz_rollout_actor_critic with mz_net_value / mz_net_act in place of mz_value /
+ * mz_policy_act / mz_policy_sample — the call leaves the handle and every output as that loop would, bit for bit; critic nullable,
+ * value_seq_dev / next_value_seq_dev [n_steps, N] (nullable; ignored without a critic).  Noise, log-prob, the launch split of the
+ * fused handles, the final_obs requirement for next_value_seq_dev under auto-reset and n_steps 1 .. 65536 are as above.  Handles with
+ * "rollout_fused" = 1 evaluate both networks inside the fused rollout kernels; every other handle runs the loop inside the call.
+ * MZ_ERR_ARG, with a message that names the argument: a NULL net or NULL params_dev, a wrong struct_size, n_hidden outside 0 .. 2, a
+ * width outside 1 .. MZ_POLICY_MAX_HIDDEN in a layer in use, a non-zero width in a layer not in use, activation outside
+ * {MZ_ACT_TANH, MZ_ACT_RELU}, squash outside {0, 1}, a critic with squash != 0, an env_stride that is neither 0 nor count, sample
+ * outside {0, 1}, and everything mz_rollout_actor_critic refuses. */
+#define MZ_NET_MAX_HIDDEN_LAYERS 2
+#define MZ_ACT_TANH 0
+#define MZ_ACT_RELU 1
+typedef struct mz_net {
+  uint32_t struct_size;      /* sizeof(mz_net); anything else: MZ_ERR_ARG */
+  int32_t n_hidden;          /* 0, 1, 2 */
+  int32_t hidden[2];         /* widths 1 .. MZ_POLICY_MAX_HIDDEN of the layers in use; unused entries 0 */
+  int32_t activation;        /* MZ_ACT_*, of the hidden layers */
+  int32_t squash;            /* actor: 0 / 1; a critic: 0 */
+  double action_scale;
+  const float* params_dev;   /* [count] or [N, count] */
+  int64_t env_stride;        /* 0 or count (count includes log_std[nu] when the call samples) */
+} mz_net;
+int32_t mz_net_act(mz_handle* h, const mz_net* actor, int32_t sample, uint64_t noise_seed, uint64_t noise_step, const float* obs_dev,
+                   float* actions_dev, float* logp_dev, void* stream);
+int32_t mz_net_value(mz_handle* h, const mz_net* critic, const float* obs_dev, float* values_dev, void* stream);
+int32_t mz_rollout_net(mz_handle* h, int32_t n_steps, const mz_net* actor, int32_t sample, uint64_t noise_seed, uint64_t noise_step,
+                       const mz_net* critic, float* value_seq_dev, float* next_value_seq_dev, float* obs_dev, float* reward_dev,
+                       uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev, float* obs_seq_dev, float* actions_seq_dev,
+                       float* logp_seq_dev, void* stream);
+
 /* Per-env status words accumulated since the last call (then cleared). [N] i32. */
 int32_t mz_get_status(mz_handle* h, int32_t* status_dev, void* stream);
 

@@ -24,6 +24,7 @@ SYMBOLS = [
     "mz_set_goals", "mz_read_wave_phase_cycles", "mz_get_info", "mz_bind_env_goals", "mz_render", "mz_rollout",
     "mz_policy_act", "mz_rollout_policy", "mz_policy_sample", "mz_rollout_policy_sample",
     "mz_value", "mz_rollout_actor_critic", "mz_gae",
+    "mz_net_act", "mz_net_value", "mz_rollout_net",
 ]
 
 
@@ -31,6 +32,22 @@ class MzCritic(C.Structure):
     """`mz_critic` of include/mazestep.h: the critic of one mz_rollout_actor_critic call."""
     _fields_ = [("params_dev", C.c_void_p), ("env_stride", C.c_int64), ("hidden", C.c_int32), ("reserved", C.c_int32),
                 ("value_seq_dev", C.c_void_p), ("next_value_seq_dev", C.c_void_p)]
+
+
+ACT_TANH, ACT_RELU = 0, 1  # MZ_ACT_* (include/mazestep.h)
+
+
+class MzNet(C.Structure):
+    """`mz_net` of include/mazestep.h: a network of up to two hidden layers, actor or critic, of one mz_net_* call."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_hidden", C.c_int32), ("hidden", C.c_int32 * 2), ("activation", C.c_int32),
+                ("squash", C.c_int32), ("action_scale", C.c_double), ("params_dev", C.c_void_p), ("env_stride", C.c_int64)]
+
+
+def make_net(params_ptr, env_stride: int, widths, activation: int, squash: bool = False, action_scale: float = 1.0) -> MzNet:
+    """An MzNet with struct_size set; widths: a sequence of 0 .. 2 hidden widths."""
+    w = tuple(int(x) for x in widths)
+    return MzNet(C.sizeof(MzNet), len(w), (C.c_int32 * 2)(*(w + (0, 0))[:2]), int(activation), 1 if squash else 0, float(action_scale), params_ptr,
+                 int(env_stride))
 
 
 _lib = None
@@ -99,6 +116,12 @@ def load():
     lib.mz_rollout_actor_critic.restype = i32
     lib.mz_rollout_actor_critic.argtypes = [vp, i32, vp, C.c_int64, i32, i32, C.c_double, i32, u64, u64, C.POINTER(MzCritic), vp, vp, vp, vp, vp, vp,
                                             vp, vp, vp]
+    lib.mz_net_act.restype = i32
+    lib.mz_net_act.argtypes = [vp, C.POINTER(MzNet), i32, u64, u64, vp, vp, vp, vp]
+    lib.mz_net_value.restype = i32
+    lib.mz_net_value.argtypes = [vp, C.POINTER(MzNet), vp, vp, vp]
+    lib.mz_rollout_net.restype = i32
+    lib.mz_rollout_net.argtypes = [vp, i32, C.POINTER(MzNet), i32, u64, u64, C.POINTER(MzNet), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mz_gae.restype = i32
     lib.mz_gae.argtypes = [vp, i32, vp, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp]
     lib.mz_get_status.restype = i32

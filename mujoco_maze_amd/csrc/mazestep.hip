@@ -80,6 +80,35 @@ __global__ __launch_bounds__(256) void value_kernel(int n, int obs_dim, int hidd
   if (live && l == 0) values[row] = v;
 }
 
+// policy_act_kernel (sample == 0: key, env0 and logp are not read) and policy_sample_kernel (sample == 1) for a network of shape s
+// (mz_net_act; mz_rollout_net where it steps launch by launch): the same groups, a second LDS row per group for the second hidden
+// vector.  Kernels of their own beside the three above, whose code stays what it was.
+__global__ __launch_bounds__(256) void net_act_kernel(int n, int obs_dim, int nu, mzp_shape s, int squash, float action_scale,
+                                                      const float* __restrict__ params, long pstride, int sample, uint64_t key, uint64_t env0,
+                                                      const float* __restrict__ obs, float* __restrict__ actions, float* __restrict__ logp) {
+  __shared__ float hid[256 / MZ_POLICY_LANES][MZ_NET_MAX_HIDDEN_LAYERS][MZ_POLICY_MAX_HIDDEN];
+  const int l = (int)threadIdx.x % MZ_POLICY_LANES, grp = (int)threadIdx.x / MZ_POLICY_LANES;
+  size_t row = (size_t)blockIdx.x * (256 / MZ_POLICY_LANES) + grp;
+  const bool live = row < (size_t)n;
+  if (!live) row = (size_t)n - 1;
+  mzp_group_net_act(l, MZ_POLICY_LANES, params + row * pstride, obs_dim, nu, s, squash, action_scale, sample != 0, key, env0 + row,
+                    obs + row * obs_dim, hid[grp][0], hid[grp][1], actions + row * nu, live, live && logp ? logp + row : nullptr);
+}
+
+// value_kernel for a critic of shape s (mz_net_value; mz_rollout_net where it steps launch by launch)
+__global__ __launch_bounds__(256) void net_value_kernel(int n, int obs_dim, mzp_shape s, const float* __restrict__ vparams, long vstride,
+                                                        const float* __restrict__ obs, const float* __restrict__ final_obs,
+                                                        const uint8_t* __restrict__ done, float* __restrict__ values) {
+  __shared__ float hid[256 / MZ_POLICY_LANES][MZ_NET_MAX_HIDDEN_LAYERS][MZ_POLICY_MAX_HIDDEN];
+  const int l = (int)threadIdx.x % MZ_POLICY_LANES, grp = (int)threadIdx.x / MZ_POLICY_LANES;
+  size_t row = (size_t)blockIdx.x * (256 / MZ_POLICY_LANES) + grp;
+  const bool live = row < (size_t)n;
+  if (!live) row = (size_t)n - 1;
+  const float* x = (done && done[row] ? final_obs : obs) + row * obs_dim;
+  const float v = mzp_group_net_value(l, MZ_POLICY_LANES, vparams + row * vstride, obs_dim, s, x, hid[grp][0], hid[grp][1]);
+  if (live && l == 0) values[row] = v;
+}
+
 // mz_gae: one lane per env, rows [k][env] coalesced across the lanes; the scan of mz_gae.h (mzg_step) from the last step back.  The
 // four loads of a step do not depend on the carry: a block of MZ_GAE_DEPTH steps is loaded before its dependent chain runs.
 constexpr int MZ_GAE_DEPTH = 8;
@@ -734,6 +763,152 @@ int32_t mz_rollout_actor_critic(mz_handle* h, int32_t n_steps, const float* para
       if (critic->next_value_seq_dev) {
         value_launch(h, st, critic->params_dev, critic->env_stride, critic->hidden, obs_dev, h->auto_reset ? h->final_obs : NULL,
                      h->auto_reset ? done_dev + k * n : NULL, critic->next_value_seq_dev + k * n);
+        HIPCHK(h, hipGetLastError());
+      }
+      if (obs_seq_dev) HIPCHK(h, hipMemcpyAsync(obs_seq_dev + k * n * od, obs_dev, n * od * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
+  }
+  h->nsteps += n_steps;
+  return MZ_OK;
+}
+
+// the checks the three mz_net entries share; `which`: the argument's name ("actor" / "critic"), nout: nu or 1, stochastic: the
+// vector carries log_std[nu] behind the network.  MZ_OK or MZ_ERR_ARG with the message set.
+static int net_args(mz_handle* h, const char* who, const char* which, const mz_net* net, int nout, bool stochastic, bool is_critic) {
+  char msg[200];
+  auto fail = [&](const char* field, const char* why) {
+    snprintf(msg, sizeof(msg), "%s: %s%s %s", who, which, field, why);
+    return set_err(h, MZ_ERR_ARG, msg, hipSuccess);
+  };
+  if (!net) return fail("", "is NULL");
+  if (net->struct_size != sizeof(mz_net)) return fail("->struct_size", "must be sizeof(mz_net)");
+  if (net->n_hidden < 0 || net->n_hidden > MZ_NET_MAX_HIDDEN_LAYERS) return fail("->n_hidden", "must be 0 .. MZ_NET_MAX_HIDDEN_LAYERS (2)");
+  for (int k = 0; k < MZ_NET_MAX_HIDDEN_LAYERS; k++) {
+    const char* field = k ? "->hidden[1]" : "->hidden[0]";
+    if (k < net->n_hidden && (net->hidden[k] < 1 || net->hidden[k] > MZ_POLICY_MAX_HIDDEN)) return fail(field, "must be 1 .. MZ_POLICY_MAX_HIDDEN (64)");
+    if (k >= net->n_hidden && net->hidden[k] != 0) return fail(field, "must be 0: the layer is not in use");
+  }
+  if (net->activation != MZ_ACT_TANH && net->activation != MZ_ACT_RELU) return fail("->activation", "must be MZ_ACT_TANH (0) or MZ_ACT_RELU (1)");
+  if (net->squash != 0 && net->squash != 1) return fail("->squash", "must be 0 or 1");
+  if (is_critic && net->squash != 0) return fail("->squash", "must be 0: a critic is never squashed");
+  if (!net->params_dev) return fail("->params_dev", "is NULL");
+  const int64_t count = (int64_t)mzp_net_param_count(h->model.obs_dim, nout, mzp_shape{net->n_hidden, net->hidden[0], net->hidden[1], net->activation}) +
+                        (stochastic ? h->model.nu : 0);
+  if (net->env_stride != 0 && net->env_stride != count)
+    return fail("->env_stride", stochastic ? "must be 0 (one shared network) or count (one per env; log_std[nu] behind the network counts)"
+                                           : "must be 0 (one shared network) or count (one per env)");
+  return MZ_OK;
+}
+
+static mzp_shape net_shape(const mz_net* net) { return mzp_shape{net->n_hidden, net->hidden[0], net->hidden[1], net->activation}; }
+// a network the one-layer kernels evaluate: at most one hidden layer, tanh
+static bool net_shallow(const mz_net* net) { return net->n_hidden <= 1 && net->activation == MZ_ACT_TANH; }
+
+static void net_act_launch(mz_handle* h, hipStream_t st, const mz_net* actor, int sample, uint64_t noise_seed, uint64_t noise_step,
+                           const float* obs_dev, float* actions_dev, float* logp_dev) {
+  const int rows = 256 / MZ_POLICY_LANES;
+  hipLaunchKernelGGL(net_act_kernel, dim3((unsigned)((h->n + rows - 1) / rows)), dim3(256), 0, st, h->n, h->model.obs_dim, h->model.nu, net_shape(actor),
+                     actor->squash, (float)actor->action_scale, actor->params_dev, (long)actor->env_stride, sample,
+                     sample ? mzp_noise_key(noise_seed, noise_step) : 0, h->env0, obs_dev, actions_dev, sample ? logp_dev : NULL);
+}
+
+static void net_value_launch(mz_handle* h, hipStream_t st, const mz_net* critic, const float* obs_dev, const float* final_obs_dev,
+                             const uint8_t* done_dev, float* values_dev) {
+  const int rows = 256 / MZ_POLICY_LANES;
+  hipLaunchKernelGGL(net_value_kernel, dim3((unsigned)((h->n + rows - 1) / rows)), dim3(256), 0, st, h->n, h->model.obs_dim, net_shape(critic),
+                     critic->params_dev, (long)critic->env_stride, obs_dev, final_obs_dev, done_dev, values_dev);
+}
+
+int32_t mz_net_act(mz_handle* h, const mz_net* actor, int32_t sample, uint64_t noise_seed, uint64_t noise_step, const float* obs_dev,
+                   float* actions_dev, float* logp_dev, void* stream) {
+  if (!h) return MZ_ERR_ARG;
+  if (sample != 0 && sample != 1) return set_err(h, MZ_ERR_ARG, "mz_net_act: sample must be 0 or 1", hipSuccess);
+  if (!obs_dev || !actions_dev) return set_err(h, MZ_ERR_ARG, "mz_net_act: null array", hipSuccess);
+  const int rc = net_args(h, "mz_net_act", "actor", actor, h->model.nu, sample != 0, false);
+  if (rc != MZ_OK) return rc;
+  DeviceScope scope(h->device);
+  net_act_launch(h, (hipStream_t)stream, actor, sample, noise_seed, noise_step, obs_dev, actions_dev, logp_dev);
+  HIPCHK(h, hipGetLastError());
+  return MZ_OK;
+}
+
+int32_t mz_net_value(mz_handle* h, const mz_net* critic, const float* obs_dev, float* values_dev, void* stream) {
+  if (!h) return MZ_ERR_ARG;
+  if (!obs_dev || !values_dev) return set_err(h, MZ_ERR_ARG, "mz_net_value: null array", hipSuccess);
+  const int rc = net_args(h, "mz_net_value", "critic", critic, 1, false, true);
+  if (rc != MZ_OK) return rc;
+  DeviceScope scope(h->device);
+  net_value_launch(h, (hipStream_t)stream, critic, obs_dev, NULL, NULL, values_dev);
+  HIPCHK(h, hipGetLastError());
+  return MZ_OK;
+}
+
+// mz_rollout_actor_critic for networks described by mz_net (include/mazestep.h).  Fused handles evaluate both networks inside the
+// rollout kernels — the one-layer instantiations where both are at most one tanh hidden layer, the DEEP ones otherwise, which
+// compute the same bits for such a network —; every other handle runs the defining loop itself: net_value_kernel, net_act_kernel,
+// the step's own launches, net_value_kernel again with the final_obs row where the env finished under auto-reset.
+int32_t mz_rollout_net(mz_handle* h, int32_t n_steps, const mz_net* actor, int32_t sample, uint64_t noise_seed, uint64_t noise_step,
+                       const mz_net* critic, float* value_seq_dev, float* next_value_seq_dev, float* obs_dev, float* reward_dev,
+                       uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev, float* obs_seq_dev, float* actions_seq_dev,
+                       float* logp_seq_dev, void* stream) {
+  if (!h) return MZ_ERR_ARG;
+  if (sample != 0 && sample != 1) return set_err(h, MZ_ERR_ARG, "mz_rollout_net: sample must be 0 or 1", hipSuccess);
+  if (!obs_dev || !reward_dev || !done_dev) return set_err(h, MZ_ERR_ARG, "mz_rollout_net: null array", hipSuccess);
+  if (n_steps < 1 || n_steps > 65536) return set_err(h, MZ_ERR_ARG, "mz_rollout_net: n_steps must be 1 .. 65536", hipSuccess);
+  int rc = net_args(h, "mz_rollout_net", "actor", actor, h->model.nu, sample != 0, false);
+  if (rc != MZ_OK) return rc;
+  if (critic) {
+    rc = net_args(h, "mz_rollout_net", "critic", critic, 1, false, true);
+    if (rc != MZ_OK) return rc;
+    if (next_value_seq_dev && h->auto_reset && !h->final_obs)
+      return set_err(h, MZ_ERR_ARG, "mz_rollout_net: next_value_seq_dev under auto-reset needs a bound final_obs buffer (mz_bind_final_obs): "
+                                    "the terminal rows are valued there", hipSuccess);
+  } else {
+    value_seq_dev = next_value_seq_dev = NULL;
+  }
+  if (!sample) logp_seq_dev = NULL;
+  const size_t n = (size_t)h->n, od = (size_t)h->model.obs_dim, nu = (size_t)h->model.nu;
+  DeviceScope scope(h->device);
+  hipStream_t st = (hipStream_t)stream;
+  if (mzk_planar_rollout_fused(h)) {
+    if (net_shallow(actor) && (!critic || net_shallow(critic))) {
+      const float* p = actor->params_dev;
+      const long ps = (long)actor->env_stride;
+      const int H = actor->hidden[0], sq = actor->squash;
+      const float scale = (float)actor->action_scale;
+      if (critic) {
+        const mz_critic c{critic->params_dev, critic->env_stride, critic->hidden[0], 0, value_seq_dev, next_value_seq_dev};
+        HIPCHK(h, mzk_planar_rollout_actor_critic(h, st, n_steps, p, ps, H, sq, scale, sample, noise_seed, noise_step, &c, obs_dev, reward_dev, done_dev,
+                                                  goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, logp_seq_dev));
+      } else if (sample) {
+        HIPCHK(h, mzk_planar_rollout_policy_sample(h, st, n_steps, p, ps, H, sq, scale, noise_seed, noise_step, obs_dev, reward_dev, done_dev,
+                                                   goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, logp_seq_dev));
+      } else {
+        HIPCHK(h, mzk_planar_rollout_policy(h, st, n_steps, p, ps, H, sq, scale, obs_dev, reward_dev, done_dev, goal_idx_dev, info_dev, obs_seq_dev,
+                                            actions_seq_dev));
+      }
+    } else {
+      HIPCHK(h, mzk_planar_rollout_net(h, st, n_steps, actor, sample, noise_seed, noise_step, critic, value_seq_dev, next_value_seq_dev, obs_dev,
+                                       reward_dev, done_dev, goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, logp_seq_dev));
+    }
+    if (h->record) {  // the last step's row
+      const size_t tot = n * (od + 2), last = (size_t)(n_steps - 1) * n;
+      hipLaunchKernelGGL(pack_record_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, h->n, h->model.obs_dim, obs_dev, reward_dev + last, done_dev + last, h->record);
+      HIPCHK(h, hipGetLastError());
+    }
+  } else {
+    if (!actions_seq_dev && !h->policy_act) HIPCHK(h, hipMalloc(&h->policy_act, n * nu * sizeof(float)));
+    for (size_t k = 0; k < (size_t)n_steps; k++) {
+      float* a = actions_seq_dev ? actions_seq_dev + k * n * nu : h->policy_act;
+      if (value_seq_dev) net_value_launch(h, st, critic, obs_dev, NULL, NULL, value_seq_dev + k * n);
+      net_act_launch(h, st, actor, sample, noise_seed, noise_step + k, obs_dev, a, logp_seq_dev ? logp_seq_dev + k * n : NULL);
+      HIPCHK(h, hipGetLastError());
+      rc = step_launches(h, st, a, obs_dev, reward_dev + k * n, done_dev + k * n, goal_idx_dev ? goal_idx_dev + k * n : NULL,
+                         info_dev ? info_dev + k * n * 4 : NULL);
+      if (rc != MZ_OK) return rc;
+      if (next_value_seq_dev) {
+        net_value_launch(h, st, critic, obs_dev, h->auto_reset ? h->final_obs : NULL, h->auto_reset ? done_dev + k * n : NULL,
+                         next_value_seq_dev + k * n);
         HIPCHK(h, hipGetLastError());
       }
       if (obs_seq_dev) HIPCHK(h, hipMemcpyAsync(obs_seq_dev + k * n * od, obs_dev, n * od * sizeof(float), hipMemcpyDeviceToDevice, st));

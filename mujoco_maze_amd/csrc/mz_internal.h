@@ -107,6 +107,11 @@ hipError_t mzk_planar_rollout_actor_critic(mz_handle* h, hipStream_t st, int nst
                                            float action_scale, int sample, uint64_t noise_seed, uint64_t noise_step, const mz_critic* critic,
                                            float* obs, float* reward, uint8_t* done, int* goal_idx, float* info, float* obs_seq, float* actions_seq,
                                            float* logp_seq);
+// mz_rollout_net on the same handles where a network has two hidden layers or ReLU units: the same launches of the kernels' DEEP
+// instantiations, which evaluate networks of every shape mz_net describes (`actor`, `critic` — nullable — checked by the caller)
+hipError_t mzk_planar_rollout_net(mz_handle* h, hipStream_t st, int nsteps, const mz_net* actor, int sample, uint64_t noise_seed,
+                                  uint64_t noise_step, const mz_net* critic, float* value_seq, float* next_value_seq, float* obs, float* reward,
+                                  uint8_t* done, int* goal_idx, float* info, float* obs_seq, float* actions_seq, float* logp_seq);
 int mzk_planar_state_width(const mz_handle* h);  // coordinates per env of the state (NV)
 int mzk_planar_record_width(const mz_handle* h); // Point: floats per env-major record; 0 for the chains (SoA)
 

@@ -39,6 +39,15 @@
 // Critics (mz_value / mz_rollout_actor_critic; value_kernel in mazestep.hip, the CRT instantiations of the fused kernels, the host
 // build tests/critic_host): the same unit functions with nu = 1 and no squash — mzp_value_row, mzp_group_value below;
 // policy.py value_reference.
+//
+// Deeper networks (mz_net_act / mz_net_value / mz_rollout_net; the mzp_net_* functions below): 0, 1 or 2 hidden layers of 1 ..
+// MZ_POLICY_MAX_HIDDEN units each (mzp_shape), one activation for both — MZ_ACT_TANH: tanhf(acc), or MZ_ACT_RELU:
+// acc < 0.0f ? 0.0f : acc, a select that adds no rounding, keeps -0.0f and lets a NaN through (fmaxf would drop it).  Packed vector,
+// input-major as above; n_hidden 0 and 1 are the two layouts above, and
+//   n_hidden == 2                         W1t [obs_dim][H1], b1 [H1], W2t [H1][H2], b2 [H2], W3t [H2][nout], b3 [nout]
+// followed by log_std[nu] for a stochastic actor.  The same rules: one lane per unit, mzp_dot; a layer-2 unit reads the complete
+// layer-1 vector.  A one-layer tanh network through mzp_net_* runs the operations of the functions above in the same order and gives
+// the same bits; a ReLU network without squash is reproduced bit for bit by numpy at any depth (policy.py).
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -152,6 +161,73 @@ MZP_HD float mzp_value_row(const float* vpar, int obs_dim, int Hv, const float* 
   return mzp_output_pre(vpar, obs_dim, 1, Hv, Hv > 0 ? hid : x, 0);
 }
 
+// ------------------------------------------------------------------ networks of up to two hidden layers (mz_net_*: the head of this file)
+typedef struct mzp_shape {
+  int n_hidden, h1, h2;  // hidden layers in use and their widths (unused: 0)
+  int act;               // MZ_ACT_* of the hidden units
+} mzp_shape;
+
+MZP_HD int mzp_net_param_count(int obs_dim, int nout, mzp_shape s) {
+  if (s.n_hidden == 2) return obs_dim * s.h1 + s.h1 + s.h1 * s.h2 + s.h2 + s.h2 * nout + nout;
+  return mzp_param_count(obs_dim, nout, s.n_hidden == 1 ? s.h1 : 0);
+}
+
+MZP_HD float mzp_activate(float acc, int act) {
+  if (act == MZ_ACT_RELU) return acc < 0.0f ? 0.0f : acc;
+  return tanhf(acc);
+}
+
+// unit j of hidden layer `layer` (0: from the observation row, 1: from the complete first hidden vector) — `in` is that input row
+MZP_HD float mzp_net_hidden_unit(const float* par, int obs_dim, mzp_shape s, int layer, const float* in, int j) {
+  const float* W = layer ? par + (size_t)obs_dim * s.h1 + s.h1 : par;
+  const int nin = layer ? s.h1 : obs_dim, w = layer ? s.h2 : s.h1;
+  return mzp_activate(mzp_dot(W + j, w, W[(size_t)nin * w + j], in, nin), s.act);
+}
+
+// pre-squash sum of output unit u from the input row of the output layer: the observation or the last hidden vector
+MZP_HD float mzp_net_output_pre(const float* par, int obs_dim, int nout, mzp_shape s, const float* in, int u) {
+  const float* W = par;
+  int nin = obs_dim;
+  if (s.n_hidden >= 1) { W += (size_t)obs_dim * s.h1 + s.h1; nin = s.h1; }
+  if (s.n_hidden == 2) { W += (size_t)s.h1 * s.h2 + s.h2; nin = s.h2; }
+  return mzp_dot(W + u, nout, W[(size_t)nin * nout + u], in, nin);
+}
+
+// the hidden layers of one row, serially; returns the input row of the output layer (x, hid1 or hid2)
+MZP_HD const float* mzp_net_hidden_row(const float* par, int obs_dim, mzp_shape s, const float* x, float* hid1, float* hid2) {
+  if (s.n_hidden < 1) return x;
+  for (int j = 0; j < s.h1; j++) hid1[j] = mzp_net_hidden_unit(par, obs_dim, s, 0, x, j);
+  if (s.n_hidden < 2) return hid1;
+  for (int j = 0; j < s.h2; j++) hid2[j] = mzp_net_hidden_unit(par, obs_dim, s, 1, hid1, j);
+  return hid2;
+}
+
+// mzp_policy_row, mzp_sample_row and mzp_value_row for a network of shape s
+MZP_HD void mzp_net_policy_row(const float* par, int obs_dim, int nu, mzp_shape s, int squash, float action_scale, const float* x, float* act) {
+  float hid1[MZ_POLICY_MAX_HIDDEN], hid2[MZ_POLICY_MAX_HIDDEN];
+  const float* in = mzp_net_hidden_row(par, obs_dim, s, x, hid1, hid2);
+  for (int u = 0; u < nu; u++) {
+    const float acc = mzp_net_output_pre(par, obs_dim, nu, s, in, u);
+    act[u] = squash ? action_scale * tanhf(acc) : acc;
+  }
+}
+
+MZP_HD void mzp_net_sample_row(const float* par, int obs_dim, int nu, mzp_shape s, int squash, float action_scale, uint64_t noise_seed,
+                               uint64_t noise_step, uint64_t slot, const float* x, float* act, float* logp) {
+  float hid1[MZ_POLICY_MAX_HIDDEN], hid2[MZ_POLICY_MAX_HIDDEN];
+  const float* ls = par + mzp_net_param_count(obs_dim, nu, s);
+  const uint64_t key = mzp_noise_key(noise_seed, noise_step);
+  const float* in = mzp_net_hidden_row(par, obs_dim, s, x, hid1, hid2);
+  for (int u = 0; u < nu; u++)
+    act[u] = mzp_sample_unit(mzp_net_output_pre(par, obs_dim, nu, s, in, u), ls[u], mzp_eps(key, slot, u), squash, action_scale);
+  if (logp) *logp = mzp_logp(ls, nu, key, slot);
+}
+
+MZP_HD float mzp_net_value_row(const float* vpar, int obs_dim, mzp_shape s, const float* x) {
+  float hid1[MZ_POLICY_MAX_HIDDEN], hid2[MZ_POLICY_MAX_HIDDEN];
+  return mzp_net_output_pre(vpar, obs_dim, 1, s, mzp_net_hidden_row(vpar, obs_dim, s, x, hid1, hid2), 0);
+}
+
 #if defined(__HIPCC__)
 // hand-off between the lanes of a group inside one wavefront (the DevCtx::sync of mz_device.h: LDS operations of a wavefront
 // execute in order, so a wavefront-scope fence that pins the compiler's ordering is a complete phase boundary)
@@ -208,6 +284,53 @@ __device__ __forceinline__ float mzp_group_value(int l, int G, const float* vpar
   float v = 0.0f;
   // (two calls, not a select of the pointers: hid is LDS, x may be global memory)
   if (l == 0) v = Hv > 0 ? mzp_output_pre(vpar, obs_dim, 1, Hv, hid, 0) : mzp_output_pre(vpar, obs_dim, 1, Hv, x, 0);
+  return v;
+}
+
+// The hidden layers of a network of shape s on a group: lanes l, l + G, ... each own one unit of a layer; the first hidden vector
+// goes through `hid`, the second through `hid2` (LDS, MZ_POLICY_MAX_HIDDEN floats of this group each), with the group's phase
+// boundary behind each layer: a layer-2 unit reads the complete layer-1 vector.  Every lane of the group must make the call.
+__device__ __forceinline__ void mzp_group_net_hidden(int l, int G, const float* par, int obs_dim, mzp_shape s, const float* x, float* hid,
+                                                     float* hid2) {
+  if (s.n_hidden >= 1) {
+    for (int j = l; j < s.h1; j += G) hid[j] = mzp_net_hidden_unit(par, obs_dim, s, 0, x, j);
+    mzp_wave_sync();
+  }
+  if (s.n_hidden == 2) {
+    for (int j = l; j < s.h2; j += G) hid2[j] = mzp_net_hidden_unit(par, obs_dim, s, 1, hid, j);
+    mzp_wave_sync();
+  }
+}
+
+// pre-squash sum of output unit u behind mzp_group_net_hidden (three calls, not a select of the pointers: hid and hid2 are LDS, x may
+// be global memory)
+__device__ __forceinline__ float mzp_group_net_pre(const float* par, int obs_dim, int nout, mzp_shape s, const float* x, const float* hid,
+                                                   const float* hid2, int u) {
+  if (s.n_hidden == 2) return mzp_net_output_pre(par, obs_dim, nout, s, hid2, u);
+  if (s.n_hidden == 1) return mzp_net_output_pre(par, obs_dim, nout, s, hid, u);
+  return mzp_net_output_pre(par, obs_dim, nout, s, x, u);
+}
+
+// mzp_group_eval (sample == false: key, slot and logp are not read) and mzp_group_sample (sample == true) for a network of shape s
+__device__ __forceinline__ void mzp_group_net_act(int l, int G, const float* par, int obs_dim, int nu, mzp_shape s, int squash, float action_scale,
+                                                  bool sample, uint64_t key, uint64_t slot, const float* x, float* hid, float* hid2, float* act,
+                                                  bool store, float* logp) {
+  mzp_group_net_hidden(l, G, par, obs_dim, s, x, hid, hid2);
+  const float* ls = par + mzp_net_param_count(obs_dim, nu, s);
+  for (int u = l; u < nu; u += G) {
+    const float m = mzp_group_net_pre(par, obs_dim, nu, s, x, hid, hid2, u);
+    const float a = sample ? mzp_sample_unit(m, ls[u], mzp_eps(key, slot, u), squash, action_scale) : (squash ? action_scale * tanhf(m) : m);
+    if (store) act[u] = a;
+  }
+  if (sample && l == 0 && logp) *logp = mzp_logp(ls, nu, key, slot);
+}
+
+// mzp_group_value for a network of shape s: `hid` and `hid2` may be the rows the actor used, under the rule of mzp_group_value
+__device__ __forceinline__ float mzp_group_net_value(int l, int G, const float* vpar, int obs_dim, mzp_shape s, const float* x, float* hid,
+                                                     float* hid2) {
+  mzp_group_net_hidden(l, G, vpar, obs_dim, s, x, hid, hid2);
+  float v = 0.0f;
+  if (l == 0) v = mzp_group_net_pre(vpar, obs_dim, 1, s, x, hid, hid2, 0);
   return v;
 }
 #endif

@@ -261,19 +261,28 @@ struct PolicyCritic {
   float* value_seq;       // [nsteps][n] rows of the launch (nullable)
   float* next_value_seq;  // [nsteps][n] rows of the launch (nullable)
 };
-template <int NB, int NS, int G, bool SMP = false, bool CRT = false>
+// DEEP (mz_rollout_net where a network has two hidden layers or ReLU units): actor and critic are networks of the shapes in `sh`
+// (mzp_group_net_act / mzp_group_net_value: the unit functions net_act_kernel and net_value_kernel, mazestep.hip, run), and every
+// group has a second hidden row (phid[grp][1]) for the second hidden vector; `hidden` and cr.hidden are not read.  The hand-offs are
+// those of the one-layer kernel — the critic takes both hidden rows only after the actor's outputs have been handed over — plus the
+// phase boundary behind each hidden layer inside the group functions.  A template parameter, not a run-time depth: DEEP == false
+// compiles the source as it was, never reads `sh`, and its instantiations keep their registers and their LDS.
+struct PolicyShapes {
+  mzp_shape actor, critic;
+};
+template <int NB, int NS, int G, bool SMP = false, bool CRT = false, bool DEEP = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && NS == 0 && G == 32) ? 2 : 1))) void planar_policy_rollout_kernel(
     const PointDev* __restrict__ Pp, int n, PointState S, int nsteps, const float* __restrict__ params, long pstride, int hidden, int squash,
     float action_scale, float* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ done, int* __restrict__ goal_idx,
     float* __restrict__ info, float* __restrict__ obs_seq, float* __restrict__ actions_seq, int* __restrict__ status, int auto_reset,
-    uint64_t seed, uint64_t env0, float* __restrict__ final_obs, PolicyNoise ns, PolicyCritic cr) {
+    uint64_t seed, uint64_t env0, float* __restrict__ final_obs, PolicyNoise ns, PolicyCritic cr, PolicyShapes sh) {
   using D = PlanarDims<NB, NS>;
   constexpr int NV = D::NV, NOBS = D::NOBS, EPW = 64 / G;
   constexpr bool BARE = NB == 0 && NS == 0;
   __shared__ PointDev P;
   __shared__ PlanarScratch<NB, NS> scr[EPW];
   __shared__ float obuf[EPW][MZ_MAX_OBS];
-  __shared__ float phid[EPW][MZ_POLICY_MAX_HIDDEN];
+  __shared__ float phid[EPW][DEEP ? 2 : 1][MZ_POLICY_MAX_HIDDEN];
   __shared__ float pact[EPW][2];
   for (int i = threadIdx.x; i < (int)(sizeof(PointDev) / 4); i += blockDim.x) ((uint32_t*)&P)[i] = ((const uint32_t*)Pp)[i];
   __syncthreads();
@@ -292,20 +301,28 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && 
   uint32_t ep = st_ep(S, NV, env);
   const float* vpar = nullptr;
   float vcur = 0.0f;  // the group's first lane: V(the row in o)
+  auto value_of_row = [&]() -> float {  // every lane of the group; phid must be free (mzp_group_value)
+    if constexpr (DEEP) return mzp_group_net_value(cx.l, G, vpar, NOBS, sh.critic, o, phid[grp][0], phid[grp][DEEP ? 1 : 0]);
+    else return mzp_group_value(cx.l, G, vpar, NOBS, cr.hidden, o, phid[grp][0]);
+  };
   if constexpr (CRT) {
     vpar = cr.params + (size_t)env * cr.stride;
     cx.sync();  // the row in o is complete
-    vcur = mzp_group_value(cx.l, G, vpar, NOBS, cr.hidden, o, phid[grp]);
+    vcur = value_of_row();
   }
   for (int step = 0; step < nsteps; step++) {
     const size_t row = (size_t)step * n + env;
     cx.sync();  // the row in o is complete (CRT: and the critic is done with phid)
     if constexpr (CRT) { if (live && cx.l == 0 && cr.value_seq) cr.value_seq[row] = vcur; }
-    if constexpr (SMP)
+    if constexpr (DEEP)
+      mzp_group_net_act(cx.l, G, par, NOBS, 2, sh.actor, squash, action_scale, SMP, SMP ? mzp_noise_key(ns.seed, ns.step + (uint64_t)step) : 0,
+                        env0 + (uint64_t)env, o, phid[grp][0], phid[grp][DEEP ? 1 : 0], pact[grp], true,
+                        SMP && live && ns.logp_seq ? ns.logp_seq + row : nullptr);
+    else if constexpr (SMP)
       mzp_group_sample(cx.l, G, par, NOBS, 2, hidden, squash, action_scale, mzp_noise_key(ns.seed, ns.step + (uint64_t)step), env0 + (uint64_t)env, o,
-                       phid[grp], pact[grp], true, live && ns.logp_seq ? ns.logp_seq + row : nullptr);
+                       phid[grp][0], pact[grp], true, live && ns.logp_seq ? ns.logp_seq + row : nullptr);
     else
-      mzp_group_eval(cx.l, G, par, NOBS, 2, hidden, squash, action_scale, o, phid[grp], pact[grp], true);
+      mzp_group_eval(cx.l, G, par, NOBS, 2, hidden, squash, action_scale, o, phid[grp][0], pact[grp], true);
     cx.sync();
     const float a0 = pact[grp][0], a1 = pact[grp][1];
     if (live && cx.l == 0 && actions_seq) { actions_seq[row * 2] = a0; actions_seq[row * 2 + 1] = a1; }
@@ -342,7 +359,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && 
     }
     cx.sync();  // lane 0 has read the whole state and the terminal row
     if constexpr (CRT) {  // V(the row this step produced), before a reset overwrites it; the actor's outputs were handed over above
-      vcur = mzp_group_value(cx.l, G, vpar, NOBS, cr.hidden, o, phid[grp]);
+      vcur = value_of_row();
       if (live && cx.l == 0 && cr.next_value_seq) cr.next_value_seq[row] = vcur;
     }
     if (rst) {
@@ -360,7 +377,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && 
         if (olast) for (int i = cx.l; i < NOBS; i += G) olast[i] = o[i];
       }
       cx.sync();  // the new row is complete (CRT: and the group's first lane has read the terminal value's hidden units)
-      if constexpr (CRT) vcur = mzp_group_value(cx.l, G, vpar, NOBS, cr.hidden, o, phid[grp]);
+      if constexpr (CRT) vcur = value_of_row();
     }
     t = rst ? 0 : t_new;
     // the state as the next launch of planar_step_kernel would load it
@@ -610,17 +627,18 @@ __global__ __launch_bounds__(256) void swimmer_rollout_kernel(const SwimmerDev* 
 // CRT: as in planar_policy_rollout_kernel, on the rows in px — after every step the group's first lane puts the row the step produced
 // there (the fp32 row swimmer_store_row writes to final_obs when the env is about to reset: rows are NO floats apart here, so both
 // are o[0 .. NO - 1]), the group values it, and after a reset the new episode's first row follows and is valued once more.
-template <int NL, int NB, int G, bool SMP = false, bool CRT = false>
+// DEEP: as in planar_policy_rollout_kernel; the second hidden row takes the block's LDS from 20 KB to 36 KB.
+template <int NL, int NB, int G, bool SMP = false, bool CRT = false, bool DEEP = false>
 __global__ __launch_bounds__(256) void swimmer_policy_rollout_kernel(const SwimmerDev* __restrict__ Pp, int n, PointState S, int nsteps,
                                                                       const float* __restrict__ params, long pstride, int hidden, int squash,
                                                                       float action_scale, float* __restrict__ obs, float* __restrict__ reward,
                                                                       uint8_t* __restrict__ done, int* __restrict__ goal_idx, float* __restrict__ info,
                                                                       float* __restrict__ obs_seq, float* __restrict__ actions_seq, int* __restrict__ status,
                                                                       int auto_reset, uint64_t seed, uint64_t env0, float* __restrict__ final_obs,
-                                                                      PolicyNoise ns, PolicyCritic cr) {
+                                                                      PolicyNoise ns, PolicyCritic cr, PolicyShapes sh) {
   constexpr int NR = NL + 2, NV = NR + NB, NH = NL - 1, NOMAX = 2 * NV + 4, GPB = 256 / G;
   __shared__ float px[GPB][NOMAX];
-  __shared__ float phid[GPB][MZ_POLICY_MAX_HIDDEN];
+  __shared__ float phid[GPB][DEEP ? 2 : 1][MZ_POLICY_MAX_HIDDEN];
   __shared__ float pact[GPB][NH > 0 ? NH : 1];
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   int env = gid / G;
@@ -641,20 +659,28 @@ __global__ __launch_bounds__(256) void swimmer_policy_rollout_kernel(const Swimm
   const int lane0 = (int)(threadIdx.x & 63u) - cx.l;
   const float* vpar = nullptr;
   float vcur = 0.0f;  // the group's first lane: V(the row in x)
+  auto value_of_row = [&]() -> float {  // every lane of the group; phid must be free (mzp_group_value)
+    if constexpr (DEEP) return mzp_group_net_value(cx.l, G, vpar, NO, sh.critic, x, phid[grp][0], phid[grp][DEEP ? 1 : 0]);
+    else return mzp_group_value(cx.l, G, vpar, NO, cr.hidden, x, phid[grp][0]);
+  };
   if constexpr (CRT) {
     vpar = cr.params + (size_t)env * cr.stride;
     mzp_wave_sync();  // the row in x is complete
-    vcur = mzp_group_value(cx.l, G, vpar, NO, cr.hidden, x, phid[grp]);
+    vcur = value_of_row();
   }
   for (int step = 0; step < nsteps; step++) {
     const size_t row = (size_t)step * n + env;
     mzp_wave_sync();  // the row in x is complete (CRT: and the critic is done with phid)
     if constexpr (CRT) { if (live && cr.value_seq) cr.value_seq[row] = vcur; }
-    if constexpr (SMP)
+    if constexpr (DEEP)
+      mzp_group_net_act(cx.l, G, par, NO, NH, sh.actor, squash, action_scale, SMP, SMP ? mzp_noise_key(ns.seed, ns.step + (uint64_t)step) : 0,
+                        env0 + (uint64_t)env, x, phid[grp][0], phid[grp][DEEP ? 1 : 0], pact[grp], true,
+                        SMP && live && ns.logp_seq ? ns.logp_seq + row : nullptr);
+    else if constexpr (SMP)
       mzp_group_sample(cx.l, G, par, NO, NH, hidden, squash, action_scale, mzp_noise_key(ns.seed, ns.step + (uint64_t)step), env0 + (uint64_t)env, x,
-                       phid[grp], pact[grp], true, live && ns.logp_seq ? ns.logp_seq + row : nullptr);
+                       phid[grp][0], pact[grp], true, live && ns.logp_seq ? ns.logp_seq + row : nullptr);
     else
-      mzp_group_eval(cx.l, G, par, NO, NH, hidden, squash, action_scale, x, phid[grp], pact[grp], true);
+      mzp_group_eval(cx.l, G, par, NO, NH, hidden, squash, action_scale, x, phid[grp][0], pact[grp], true);
     mzp_wave_sync();
     for (int k = 0; k < NH; k++) af[k] = pact[grp][k];
     if (live && actions_seq) for (int k = 0; k < NH; k++) actions_seq[row * NH + k] = af[k];
@@ -686,7 +712,7 @@ __global__ __launch_bounds__(256) void swimmer_policy_rollout_kernel(const Swimm
         for (int k = 0; k < NOMAX; k++) if (k < NO) x[k] = o[k];
       }
       mzp_wave_sync();
-      vcur = mzp_group_value(cx.l, G, vpar, NO, cr.hidden, x, phid[grp]);
+      vcur = value_of_row();
       if (live && cr.next_value_seq) cr.next_value_seq[row] = vcur;
     }
     if (rst) {
@@ -711,7 +737,7 @@ __global__ __launch_bounds__(256) void swimmer_policy_rollout_kernel(const Swimm
           for (int k = 0; k < NOMAX; k++) if (k < NO) x[k] = o[k];
         }
         mzp_wave_sync();
-        vcur = mzp_group_value(cx.l, G, vpar, NO, cr.hidden, x, phid[grp]);
+        vcur = value_of_row();
       }
     } else {
       if (lead) {
@@ -935,11 +961,13 @@ hipError_t mzk_planar_rollout(mz_handle* h, hipStream_t st, int nsteps, const fl
 // the fused handles: mzk_planar_rollout's launches with the policy in place of the action tensor.  Every launch writes obs_dev at
 // its last step, and the next one reads its first observation there — and continues at noise_step + the steps done so far.
 // CRT (mz_rollout_actor_critic with a critic): `critic` holds the critic's parameters and the call's value_seq / next_value_seq.
-template <bool SMP, bool CRT = false>
+// DEEP (mz_rollout_net with a network of two hidden layers or ReLU units): `shapes` holds both networks' shapes.
+template <bool SMP, bool CRT = false, bool DEEP = false>
 static hipError_t planar_rollout_policy_launches(mz_handle* h, hipStream_t st, int nsteps, const float* params_dev, long pstride, int hidden,
                                                  int squash, float action_scale, float* obs_dev, float* reward_dev, uint8_t* done_dev,
                                                  int* goal_idx_dev, float* info_dev, float* obs_seq_dev, float* actions_seq_dev, PolicyNoise noise,
-                                                 PolicyCritic critic = PolicyCritic{nullptr, 0, 0, nullptr, nullptr}) {
+                                                 PolicyCritic critic = PolicyCritic{nullptr, 0, 0, nullptr, nullptr},
+                                                 PolicyShapes shapes = PolicyShapes{{0, 0, 0, 0}, {0, 0, 0, 0}}) {
   PointState S{h->state, h->pt_t, h->pt_ep, h->pt_rec};
   const size_t n = (size_t)h->n, od = (size_t)h->model.obs_dim, nu = (size_t)h->model.nu;
   for (int k0 = 0; k0 < nsteps; k0 += MZ_ROLLOUT_CHUNK) {
@@ -955,9 +983,9 @@ static hipError_t planar_rollout_policy_launches(mz_handle* h, hipStream_t st, i
                           critic.next_value_seq ? critic.next_value_seq + k0 * n : nullptr};
     if (h->robot == MZ_ROBOT_SWIMMER) {
 #define MZ_SW_ROLL(NL, NB)                                                                                                          \
-  hipLaunchKernelGGL((swimmer_policy_rollout_kernel<NL, NB, (NL <= 4 ? 4 : 8), SMP, CRT>), dim3((unsigned)((n * (NL <= 4 ? 4 : 8) + sw_bd - 1) / sw_bd)), dim3(sw_bd), 0, st, \
+  hipLaunchKernelGGL((swimmer_policy_rollout_kernel<NL, NB, (NL <= 4 ? 4 : 8), SMP, CRT, DEEP>), dim3((unsigned)((n * (NL <= 4 ? 4 : 8) + sw_bd - 1) / sw_bd)), dim3(sw_bd), 0, st, \
                      h->swimmer_dev, h->n, S, ks, params_dev, pstride, hidden, squash, action_scale, obs_dev, rew, dn, gi, inf, oseq, aseq, h->status,         \
-                     h->auto_reset, h->seed, h->env0, h->final_obs, ns, cr)
+                     h->auto_reset, h->seed, h->env0, h->final_obs, ns, cr, shapes)
       const int bd = h->swimmer.nblock ? h->swimmer.nbdof : 0;
       const unsigned sw_bd = 64u * (unsigned)(h->wpb_set ? h->waves_per_block : 4);
       if (h->swimmer.nlink == 3) { if (bd == 3) MZ_SW_ROLL(3, 3); else if (bd == 2) MZ_SW_ROLL(3, 2); else MZ_SW_ROLL(3, 0); }
@@ -968,8 +996,8 @@ static hipError_t planar_rollout_policy_launches(mz_handle* h, hipStream_t st, i
 #undef MZ_SW_ROLL
     } else {
 #define MZ_PLANAR_ROLL(NB, NS, G)                                                                                                      \
-  hipLaunchKernelGGL((planar_policy_rollout_kernel<NB, NS, G, SMP, CRT>), dim3((h->n + 64 / G - 1) / (64 / G)), dim3(64), 0, st, h->point_dev, h->n, S, ks, params_dev, \
-                     pstride, hidden, squash, action_scale, obs_dev, rew, dn, gi, inf, oseq, aseq, h->status, h->auto_reset, h->seed, h->env0, h->final_obs, ns, cr)
+  hipLaunchKernelGGL((planar_policy_rollout_kernel<NB, NS, G, SMP, CRT, DEEP>), dim3((h->n + 64 / G - 1) / (64 / G)), dim3(64), 0, st, h->point_dev, h->n, S, ks, params_dev, \
+                     pstride, hidden, squash, action_scale, obs_dev, rew, dn, gi, inf, oseq, aseq, h->status, h->auto_reset, h->seed, h->env0, h->final_obs, ns, cr, shapes)
       if (h->point.nball) MZ_PLANAR_ROLL(0, 1, 32);
       else switch (h->point.nblock) {
         case 0: {
@@ -1017,6 +1045,26 @@ hipError_t mzk_planar_rollout_actor_critic(mz_handle* h, hipStream_t st, int nst
                                                       PolicyNoise{noise_seed, noise_step, logp_seq_dev}, cr);
   return planar_rollout_policy_launches<false, true>(h, st, nsteps, params_dev, pstride, hidden, squash, action_scale, obs_dev, reward_dev, done_dev,
                                                      goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, PolicyNoise{0, 0, nullptr}, cr);
+}
+
+hipError_t mzk_planar_rollout_net(mz_handle* h, hipStream_t st, int nsteps, const mz_net* actor, int sample, uint64_t noise_seed,
+                                  uint64_t noise_step, const mz_net* critic, float* value_seq_dev, float* next_value_seq_dev, float* obs_dev,
+                                  float* reward_dev, uint8_t* done_dev, int* goal_idx_dev, float* info_dev, float* obs_seq_dev,
+                                  float* actions_seq_dev, float* logp_seq_dev) {
+  const PolicyNoise ns = sample ? PolicyNoise{noise_seed, noise_step, logp_seq_dev} : PolicyNoise{0, 0, nullptr};
+  PolicyShapes sh{{actor->n_hidden, actor->hidden[0], actor->hidden[1], actor->activation}, {0, 0, 0, 0}};
+  PolicyCritic cr{nullptr, 0, 0, nullptr, nullptr};
+  if (critic) {
+    sh.critic = mzp_shape{critic->n_hidden, critic->hidden[0], critic->hidden[1], critic->activation};
+    cr = PolicyCritic{critic->params_dev, (long)critic->env_stride, 0, value_seq_dev, next_value_seq_dev};
+  }
+#define MZ_NET_ROLL(SMP, CRT)                                                                                                               \
+  planar_rollout_policy_launches<SMP, CRT, true>(h, st, nsteps, actor->params_dev, (long)actor->env_stride, 0, actor->squash,               \
+                                                 (float)actor->action_scale, obs_dev, reward_dev, done_dev, goal_idx_dev, info_dev, obs_seq_dev, \
+                                                 actions_seq_dev, ns, cr, sh)
+  if (critic) return sample ? MZ_NET_ROLL(true, true) : MZ_NET_ROLL(false, true);
+  return sample ? MZ_NET_ROLL(true, false) : MZ_NET_ROLL(false, false);
+#undef MZ_NET_ROLL
 }
 
 hipError_t mzk_planar_reset(mz_handle* h, hipStream_t st, const uint8_t* mask_dev, uint64_t seed, float* obs_dev) {

@@ -459,15 +459,21 @@ class VecMazeEnv:
             info["final_observation"] = self._final_obs
         return self._obs, buf["reward"], buf["done"], info
 
-    def _policy_params(self, params, hidden: int, stochastic: bool = False):
+    @staticmethod
+    def _net_kind(hidden, activation: str, what: str = "hidden"):
+        """(widths, activation index, legacy) of a network given as `hidden` / `activation` (policy.net_shape); legacy: an int
+        `hidden` with tanh, which the entries without mz_net take."""
+        from mujoco_maze_amd import policy
+
+        widths, act = policy.net_shape(hidden, activation, what)
+        return widths, act, bool(np.ndim(hidden) == 0 and act == 0)
+
+    def _policy_params(self, params, hidden, stochastic: bool = False):
         """params as a contiguous float32 device tensor [npar] or [N, npar] (stochastic: npar_s = npar + nu, log_std behind the
         network); returns (tensor, param_env_stride)."""
         from mujoco_maze_amd import policy
 
         torch = self._torch
-        hidden = int(hidden)
-        if not 0 <= hidden <= policy.MAX_HIDDEN:
-            raise ValueError(f"hidden must be 0 .. {policy.MAX_HIDDEN}, got {hidden}")
         npar = policy.param_count(self.obs_dim, self.nu, hidden, stochastic)
         p = params if torch.is_tensor(params) else torch.as_tensor(np.asarray(params, dtype=np.float32), device=self.device)
         if p.dtype != torch.float32 or not p.is_contiguous() or p.device != self.device:
@@ -486,20 +492,30 @@ class VecMazeEnv:
             o = o.to(device=self.device, dtype=torch.float32).contiguous()
         return o
 
-    def policy_act(self, params, obs=None, hidden: int = 0, squash: bool = False, action_scale: float = 1.0):
+    def policy_act(self, params, obs=None, hidden=0, squash: bool = False, action_scale: float = 1.0, activation: str = "tanh"):
         """Actions [N, nu] of a small policy evaluated on the device (mz_policy_act): affine (`hidden=0`) or one tanh hidden layer of
         up to 64 units; `squash` makes the output action_scale * tanh(.).  params: float32 [npar] (one policy for all envs) or
         [N, npar] (one per env), packed by `mujoco_maze_amd.policy.pack` / `pack_linear`; obs: [N, obs_dim], default the env's last
-        returned observation.  The actions are not clamped (step() clamps where the reference does).  A new tensor per call."""
+        returned observation.  The actions are not clamped (step() clamps where the reference does).  A new tensor per call.
+
+        `hidden` may also be a sequence of one or two widths, e.g. `(64, 64)` (params packed by `policy.pack_mlp`), and
+        `activation="relu"` makes the hidden units ReLU instead of tanh, one choice for both layers (mz_net_act)."""
+        widths, act, legacy = self._net_kind(hidden, activation)
         p, stride = self._policy_params(params, hidden)
         o = self._obs if obs is None else self._policy_obs(obs)
         out = self._torch.empty((self.num_envs, self.nu), dtype=self._torch.float32, device=self.device)
-        rc = self._lib.mz_policy_act(self._h, _ptr(p), stride, int(hidden), 1 if squash else 0, float(action_scale), _ptr(o), _ptr(out), self._stream())
-        _capi.check(self._lib, self._h, rc, "mz_policy_act")
+        if legacy:
+            rc = self._lib.mz_policy_act(self._h, _ptr(p), stride, int(hidden), 1 if squash else 0, float(action_scale), _ptr(o), _ptr(out), self._stream())
+            _capi.check(self._lib, self._h, rc, "mz_policy_act")
+        else:
+            net = _capi.make_net(_ptr(p), stride, widths, act, squash, action_scale)
+            rc = self._lib.mz_net_act(self._h, C.byref(net), 0, 0, 0, _ptr(o), _ptr(out), None, self._stream())
+            _capi.check(self._lib, self._h, rc, "mz_net_act")
         return out
 
-    def rollout_policy(self, params, steps: int, hidden: int = 0, squash: bool = False, action_scale: float = 1.0, obs=None,
-                       return_obs: bool = False, return_actions: bool = False, value_params=None, value_hidden: int = 0, gae=None):
+    def rollout_policy(self, params, steps: int, hidden=0, squash: bool = False, action_scale: float = 1.0, obs=None,
+                       return_obs: bool = False, return_actions: bool = False, value_params=None, value_hidden=0, gae=None,
+                       activation: str = "tanh", value_activation: str = "tanh"):
         """K = `steps` closed-loop steps in one call: a = policy(obs); obs, reward, done = step(a) — exactly what K times
         (`policy_act`, `step`) give, state and outputs bit for bit.  params / hidden / squash / action_scale as in `policy_act`.
         The policy acts first on the env's last returned observation (what reset / step / rollout left in the observation buffer),
@@ -514,10 +530,12 @@ class VecMazeEnv:
         host has work between steps (Python reward()/termination() overrides; per-env goals under auto-reset): there this method
         loops `policy_act` + `step` itself.
 
-        value_params / value_hidden / gae: a critic evaluated along the way and the advantages from it, see `rollout_policy_sample`."""
-        if value_params is not None or gae is not None:
+        value_params / value_hidden / gae: a critic evaluated along the way and the advantages from it, see `rollout_policy_sample`.
+        hidden / activation as in `policy_act`, value_hidden / value_activation as in `value`: a network with two hidden layers or
+        ReLU units, actor or critic, makes the call one mz_rollout_net."""
+        if value_params is not None or gae is not None or not self._net_kind(hidden, activation)[2]:
             return self._rollout_actor_critic(False, params, steps, hidden, squash, action_scale, obs, None, None, return_obs, return_actions,
-                                              value_params, value_hidden, gae)
+                                              value_params, value_hidden, gae, activation, value_activation)
         torch, n = self._torch, self.num_envs
         p, stride = self._policy_params(params, hidden)
         K = int(steps)
@@ -566,8 +584,8 @@ class VecMazeEnv:
             step = int(noise_step)
         return C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), C.c_uint64(step & 0xFFFFFFFFFFFFFFFF)
 
-    def policy_sample(self, params, obs=None, hidden: int = 0, squash: bool = False, action_scale: float = 1.0, noise_seed: Optional[int] = None,
-                      noise_step: Optional[int] = None):
+    def policy_sample(self, params, obs=None, hidden=0, squash: bool = False, action_scale: float = 1.0, noise_seed: Optional[int] = None,
+                      noise_step: Optional[int] = None, activation: str = "tanh"):
         """One draw from a diagonal-Gaussian policy on the device (mz_policy_sample): (actions [N, nu], logp [N]).  params: float32
         [npar_s] or [N, npar_s], the vector of `policy_act` followed by log_std [nu] (`policy.pack(..., log_std=)`).  With m the
         network's pre-squash output, a = m + exp(log_std) * eps, or action_scale * tanh(.) of that with `squash`; logp is the density
@@ -576,21 +594,30 @@ class VecMazeEnv:
         eps is a pure function of (noise_seed, noise_step, global env slot, action index) — `policy.noise` —, so a draw does not
         depend on the batch size or on how a batch is sharded.  noise_seed defaults to the seed of the last `reset(seed=...)`, else the
         constructor's; noise_step to an env-held counter that starts at 0 (again after `reset(seed=...)`) and advances by 1 per call
-        and by K per `rollout_policy_sample`.  Explicit values are used as given and leave the counter alone."""
+        and by K per `rollout_policy_sample`.  Explicit values are used as given and leave the counter alone.
+
+        hidden / activation as in `policy_act`; the noise and logp do not depend on the network's shape."""
+        widths, act, legacy = self._net_kind(hidden, activation)
         p, stride = self._policy_params(params, hidden, stochastic=True)
         o = self._obs if obs is None else self._policy_obs(obs)
         torch = self._torch
         out = torch.empty((self.num_envs, self.nu), dtype=torch.float32, device=self.device)
         logp = torch.empty(self.num_envs, dtype=torch.float32, device=self.device)
         seed, step = self._noise_args(noise_seed, noise_step, 1)
-        rc = self._lib.mz_policy_sample(self._h, _ptr(p), stride, int(hidden), 1 if squash else 0, float(action_scale), seed, step, _ptr(o), _ptr(out),
-                                        _ptr(logp), self._stream())
-        _capi.check(self._lib, self._h, rc, "mz_policy_sample")
+        if legacy:
+            rc = self._lib.mz_policy_sample(self._h, _ptr(p), stride, int(hidden), 1 if squash else 0, float(action_scale), seed, step, _ptr(o), _ptr(out),
+                                            _ptr(logp), self._stream())
+            _capi.check(self._lib, self._h, rc, "mz_policy_sample")
+        else:
+            net = _capi.make_net(_ptr(p), stride, widths, act, squash, action_scale)
+            rc = self._lib.mz_net_act(self._h, C.byref(net), 1, seed, step, _ptr(o), _ptr(out), _ptr(logp), self._stream())
+            _capi.check(self._lib, self._h, rc, "mz_net_act")
         return out, logp
 
-    def rollout_policy_sample(self, params, steps: int, hidden: int = 0, squash: bool = False, action_scale: float = 1.0, obs=None,
+    def rollout_policy_sample(self, params, steps: int, hidden=0, squash: bool = False, action_scale: float = 1.0, obs=None,
                               noise_seed: Optional[int] = None, noise_step: Optional[int] = None, return_obs: bool = False,
-                              return_actions: bool = False, value_params=None, value_hidden: int = 0, gae=None):
+                              return_actions: bool = False, value_params=None, value_hidden=0, gae=None, activation: str = "tanh",
+                              value_activation: str = "tanh"):
         """K = `steps` closed-loop steps with a sampled action each, in one call: exactly what K times (`policy_sample` with
         noise_step + k, `step`) give, state and outputs bit for bit.  Everything as in `rollout_policy`, plus info["logp"] [K, N], the
         log-probabilities of the draws (see `policy_sample`); info["actions"] [K, N, nu] with `return_actions` holds the sampled
@@ -606,10 +633,14 @@ class VecMazeEnv:
         info["advantages"] and info["returns"] [K, N] (`gae`).  One mz_rollout_actor_critic call (the critic runs inside the fused
         kernels, on the row that is on chip anyway) plus one mz_gae call; the critic changes nothing else the call returns.  Where
         this method loops itself it loops `value` + `policy_sample` + `step` + `value`, with the terminal rows taken from
-        info["final_observation"]."""
-        if value_params is not None or gae is not None:
+        info["final_observation"].
+
+        hidden / activation as in `policy_act`, value_hidden / value_activation as in `value`: `hidden=(64, 64)`,
+        `value_hidden=(64, 64)` is the default network of PPO / A2C code.  A network with two hidden layers or ReLU units, actor or
+        critic, makes the call one mz_rollout_net — the same loop, the same fused kernels on the Point, Swimmer and Reacher."""
+        if value_params is not None or gae is not None or not self._net_kind(hidden, activation)[2]:
             return self._rollout_actor_critic(True, params, steps, hidden, squash, action_scale, obs, noise_seed, noise_step, return_obs,
-                                              return_actions, value_params, value_hidden, gae)
+                                              return_actions, value_params, value_hidden, gae, activation, value_activation)
         torch, n = self._torch, self.num_envs
         p, stride = self._policy_params(params, hidden, stochastic=True)
         K = int(steps)
@@ -650,14 +681,12 @@ class VecMazeEnv:
             info["final_observation"] = self._final_obs
         return self._obs, buf["reward"], buf["done"], info
 
-    def _value_params(self, value_params, hidden: int):
+    def _value_params(self, value_params, hidden):
         """A critic's parameters as a contiguous float32 device tensor [nvpar] or [N, nvpar]; returns (tensor, env_stride)."""
         from mujoco_maze_amd import policy
 
         torch = self._torch
-        hidden = int(hidden)
-        if not 0 <= hidden <= policy.MAX_HIDDEN:
-            raise ValueError(f"the critic's hidden must be 0 .. {policy.MAX_HIDDEN}, got {hidden}")
+        policy.net_shape(hidden, what="the critic's hidden")
         npar = policy.param_count(self.obs_dim, 1, hidden)
         p = value_params if torch.is_tensor(value_params) else torch.as_tensor(np.asarray(value_params, dtype=np.float32), device=self.device)
         if p.dtype != torch.float32 or not p.is_contiguous() or p.device != self.device:
@@ -667,16 +696,23 @@ class VecMazeEnv:
                              f"{self.obs_dim}, hidden {hidden}, got {tuple(p.shape)}")
         return p, (npar if p.dim() == 2 else 0)
 
-    def value(self, value_params, obs=None, hidden: int = 0):
+    def value(self, value_params, obs=None, hidden=0, activation: str = "tanh"):
         """Values [N] of a small critic evaluated on the device (mz_value): a policy of `policy_act` with one output, never squashed —
         affine (`hidden=0`) or one tanh hidden layer of up to 64 units.  value_params: float32 [nvpar] (one critic for all envs) or
         [N, nvpar] (one per env), nvpar = policy.param_count(obs_dim, 1, hidden), packed by `policy.pack` / `pack_linear` with
-        nu = 1; obs: [N, obs_dim], default the env's last returned observation.  A new tensor per call."""
+        nu = 1; obs: [N, obs_dim], default the env's last returned observation.  A new tensor per call.  `hidden` may also be a
+        sequence of one or two widths (`policy.pack_mlp`), `activation="relu"` makes the hidden units ReLU (mz_net_value)."""
+        widths, act, legacy = self._net_kind(hidden, activation, "the critic's hidden")
         p, stride = self._value_params(value_params, hidden)
         o = self._obs if obs is None else self._policy_obs(obs)
         out = self._torch.empty(self.num_envs, dtype=self._torch.float32, device=self.device)
-        rc = self._lib.mz_value(self._h, _ptr(p), stride, int(hidden), _ptr(o), _ptr(out), self._stream())
-        _capi.check(self._lib, self._h, rc, "mz_value")
+        if legacy:
+            rc = self._lib.mz_value(self._h, _ptr(p), stride, int(hidden), _ptr(o), _ptr(out), self._stream())
+            _capi.check(self._lib, self._h, rc, "mz_value")
+        else:
+            net = _capi.make_net(_ptr(p), stride, widths, act)
+            rc = self._lib.mz_net_value(self._h, C.byref(net), _ptr(o), _ptr(out), self._stream())
+            _capi.check(self._lib, self._h, rc, "mz_net_value")
         return out
 
     def gae(self, rewards, dones, values, next_values, gamma: float = 0.99, lam: float = 0.95, out=None):
@@ -708,16 +744,22 @@ class VecMazeEnv:
         return adv, ret
 
     def _rollout_actor_critic(self, sample: bool, params, steps, hidden, squash, action_scale, obs, noise_seed, noise_step, return_obs,
-                              return_actions, value_params, value_hidden, gae):
-        """rollout_policy (sample False) / rollout_policy_sample (sample True) with a critic: one mz_rollout_actor_critic call, or the
-        defining loop where the host has work between steps."""
+                              return_actions, value_params, value_hidden, gae, activation="tanh", value_activation="tanh"):
+        """rollout_policy (sample False) / rollout_policy_sample (sample True) with a critic, or with a network that needs mz_net
+        (then the critic is optional): one mz_rollout_actor_critic or mz_rollout_net call, or the defining loop where the host has
+        work between steps."""
         torch, n = self._torch, self.num_envs
-        if value_params is None:
+        with_critic = value_params is not None
+        if gae is not None and not with_critic:
             raise ValueError("gae=(gamma, lam) needs a critic: pass value_params")
         if gae is not None:
             gamma, lam = (float(x) for x in gae)
+        widths, act, legacy = self._net_kind(hidden, activation)
         p, stride = self._policy_params(params, hidden, stochastic=sample)
-        vp, vstride = self._value_params(value_params, value_hidden)
+        if with_critic:
+            vwidths, vact, vlegacy = self._net_kind(value_hidden, value_activation, "the critic's hidden")
+            vp, vstride = self._value_params(value_params, value_hidden)
+            legacy = legacy and vlegacy
         K = int(steps)
         if not 1 <= K <= 65536:
             raise ValueError(f"a rollout takes 1 .. 65536 steps, got {K}")
@@ -728,27 +770,38 @@ class VecMazeEnv:
         buf = self._rollout_buffers(K, return_obs)
         if return_actions and "actions" not in buf:
             buf["actions"] = torch.empty((K, n, self.nu), dtype=torch.float32, device=self.device)
-        for key in (("logp",) if sample else ()) + ("values", "next_values") + (("advantages", "returns") if gae is not None else ()):
+        for key in (("logp",) if sample else ()) + (("values", "next_values") if with_critic else ()) + (("advantages", "returns") if gae is not None else ()):
             if key not in buf:
                 buf[key] = torch.empty((K, n), dtype=torch.float32, device=self.device)
         seed, step = self._noise_args(noise_seed, noise_step, K) if sample else (C.c_uint64(0), C.c_uint64(0))
         if self._host_rewards or (self._env_goals is not None and self._auto_reset):
             for k in range(K):
-                buf["values"][k] = self.value(vp, None, value_hidden)
+                if with_critic:
+                    buf["values"][k] = self.value(vp, None, value_hidden, value_activation)
                 if sample:
-                    a, buf["logp"][k] = self.policy_sample(p, None, hidden, squash, action_scale, seed.value, step.value + k)
+                    a, buf["logp"][k] = self.policy_sample(p, None, hidden, squash, action_scale, seed.value, step.value + k, activation)
                 else:
-                    a = self.policy_act(p, None, hidden, squash, action_scale)
+                    a = self.policy_act(p, None, hidden, squash, action_scale, activation)
                 o, rew, done, inf = self.step(a)
                 buf["reward"][k], buf["done"][k], buf["goal"][k], buf["info"][k] = rew, done, inf["goal_index"], self._info
-                nv = self.value(vp, None, value_hidden)
-                if self._auto_reset:  # an env that finished: the value of its terminal row, which `o` no longer holds
-                    nv = torch.where(done != 0, self.value(vp, inf["final_observation"], value_hidden), nv)
-                buf["next_values"][k] = nv
+                if with_critic:
+                    nv = self.value(vp, None, value_hidden, value_activation)
+                    if self._auto_reset:  # an env that finished: the value of its terminal row, which `o` no longer holds
+                        nv = torch.where(done != 0, self.value(vp, inf["final_observation"], value_hidden, value_activation), nv)
+                    buf["next_values"][k] = nv
                 if return_obs:
                     buf["obs_seq"][k] = o
                 if return_actions:
                     buf["actions"][k] = a
+        elif not legacy:
+            actor = _capi.make_net(_ptr(p), stride, widths, act, squash, action_scale)
+            critic = _capi.make_net(_ptr(vp), vstride, vwidths, vact) if with_critic else None
+            rc = self._lib.mz_rollout_net(self._h, K, C.byref(actor), 1 if sample else 0, seed, step, C.byref(critic) if with_critic else None,
+                                          _ptr(buf["values"]) if with_critic else None, _ptr(buf["next_values"]) if with_critic else None,
+                                          _ptr(self._obs), _ptr(buf["reward"]), _ptr(buf["done"]), _ptr(buf["goal"]), _ptr(buf["info"]),
+                                          _ptr(buf["obs_seq"]) if return_obs else None, _ptr(buf["actions"]) if return_actions else None,
+                                          _ptr(buf["logp"]) if sample else None, self._stream())
+            _capi.check(self._lib, self._h, rc, "mz_rollout_net")
         else:
             critic = _capi.MzCritic(_ptr(vp), vstride, int(value_hidden), 0, _ptr(buf["values"]), _ptr(buf["next_values"]))
             rc = self._lib.mz_rollout_actor_critic(self._h, K, _ptr(p), stride, int(hidden), 1 if squash else 0, float(action_scale), 1 if sample else 0,
@@ -758,7 +811,9 @@ class VecMazeEnv:
                                                    self._stream())
             _capi.check(self._lib, self._h, rc, "mz_rollout_actor_critic")
         info = {"position": buf["info"][:, :, :2], "reward_forward": buf["info"][:, :, 2], "reward_ctrl": buf["info"][:, :, 3],
-                "goal_index": buf["goal"], "values": buf["values"], "next_values": buf["next_values"]}
+                "goal_index": buf["goal"]}
+        if with_critic:
+            info["values"], info["next_values"] = buf["values"], buf["next_values"]
         if sample:
             info["logp"] = buf["logp"]
         if gae is not None:

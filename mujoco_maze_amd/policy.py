@@ -32,18 +32,46 @@ Critics (VecMazeEnv.value, the `value_params=` of the rollouts; mz_value / mz_ro
 squashed, in a vector of their own (`param_count(obs_dim, 1, hidden)`, packed by `pack` / `pack_linear`): `value_reference` is the
 pre-squash sum of the one output unit, bit-equal to the device for hidden == 0.  `gae_reference` is the backward scan of
 VecMazeEnv.gae / mz_gae (csrc/mz_gae.h) in float32, operation by operation: bit-equal to the device.
+
+Deeper networks (mz_net_act / mz_net_value / mz_rollout_net): wherever a function here takes `hidden` it is an int as above or a
+sequence of one or two widths, and `activation` is "tanh" or "relu", one choice for both hidden layers.  Two hidden layers pack as
+
+    W1t [obs_dim, H1], b1 [H1], W2t [H1, H2], b2 [H2], W3t [H2, nout], b3 [nout]         (`pack_mlp`)
+
+then log_std [nu] for a stochastic actor.  ReLU is `0 if acc < 0 else acc`: no rounding, -0.0 stays -0.0, NaN propagates — so a
+ReLU network without squash equals the device bit for bit at any depth.
 """
 import numpy as np
 
 MAX_HIDDEN = 64  # MZ_POLICY_MAX_HIDDEN (include/mazestep.h)
+MAX_HIDDEN_LAYERS = 2  # MZ_NET_MAX_HIDDEN_LAYERS
+ACTIVATIONS = ("tanh", "relu")  # index: MZ_ACT_TANH, MZ_ACT_RELU
 
 
-def param_count(obs_dim: int, nu: int, hidden: int = 0, stochastic: bool = False) -> int:
-    """Floats of one policy; with `stochastic` the network's count plus log_std [nu]."""
-    obs_dim, nu, hidden = int(obs_dim), int(nu), int(hidden)
-    if not 0 <= hidden <= MAX_HIDDEN:
-        raise ValueError(f"hidden must be 0 .. {MAX_HIDDEN}, got {hidden}")
-    return (obs_dim * hidden + hidden + hidden * nu + nu if hidden else obs_dim * nu + nu) + (nu if stochastic else 0)
+def net_shape(hidden=0, activation: str = "tanh", what: str = "hidden"):
+    """(widths, activation index) of a network: `hidden` an int (0: affine) or a sequence of one or two widths 1 .. 64, `activation`
+    "tanh" or "relu".  `what` names the argument in the errors."""
+    if activation not in ACTIVATIONS:
+        raise ValueError(f"activation must be 'tanh' or 'relu', got {activation!r}")
+    if np.ndim(hidden) == 0:
+        h = int(hidden)
+        if not 0 <= h <= MAX_HIDDEN:
+            raise ValueError(f"{what} must be 0 .. {MAX_HIDDEN}, got {h}")
+        return ((h,) if h else ()), ACTIVATIONS.index(activation)
+    widths = tuple(int(w) for w in hidden)
+    if not 1 <= len(widths) <= MAX_HIDDEN_LAYERS:
+        raise ValueError(f"{what} must be an int or a sequence of one or two widths, got {len(widths)} hidden layers")
+    if any(not 1 <= w <= MAX_HIDDEN for w in widths):
+        raise ValueError(f"{what}: a hidden layer has 1 .. {MAX_HIDDEN} units, got {widths}")
+    return widths, ACTIVATIONS.index(activation)
+
+
+def param_count(obs_dim: int, nu: int, hidden=0, stochastic: bool = False) -> int:
+    """Floats of one policy; with `stochastic` the network's count plus log_std [nu].  hidden: an int or a sequence of one or two
+    widths."""
+    obs_dim, nu = int(obs_dim), int(nu)
+    sizes = (obs_dim,) + net_shape(hidden)[0] + (nu,)
+    return sum(a * b + b for a, b in zip(sizes[:-1], sizes[1:])) + (nu if stochastic else 0)
 
 
 def _np(x):
@@ -81,6 +109,21 @@ def pack(W1, b1, W2, b2, log_std=None):
     return _with_log_std([W1.T.ravel(), b1, W2.T.ravel(), b2], W2.shape[0], log_std)
 
 
+def pack_mlp(layers, log_std=None):
+    """A network of 0, 1 or 2 hidden layers from 1 .. 3 `(W, b)` pairs in nn.Linear orientation, first layer first: W [out, in],
+    b [out] -> float32 [count], every layer as W.T then b; with `log_std` [nu] the stochastic policy's vector, nu numbers longer.
+    One pair is `pack_linear`, two pairs are `pack`."""
+    pairs = [(_np(W), _np(b)) for W, b in layers]
+    if not 1 <= len(pairs) <= MAX_HIDDEN_LAYERS + 1:
+        raise ValueError(f"layers must hold 1 .. {MAX_HIDDEN_LAYERS + 1} (W, b) pairs, got {len(pairs)}")
+    for k, (W, b) in enumerate(pairs):
+        if W.ndim != 2 or b.shape != (W.shape[0],) or (k and W.shape[1] != pairs[k - 1][0].shape[0]):
+            raise ValueError(f"layers[{k}]: want W [out, in] and b [out] with in = the width of the layer before, got {W.shape} and {b.shape}")
+        if k < len(pairs) - 1 and not 1 <= W.shape[0] <= MAX_HIDDEN:
+            raise ValueError(f"layers[{k}]: a hidden layer has 1 .. {MAX_HIDDEN} units, got {W.shape[0]}")
+    return _with_log_std([a for W, b in pairs for a in (W.T.ravel(), b)], pairs[-1][0].shape[0], log_std)
+
+
 def _layer(x, Wt, b):
     """b + sum_i Wt[.., i, :] * x[.., i] in index order, float32, two roundings per term.  x [R, n]; Wt [n, m] or [R, n, m]; b [m] or [R, m]."""
     acc = np.broadcast_to(b, (x.shape[0], Wt.shape[-1])).astype(np.float32)
@@ -90,32 +133,36 @@ def _layer(x, Wt, b):
     return acc
 
 
-def _pre_squash(x, p, nu, H):
-    """The output units' sums before the squash: x [R, obs_dim], p [npar] or [R, npar] -> float32 [R, nu]."""
-    od, lead = x.shape[1], p.shape[:-1]
-    if H:
-        o1, o2, o3 = od * H, od * H + H, od * H + H + H * nu
-        h = np.tanh(_layer(x, p[..., :o1].reshape(lead + (od, H)), p[..., o1:o2])).astype(np.float32)
-        return _layer(h, p[..., o2:o3].reshape(lead + (H, nu)), p[..., o3:])
-    return _layer(x, p[..., : od * nu].reshape(lead + (od, nu)), p[..., od * nu:])
+def _pre_squash(x, p, nu, shape):
+    """The output units' sums before the squash: x [R, obs_dim], p [npar] or [R, npar], shape = net_shape(..) -> float32 [R, nu]."""
+    widths, act = shape
+    lead, off, h = p.shape[:-1], 0, x
+    for k, m in enumerate(widths + (nu,)):
+        n = h.shape[1]
+        acc = _layer(h, p[..., off: off + n * m].reshape(lead + (n, m)), p[..., off + n * m: off + n * m + m])
+        off += n * m + m
+        if k == len(widths):
+            return acc
+        # hidden units: tanh, or the select of mzp_activate (no rounding, -0.0 and NaN pass)
+        h = np.where(acc < 0, np.float32(0.0), acc).astype(np.float32) if act else np.tanh(acc).astype(np.float32)
 
 
 def _squashed(acc, squash, action_scale):
     return (np.float32(action_scale) * np.tanh(acc).astype(np.float32)).astype(np.float32) if squash else acc
 
 
-def reference(params, obs, nu: int, hidden: int = 0, squash: bool = False, action_scale: float = 1.0):
+def reference(params, obs, nu: int, hidden=0, squash: bool = False, action_scale: float = 1.0, activation: str = "tanh"):
     """The policy of csrc/mz_policy.h on rows of observations: obs [R, obs_dim] (or [obs_dim]); params [npar] shared by the rows or
-    [R, npar], one policy per row.  Returns float32 [R, nu] (or [nu])."""
+    [R, npar], one policy per row; hidden / activation as in `net_shape`.  Returns float32 [R, nu] (or [nu])."""
     x = np.asarray(obs, dtype=np.float32)
     single = x.ndim == 1
     x = np.atleast_2d(x)
     p = np.asarray(params, dtype=np.float32)
-    R, od, nu, H = x.shape[0], x.shape[1], int(nu), int(hidden)
-    npar = param_count(od, nu, H)
+    R, od, nu, shape = x.shape[0], x.shape[1], int(nu), net_shape(hidden, activation)
+    npar = param_count(od, nu, hidden)
     if p.shape not in ((npar,), (R, npar)):
         raise ValueError(f"params must have shape {(npar,)} or {(R, npar)}, got {p.shape}")
-    out = _squashed(_pre_squash(x, p, nu, H), squash, action_scale)
+    out = _squashed(_pre_squash(x, p, nu, shape), squash, action_scale)
     return out[0] if single else out
 
 
@@ -161,8 +208,8 @@ def noise(noise_seed: int, noise_step: int, slots, nu: int):
     return (r * c).astype(np.float32)
 
 
-def sample_reference(params, obs, nu: int, hidden: int = 0, squash: bool = False, action_scale: float = 1.0, noise_seed: int = 0,
-                     noise_step: int = 0, slots=None):
+def sample_reference(params, obs, nu: int, hidden=0, squash: bool = False, action_scale: float = 1.0, noise_seed: int = 0,
+                     noise_step: int = 0, slots=None, activation: str = "tanh"):
     """The stochastic policy of csrc/mz_policy.h on rows of observations: obs [R, obs_dim] (or [obs_dim]); params [npar_s] shared by
     the rows or [R, npar_s]; slots: the rows' global env slots, default 0 .. R - 1.  Returns (actions float32 [R, nu], logp float32
     [R]) — or ([nu], scalar) for a single row."""
@@ -170,15 +217,15 @@ def sample_reference(params, obs, nu: int, hidden: int = 0, squash: bool = False
     single = x.ndim == 1
     x = np.atleast_2d(x)
     p = np.asarray(params, dtype=np.float32)
-    R, od, nu, H = x.shape[0], x.shape[1], int(nu), int(hidden)
-    npar = param_count(od, nu, H)
+    R, od, nu, shape = x.shape[0], x.shape[1], int(nu), net_shape(hidden, activation)
+    npar = param_count(od, nu, hidden)
     if p.shape not in ((npar + nu,), (R, npar + nu)):
         raise ValueError(f"params must have shape {(npar + nu,)} or {(R, npar + nu)} (the network, then log_std [nu]), got {p.shape}")
     sl = np.arange(R) if slots is None else np.atleast_1d(np.asarray(slots, dtype=object)).ravel()
     if len(sl) != R:
         raise ValueError(f"slots must name one global env slot per row ({R}), got {len(sl)}")
     ls = np.broadcast_to(p[..., npar:], (R, nu))
-    m = _pre_squash(x, p[..., :npar], nu, H)
+    m = _pre_squash(x, p[..., :npar], nu, shape)
     eps = noise(noise_seed, noise_step, sl, nu)
     with np.errstate(over="ignore", invalid="ignore"):
         s = np.exp(ls.astype(np.float64)).astype(np.float32)
@@ -193,7 +240,7 @@ def sample_reference(params, obs, nu: int, hidden: int = 0, squash: bool = False
     return (act[0], logp[0]) if single else (act, logp)
 
 
-def value_reference(value_params, obs, hidden: int = 0):
+def value_reference(value_params, obs, hidden=0, activation: str = "tanh"):
     """The critic of csrc/mz_policy.h (mzp_value_row) on rows of observations: a policy with nu = 1, never squashed, whose value is
     the pre-squash sum of its one output unit.  obs [R, obs_dim] (or [obs_dim]); value_params [nvpar] shared by the rows or
     [R, nvpar], nvpar = param_count(obs_dim, 1, hidden).  Returns float32 [R] (or a scalar); bit-equal to the device for hidden == 0."""
@@ -201,12 +248,12 @@ def value_reference(value_params, obs, hidden: int = 0):
     single = x.ndim == 1
     x = np.atleast_2d(x)
     p = np.asarray(value_params, dtype=np.float32)
-    R, od, H = x.shape[0], x.shape[1], int(hidden)
-    npar = param_count(od, 1, H)
+    R, od, shape = x.shape[0], x.shape[1], net_shape(hidden, activation)
+    npar = param_count(od, 1, hidden)
     if p.shape not in ((npar,), (R, npar)):
         raise ValueError(f"value_params must have shape {(npar,)} or {(R, npar)}, got {p.shape}")
     with np.errstate(over="ignore", invalid="ignore"):
-        v = _pre_squash(x, p, 1, H)[:, 0]
+        v = _pre_squash(x, p, 1, shape)[:, 0]
     return v[0] if single else v
 
 

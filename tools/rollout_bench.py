@@ -15,6 +15,9 @@ of K iterations; one env.rollout_policy_sample(..., value_params=, gae=); and th
 torch leg bootstraps every row from the value of the NEXT row it holds: the terminal rows are gone, which is the gap the one-call path
 closes — its cost is what this compares, not its result.)
     python tools/rollout_bench.py --policy 32 --sample --critic 32 --steps 128 --ids PointUMaze-v0,SwimmerUMaze-v0,AntUMaze-v0
+--policy and --critic also take two widths, `64,64`: a network with two hidden layers (mz_net_act / mz_rollout_net), the torch legs then
+run a two-layer torch MLP; --activation tanh|relu chooses the hidden units of both networks (relu goes through the same entries).
+    python tools/rollout_bench.py --policy 64,64 --sample --critic 64,64 --activation relu --steps 128
 Kernel durations come from a run of their own:  rocprofv3 --kernel-trace --stats -d <dir> -- python tools/rollout_bench.py --seconds 0.2"""
 import argparse
 import json
@@ -43,6 +46,31 @@ def leg(fn, windows_min, seconds, dev):
         dt = time.perf_counter() - t0
         if dt >= seconds:
             return done, dt
+
+
+def hidden_arg(text):
+    """`32` -> 32, `64,64` -> (64, 64)"""
+    w = tuple(int(x) for x in text.split(","))
+    return w[0] if len(w) == 1 else w
+
+
+def build_net(lin, obs_dim, nout, hidden, activation, dev, log_std=None):
+    """One network as (packed params on the device, the same network as a torch function of [R, obs_dim] rows); lin(out, fan_in)
+    draws one layer's (W, b), first layer first."""
+    from mujoco_maze_amd import policy
+
+    sizes = (obs_dim,) + policy.net_shape(hidden, activation)[0] + (nout,)
+    layers = [lin(o, i) for i, o in zip(sizes[:-1], sizes[1:])]
+    params = torch.as_tensor(policy.pack_mlp(layers, log_std=log_std), device=dev)
+    wts = [(W.T.contiguous(), b) for W, b in layers]
+    f = torch.tanh if activation == "tanh" else torch.relu
+
+    def fn(obs):
+        for Wt, b in wts[:-1]:
+            obs = f(torch.addmm(b, obs, Wt))
+        return torch.addmm(wts[-1][1], obs, wts[-1][0])
+
+    return params, fn
 
 
 def bench(env_id, n, K, seconds, repeats):
@@ -75,10 +103,8 @@ def bench(env_id, n, K, seconds, repeats):
             "step_env_steps_per_s": res["step"], "rollout_env_steps_per_s": res["rollout"]}
 
 
-def bench_policy(env_id, n, K, H, seconds, repeats):
+def bench_policy(env_id, n, K, H, seconds, repeats, ACT="tanh"):
     """K closed-loop steps of one shared policy, three ways: torch policy + step, policy_act + step, one rollout_policy."""
-    from mujoco_maze_amd import policy
-
     dev = torch.device("cuda", 0)
     env = mm.make(env_id, num_envs=n, auto_reset=True, device=dev, force_vec=True)
     env.reset(seed=20260928)
@@ -88,16 +114,7 @@ def bench_policy(env_id, n, K, H, seconds, repeats):
         k = fan_in ** -0.5
         return (2 * torch.rand((out, fan_in), device=dev, generator=g) - 1) * k, (2 * torch.rand(out, device=dev, generator=g) - 1) * k
 
-    if H:
-        (W1, b1), (W2, b2) = lin(H, env.obs_dim), lin(env.nu, H)
-        params = torch.as_tensor(policy.pack(W1, b1, W2, b2), device=dev)
-        W1t, W2t = W1.T.contiguous(), W2.T.contiguous()
-        torch_policy = lambda obs: torch.addmm(b2, torch.tanh(torch.addmm(b1, obs, W1t)), W2t)
-    else:
-        W, b = lin(env.nu, env.obs_dim)
-        params = torch.as_tensor(policy.pack_linear(W, b), device=dev)
-        Wt = W.T.contiguous()
-        torch_policy = lambda obs: torch.addmm(b, obs, Wt)
+    params, torch_policy = build_net(lin, env.obs_dim, env.nu, H, ACT, dev)
     state = {"obs": env._obs}
 
     def torch_step():
@@ -106,10 +123,10 @@ def bench_policy(env_id, n, K, H, seconds, repeats):
 
     def act_step():
         for k in range(K):
-            env.step(env.policy_act(params, hidden=H))
+            env.step(env.policy_act(params, hidden=H, activation=ACT))
 
     def fused():
-        env.rollout_policy(params, K, hidden=H)
+        env.rollout_policy(params, K, hidden=H, activation=ACT)
 
     legs = (("torch_step", torch_step), ("act_step", act_step), ("rollout_policy", fused))
     for _ in range(4):
@@ -123,15 +140,13 @@ def bench_policy(env_id, n, K, H, seconds, repeats):
     bad = int((env.status() & 3).ne(0).sum())
     fused_flag = env.launch_info()["rollout_fused"]
     env.close()
-    return {"env": env_id, "envs": n, "steps_per_window": K, "hidden": H, "fused": fused_flag, "flagged_envs": bad,
+    return {"env": env_id, "envs": n, "steps_per_window": K, "hidden": H, "activation": ACT, "fused": fused_flag, "flagged_envs": bad,
             **{name + "_env_steps_per_s": v for name, v in res.items()}}
 
 
-def bench_sample(env_id, n, K, H, seconds, repeats):
+def bench_sample(env_id, n, K, H, seconds, repeats, ACT="tanh"):
     """K closed-loop steps of one shared Gaussian policy: policy_sample + step, one rollout_policy_sample; the deterministic
     rollout_policy of the same network as the yardstick."""
-    from mujoco_maze_amd import policy
-
     dev = torch.device("cuda", 0)
     env = mm.make(env_id, num_envs=n, auto_reset=True, device=dev, force_vec=True)
     env.reset(seed=20260928)
@@ -142,22 +157,18 @@ def bench_sample(env_id, n, K, H, seconds, repeats):
         return (2 * torch.rand((out, fan_in), device=dev, generator=g) - 1) * k, (2 * torch.rand(out, device=dev, generator=g) - 1) * k
 
     log_std = torch.full((env.nu,), -0.5)
-    if H:
-        (W1, b1), (W2, b2) = lin(H, env.obs_dim), lin(env.nu, H)
-        params = torch.as_tensor(policy.pack(W1, b1, W2, b2, log_std=log_std), device=dev)
-    else:
-        params = torch.as_tensor(policy.pack_linear(*lin(env.nu, env.obs_dim), log_std=log_std), device=dev)
+    params, _ = build_net(lin, env.obs_dim, env.nu, H, ACT, dev, log_std=log_std)
     det = params[: -env.nu].contiguous()
 
     def sample_step():
         for k in range(K):
-            env.step(env.policy_sample(params, hidden=H)[0])
+            env.step(env.policy_sample(params, hidden=H, activation=ACT)[0])
 
     def fused():
-        env.rollout_policy_sample(params, K, hidden=H)
+        env.rollout_policy_sample(params, K, hidden=H, activation=ACT)
 
     def fused_det():
-        env.rollout_policy(det, K, hidden=H)
+        env.rollout_policy(det, K, hidden=H, activation=ACT)
 
     legs = (("sample_step", sample_step), ("rollout_policy_sample", fused), ("rollout_policy", fused_det))
     for _ in range(4):
@@ -171,15 +182,13 @@ def bench_sample(env_id, n, K, H, seconds, repeats):
     bad = int((env.status() & 3).ne(0).sum())
     fused_flag = env.launch_info()["rollout_fused"]
     env.close()
-    return {"env": env_id, "envs": n, "steps_per_window": K, "hidden": H, "sample": True, "fused": fused_flag, "flagged_envs": bad,
+    return {"env": env_id, "envs": n, "steps_per_window": K, "hidden": H, "activation": ACT, "sample": True, "fused": fused_flag, "flagged_envs": bad,
             **{name + "_env_steps_per_s": v for name, v in res.items()}}
 
 
-def bench_critic(env_id, n, K, H, HV, seconds, repeats):
+def bench_critic(env_id, n, K, H, HV, seconds, repeats, ACT="tanh"):
     """One actor-critic collection window of K steps: policy_sample + step + torch critic + torch GAE loop; one
     rollout_policy_sample with value_params and gae; the same call without a critic."""
-    from mujoco_maze_amd import policy
-
     dev = torch.device("cuda", 0)
     env = mm.make(env_id, num_envs=n, auto_reset=True, device=dev, force_vec=True)
     env.reset(seed=20260928)
@@ -191,21 +200,8 @@ def bench_critic(env_id, n, K, H, HV, seconds, repeats):
         return (2 * torch.rand((out, fan_in), device=dev, generator=g) - 1) * k, (2 * torch.rand(out, device=dev, generator=g) - 1) * k
 
     log_std = torch.full((env.nu,), -0.5)
-    if H:
-        (W1, b1), (W2, b2) = lin(H, env.obs_dim), lin(env.nu, H)
-        params = torch.as_tensor(policy.pack(W1, b1, W2, b2, log_std=log_std), device=dev)
-    else:
-        params = torch.as_tensor(policy.pack_linear(*lin(env.nu, env.obs_dim), log_std=log_std), device=dev)
-    if HV:
-        (V1, c1), (V2, c2) = lin(HV, env.obs_dim), lin(1, HV)
-        vparams = torch.as_tensor(policy.pack(V1, c1, V2, c2), device=dev)
-        V1t, V2t = V1.T.contiguous(), V2.T.contiguous()
-        torch_critic = lambda obs: torch.addmm(c2, torch.tanh(torch.addmm(c1, obs, V1t)), V2t)
-    else:
-        V, c = lin(1, env.obs_dim)
-        vparams = torch.as_tensor(policy.pack_linear(V, c), device=dev)
-        Vt = V.T.contiguous()
-        torch_critic = lambda obs: torch.addmm(c, obs, Vt)
+    params, _ = build_net(lin, env.obs_dim, env.nu, H, ACT, dev, log_std=log_std)
+    vparams, torch_critic = build_net(lin, env.obs_dim, 1, HV, ACT, dev)
     rows = torch.empty((K + 1, n, env.obs_dim), device=dev)
     rew, done = torch.empty((K, n), device=dev), torch.empty((K, n), dtype=torch.uint8, device=dev)
     adv = torch.empty((K, n), device=dev)
@@ -213,7 +209,7 @@ def bench_critic(env_id, n, K, H, HV, seconds, repeats):
     def torch_path():
         rows[0] = env._obs
         for k in range(K):
-            o, r, d, _ = env.step(env.policy_sample(params, hidden=H)[0])
+            o, r, d, _ = env.step(env.policy_sample(params, hidden=H, activation=ACT)[0])
             rows[k + 1], rew[k], done[k] = o, r, d
         v = torch_critic(rows.view((K + 1) * n, env.obs_dim)).view(K + 1, n)
         carry = torch.zeros(n, device=dev)
@@ -225,10 +221,10 @@ def bench_critic(env_id, n, K, H, HV, seconds, repeats):
         return adv, adv + v[:K]
 
     def one_call():
-        env.rollout_policy_sample(params, K, hidden=H, value_params=vparams, value_hidden=HV, gae=(gamma, lam))
+        env.rollout_policy_sample(params, K, hidden=H, value_params=vparams, value_hidden=HV, gae=(gamma, lam), activation=ACT, value_activation=ACT)
 
     def no_critic():
-        env.rollout_policy_sample(params, K, hidden=H)
+        env.rollout_policy_sample(params, K, hidden=H, activation=ACT)
 
     legs = (("torch_critic_gae", torch_path), ("rollout_actor_critic_gae", one_call), ("rollout_policy_sample", no_critic))
     for _ in range(4):
@@ -242,18 +238,18 @@ def bench_critic(env_id, n, K, H, HV, seconds, repeats):
     bad = int((env.status() & 3).ne(0).sum())
     fused_flag = env.launch_info()["rollout_fused"]
     env.close()
-    return {"env": env_id, "envs": n, "steps_per_window": K, "hidden": H, "critic_hidden": HV, "sample": True, "fused": fused_flag, "flagged_envs": bad,
+    return {"env": env_id, "envs": n, "steps_per_window": K, "hidden": H, "critic_hidden": HV, "activation": ACT, "sample": True, "fused": fused_flag, "flagged_envs": bad,
             **{name + "_env_steps_per_s": v for name, v in res.items()}}
 
 
 def main_critic(args):
     out = []
     med = lambda v: sorted(v)[len(v) // 2]
-    print(f"actor-critic window, shared Gaussian policy (hidden {args.policy}) and critic (hidden {args.critic}), GAE(0.99, 0.95), {args.steps} steps per "
+    print(f"actor-critic window, shared Gaussian policy (hidden {args.policy}) and critic (hidden {args.critic}), {args.activation} units, GAE(0.99, 0.95), {args.steps} steps per "
           f"window, {args.envs} envs, auto-reset, >= {args.seconds} s per leg, {args.repeats} alternating repeats; M env-steps/s, median (max - min)")
     print("%-18s %5s %26s %26s %26s" % ("env", "fused", "sample+step, torch V, GAE", "one call, critic + gae", "one call, no critic"))
     for env_id in args.ids.split(","):
-        r = bench_critic(env_id, args.envs, args.steps, args.policy, args.critic, args.seconds, args.repeats)
+        r = bench_critic(env_id, args.envs, args.steps, args.policy, args.critic, args.seconds, args.repeats, args.activation)
         out.append(r)
         cell = lambda v: "%10.3f (%6.3f)" % (med(v) / 1e6, (max(v) - min(v)) / 1e6)
         print("%-18s %5d %26s %26s %26s" % (env_id, r["fused"], cell(r["torch_critic_gae_env_steps_per_s"]), cell(r["rollout_actor_critic_gae_env_steps_per_s"]),
@@ -267,11 +263,11 @@ def main_critic(args):
 def main_sample(args):
     out = []
     med = lambda v: sorted(v)[len(v) // 2]
-    print(f"closed loop, one shared Gaussian policy (hidden {args.policy}, log_std -0.5), {args.steps} steps per window, {args.envs} envs, auto-reset, "
+    print(f"closed loop, one shared Gaussian policy (hidden {args.policy}, {args.activation} units, log_std -0.5), {args.steps} steps per window, {args.envs} envs, auto-reset, "
           f">= {args.seconds} s per leg, {args.repeats} alternating repeats; M env-steps/s, median (max - min)")
     print("%-18s %5s %24s %24s %24s" % ("env", "fused", "policy_sample + step", "rollout_policy_sample", "rollout_policy (det.)"))
     for env_id in args.ids.split(","):
-        r = bench_sample(env_id, args.envs, args.steps, args.policy, args.seconds, args.repeats)
+        r = bench_sample(env_id, args.envs, args.steps, args.policy, args.seconds, args.repeats, args.activation)
         out.append(r)
         cell = lambda v: "%10.3f (%6.3f)" % (med(v) / 1e6, (max(v) - min(v)) / 1e6)
         print("%-18s %5d %24s %24s %24s" % (env_id, r["fused"], cell(r["sample_step_env_steps_per_s"]), cell(r["rollout_policy_sample_env_steps_per_s"]),
@@ -285,11 +281,11 @@ def main_sample(args):
 def main_policy(args):
     out = []
     med = lambda v: sorted(v)[len(v) // 2]
-    print(f"closed loop, one shared policy (hidden {args.policy}), {args.steps} steps per window, {args.envs} envs, auto-reset, >= {args.seconds} s per leg, "
+    print(f"closed loop, one shared policy (hidden {args.policy}, {args.activation} units), {args.steps} steps per window, {args.envs} envs, auto-reset, >= {args.seconds} s per leg, "
           f"{args.repeats} alternating repeats; M env-steps/s, median (max - min)")
     print("%-18s %5s %24s %24s %24s" % ("env", "fused", "torch policy + step", "policy_act + step", "rollout_policy"))
     for env_id in args.ids.split(","):
-        r = bench_policy(env_id, args.envs, args.steps, args.policy, args.seconds, args.repeats)
+        r = bench_policy(env_id, args.envs, args.steps, args.policy, args.seconds, args.repeats, args.activation)
         out.append(r)
         cell = lambda v: "%10.3f (%6.3f)" % (med(v) / 1e6, (max(v) - min(v)) / 1e6)
         print("%-18s %5d %24s %24s %24s" % (env_id, r["fused"], cell(r["torch_step_env_steps_per_s"]), cell(r["act_step_env_steps_per_s"]),
@@ -308,9 +304,10 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--ids", type=str, default=",".join(IDS))
     ap.add_argument("--out", type=str, default=None, help="also write the rows as JSON lines")
-    ap.add_argument("--policy", type=int, default=None, metavar="H", help="closed-loop mode: hidden units of the policy (0 = affine)")
+    ap.add_argument("--policy", type=hidden_arg, default=None, metavar="H", help="closed-loop mode: hidden units of the policy (0 = affine), or two widths H1,H2")
     ap.add_argument("--sample", action="store_true", help="with --policy: Gaussian policies, a sampled action every step")
-    ap.add_argument("--critic", type=int, default=None, metavar="HV", help="with --policy H --sample: a critic with HV hidden units (0 = affine) and GAE")
+    ap.add_argument("--critic", type=hidden_arg, default=None, metavar="HV", help="with --policy H --sample: a critic with HV hidden units (0 = affine; or HV1,HV2) and GAE")
+    ap.add_argument("--activation", choices=("tanh", "relu"), default="tanh", help="with --policy: the hidden units of policy and critic")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "rollout_bench.py measures on the GPU only"
     if args.sample and args.policy is None:
