@@ -550,6 +550,46 @@ int32_t mz_rollout_net(mz_handle* h, int32_t n_steps, const mz_net* actor, int32
                        uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev, float* obs_seq_dev, float* actions_seq_dev,
                        float* logp_seq_dev, void* stream);
 
+/* Normalised observations for the device-side networks (the observation half of VecNormalize; ARS-V2's state normalisation), and the
+ * forward return scan that reward scaling and episode logging need.  Additive entries: MZ_ABI_VERSION does not change for them.
+ *
+ * mz_bind_obs_norm: binds one normaliser, shared by all envs, to the handle.  mean_dev and inv_std_dev are [obs_dim] fp32 DEVICE
+ * arrays owned by the caller (obs_dim = mz_obs_dim: a top-down view's entries included).  While bound, every network evaluation reads
+ * the row y in place of the raw row x — element i, fp32, every operation rounded separately (csrc/mz_policy.h mzp_norm_elem):
+ *     d = x[i] - mean[i];   y = d * inv_std[i];   y = y < -c ? -c : (y > c ? c : y)             c = (float)clip
+ * a product with inv_std, never a quotient; two selects, so a NaN passes through, clip = +inf switches the clip off, x = +-inf becomes
+ * +-c and a constant column (d == 0) becomes 0 whatever a finite inv_std is.  numpy reproduces it bit for bit
+ * (mujoco_maze_amd/policy.py normalize_reference), so an affine or ReLU network without squash on normalised rows stays
+ * bit-reproducible.
+ *  normalised  what the NETWORKS read in mz_policy_act, mz_policy_sample, mz_value, mz_net_act, mz_net_value and the four closed-loop
+ *              rollouts mz_rollout_policy, mz_rollout_policy_sample, mz_rollout_actor_critic, mz_rollout_net — the critic's terminal row
+ *              included: the final_obs row in the loop form, the on-chip terminal row in the fused form.  Each of these calls equals
+ *              the unbound call on rows normalised beforehand, and the rollouts still equal their defining loops bit for bit.
+ *  raw         everything the env itself reads or writes: obs_dev, obs_seq_dev, the bound final_obs buffer and the bound record; the
+ *              task predicate and the info rows; mz_step and the open-loop mz_rollout, which do not look at the binding.
+ * The arrays are read by every later evaluation in stream order, so the caller may rewrite them between two calls without binding
+ * again.  Both pointers NULL unbinds (clip is ignored).  The call stores the two pointers and clip and does not synchronise (`stream`
+ * is not used).  While a normaliser is bound the legacy entries (int `hidden`, tanh) run the kernels of the mz_net entries, which
+ * return the same bits for such a network.  mz_get_info "obs_norm" is 1 while a normaliser is bound, else 0.
+ * Returns MZ_OK, or MZ_ERR_ARG with a message that names the argument: exactly one pointer NULL; clip NaN or <= 0.  A refused call
+ * leaves the previous binding in place.
+ *
+ * mz_return_scan: the running discounted return and the episode step count of every env over the [n_steps, N] rows of a rollout, one
+ * forward scan per env, k from 0 up to n_steps - 1; fp32, every operation rounded separately; selects (csrc/mz_returns.h):
+ *     g = (float)gamma
+ *     p = g * carry;  s = p + reward[k];  ret_seq[k] = s;  len = len + 1;  len_seq[k] = len
+ *     carry = done[k] ? 0.0f : s;         len = done[k] ? 0 : len
+ *  carry_dev [N] fp32 and len_carry_dev [N] i32 are IN/OUT and per env: a scan over K1 steps followed by a scan over K2 steps equals
+ *            one scan over K1 + K2 steps.  A new series starts from zeros.
+ *  ret_seq_dev [n_steps, N] fp32; len_seq_dev [n_steps, N] i32.
+ * With gamma == 1 the product is exact: ret_seq[k] where done[k] != 0 is that episode's return and len_seq[k] its length.  With
+ * gamma < 1 ret_seq is the series whose running variance VecNormalize divides rewards by.  len_carry_dev and len_seq_dev are nullable;
+ * a NULL len_carry_dev means the length is not tracked, and a len_seq_dev without it is MZ_ERR_ARG.  carry_dev and ret_seq_dev are
+ * required.  n_steps 1 .. 65536.  Returns MZ_OK, MZ_ERR_ARG or MZ_ERR_HIP. */
+int32_t mz_bind_obs_norm(mz_handle* h, const float* mean_dev, const float* inv_std_dev, double clip, void* stream);
+int32_t mz_return_scan(mz_handle* h, int32_t n_steps, const float* reward_dev, const uint8_t* done_dev, double gamma,
+                       float* carry_dev, int32_t* len_carry_dev, float* ret_seq_dev, int32_t* len_seq_dev, void* stream);
+
 /* Per-env status words accumulated since the last call (then cleared). [N] i32. */
 int32_t mz_get_status(mz_handle* h, int32_t* status_dev, void* stream);
 

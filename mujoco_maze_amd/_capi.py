@@ -25,6 +25,7 @@ SYMBOLS = [
     "mz_policy_act", "mz_rollout_policy", "mz_policy_sample", "mz_rollout_policy_sample",
     "mz_value", "mz_rollout_actor_critic", "mz_gae",
     "mz_net_act", "mz_net_value", "mz_rollout_net",
+    "mz_bind_obs_norm", "mz_return_scan",
 ]
 
 
@@ -122,6 +123,10 @@ def load():
     lib.mz_net_value.argtypes = [vp, C.POINTER(MzNet), vp, vp, vp]
     lib.mz_rollout_net.restype = i32
     lib.mz_rollout_net.argtypes = [vp, i32, C.POINTER(MzNet), i32, u64, u64, C.POINTER(MzNet), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.mz_bind_obs_norm.restype = i32
+    lib.mz_bind_obs_norm.argtypes = [vp, vp, vp, C.c_double, vp]
+    lib.mz_return_scan.restype = i32
+    lib.mz_return_scan.argtypes = [vp, i32, vp, vp, C.c_double, vp, vp, vp, vp, vp]
     lib.mz_gae.restype = i32
     lib.mz_gae.argtypes = [vp, i32, vp, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp]
     lib.mz_get_status.restype = i32

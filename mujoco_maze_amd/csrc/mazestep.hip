@@ -12,6 +12,7 @@
 #include "mz_internal.h"
 #include "mz_policy.h"
 #include "mz_render.h"
+#include "mz_returns.h"
 
 __global__ void fetch_clear_status_kernel(int n, int* status, int* out) {
   int env = blockIdx.x * blockDim.x + threadIdx.x;
@@ -83,29 +84,53 @@ __global__ __launch_bounds__(256) void value_kernel(int n, int obs_dim, int hidd
 // policy_act_kernel (sample == 0: key, env0 and logp are not read) and policy_sample_kernel (sample == 1) for a network of shape s
 // (mz_net_act; mz_rollout_net where it steps launch by launch): the same groups, a second LDS row per group for the second hidden
 // vector.  Kernels of their own beside the three above, whose code stays what it was.
+// NRM (a normaliser bound with mz_bind_obs_norm; every entry, the legacy ones included, then runs these two kernels): the group first
+// stages the normalised row of mz_policy.h in a third LDS row — lanes l, l + 16, .. own its elements —, hands it over and evaluates
+// the network on it.  obs_dim <= MZ_MAX_OBS + MZ_VIEW_DIM on every handle (mz_create; mz_bind_obs_norm checks it again).  NRM == false
+// compiles the source as it was and never reads `nm`.
+template <bool NRM = false>
 __global__ __launch_bounds__(256) void net_act_kernel(int n, int obs_dim, int nu, mzp_shape s, int squash, float action_scale,
                                                       const float* __restrict__ params, long pstride, int sample, uint64_t key, uint64_t env0,
-                                                      const float* __restrict__ obs, float* __restrict__ actions, float* __restrict__ logp) {
+                                                      const float* __restrict__ obs, float* __restrict__ actions, float* __restrict__ logp,
+                                                      mzp_norm nm) {
   __shared__ float hid[256 / MZ_POLICY_LANES][MZ_NET_MAX_HIDDEN_LAYERS][MZ_POLICY_MAX_HIDDEN];
   const int l = (int)threadIdx.x % MZ_POLICY_LANES, grp = (int)threadIdx.x / MZ_POLICY_LANES;
   size_t row = (size_t)blockIdx.x * (256 / MZ_POLICY_LANES) + grp;
   const bool live = row < (size_t)n;
   if (!live) row = (size_t)n - 1;
-  mzp_group_net_act(l, MZ_POLICY_LANES, params + row * pstride, obs_dim, nu, s, squash, action_scale, sample != 0, key, env0 + row,
-                    obs + row * obs_dim, hid[grp][0], hid[grp][1], actions + row * nu, live, live && logp ? logp + row : nullptr);
+  if constexpr (NRM) {
+    __shared__ float xn[256 / MZ_POLICY_LANES][MZ_MAX_OBS + MZ_VIEW_DIM];
+    mzp_group_norm(l, MZ_POLICY_LANES, nm, obs_dim, obs + row * obs_dim, xn[grp]);
+    mzp_wave_sync();
+    mzp_group_net_act(l, MZ_POLICY_LANES, params + row * pstride, obs_dim, nu, s, squash, action_scale, sample != 0, key, env0 + row, xn[grp],
+                      hid[grp][0], hid[grp][1], actions + row * nu, live, live && logp ? logp + row : nullptr);
+  } else {
+    mzp_group_net_act(l, MZ_POLICY_LANES, params + row * pstride, obs_dim, nu, s, squash, action_scale, sample != 0, key, env0 + row,
+                      obs + row * obs_dim, hid[grp][0], hid[grp][1], actions + row * nu, live, live && logp ? logp + row : nullptr);
+  }
 }
 
-// value_kernel for a critic of shape s (mz_net_value; mz_rollout_net where it steps launch by launch)
+// value_kernel for a critic of shape s (mz_net_value; mz_rollout_net where it steps launch by launch); NRM as in net_act_kernel: the
+// row that is staged is the one the critic values, the final_obs row where the env finished
+template <bool NRM = false>
 __global__ __launch_bounds__(256) void net_value_kernel(int n, int obs_dim, mzp_shape s, const float* __restrict__ vparams, long vstride,
                                                         const float* __restrict__ obs, const float* __restrict__ final_obs,
-                                                        const uint8_t* __restrict__ done, float* __restrict__ values) {
+                                                        const uint8_t* __restrict__ done, float* __restrict__ values, mzp_norm nm) {
   __shared__ float hid[256 / MZ_POLICY_LANES][MZ_NET_MAX_HIDDEN_LAYERS][MZ_POLICY_MAX_HIDDEN];
   const int l = (int)threadIdx.x % MZ_POLICY_LANES, grp = (int)threadIdx.x / MZ_POLICY_LANES;
   size_t row = (size_t)blockIdx.x * (256 / MZ_POLICY_LANES) + grp;
   const bool live = row < (size_t)n;
   if (!live) row = (size_t)n - 1;
   const float* x = (done && done[row] ? final_obs : obs) + row * obs_dim;
-  const float v = mzp_group_net_value(l, MZ_POLICY_LANES, vparams + row * vstride, obs_dim, s, x, hid[grp][0], hid[grp][1]);
+  float v;
+  if constexpr (NRM) {
+    __shared__ float xn[256 / MZ_POLICY_LANES][MZ_MAX_OBS + MZ_VIEW_DIM];
+    mzp_group_norm(l, MZ_POLICY_LANES, nm, obs_dim, x, xn[grp]);
+    mzp_wave_sync();
+    v = mzp_group_net_value(l, MZ_POLICY_LANES, vparams + row * vstride, obs_dim, s, xn[grp], hid[grp][0], hid[grp][1]);
+  } else {
+    v = mzp_group_net_value(l, MZ_POLICY_LANES, vparams + row * vstride, obs_dim, s, x, hid[grp][0], hid[grp][1]);
+  }
   if (live && l == 0) values[row] = v;
 }
 
@@ -141,6 +166,42 @@ __global__ __launch_bounds__(64) void gae_kernel(int n, int nsteps, const float*
       }
     }
   }
+}
+
+// mz_return_scan: one lane per env, rows [k][env] coalesced across the lanes; the scan of mz_returns.h (mzr_step) from the first step
+// on.  The two loads of a step do not depend on the carries: a block of MZ_GAE_DEPTH steps is loaded before its dependent chain runs.
+// len_carry NULL: the length is not tracked (len_seq is NULL then: mz_return_scan).
+__global__ __launch_bounds__(64) void return_scan_kernel(int n, int nsteps, const float* __restrict__ reward, const uint8_t* __restrict__ done,
+                                                         float g, float* __restrict__ carry, int32_t* __restrict__ len_carry,
+                                                         float* __restrict__ ret_seq, int32_t* __restrict__ len_seq) {
+  const int env = blockIdx.x * blockDim.x + threadIdx.x;
+  if (env >= n) return;
+  float c = carry[env];
+  int32_t len = len_carry ? len_carry[env] : 0;
+  for (int k0 = 0; k0 < nsteps; k0 += MZ_GAE_DEPTH) {
+    float r[MZ_GAE_DEPTH];
+    uint8_t d[MZ_GAE_DEPTH];
+#pragma unroll
+    for (int j = 0; j < MZ_GAE_DEPTH; j++) {
+      const int k = k0 + j;
+      if (k < nsteps) {
+        const size_t i = (size_t)k * n + env;
+        r[j] = reward[i]; d[j] = done[i];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < MZ_GAE_DEPTH; j++) {
+      const int k = k0 + j;
+      if (k < nsteps) {
+        const size_t i = (size_t)k * n + env;
+        int32_t lo;
+        ret_seq[i] = mzr_step(r[j], d[j], g, &c, &len, &lo);
+        if (len_seq) len_seq[i] = lo;
+      }
+    }
+  }
+  carry[env] = c;
+  if (len_carry) len_carry[env] = len;
 }
 
 static int set_err(mz_handle* h, int code, const char* what, hipError_t e) {
@@ -366,6 +427,7 @@ int32_t mz_get_info(const mz_handle* h, const char* key, double* value) {
   if (!h || !key || !value) return MZ_ERR_ARG;
   if (!strcmp(key, "engine")) { *value = h->robot == MZ_ROBOT_GENERIC ? 1.0 : 0.0; return MZ_OK; }
   if (!strcmp(key, "device_simds")) { *value = (double)h->simds; return MZ_OK; }
+  if (!strcmp(key, "obs_norm")) { *value = h->nrm_mean ? 1.0 : 0.0; return MZ_OK; }  // mz_bind_obs_norm: a normaliser is bound (1) or not (0)
   if (!strcmp(key, "rollout_fused")) { *value = (double)mzk_planar_rollout_fused(h); return MZ_OK; }  // mz_rollout: fused kernels (1) or the step's launches in a loop (0)
   if (!strcmp(key, "ls_fast_iterations")) {  // Newton iterations of a solve that take unit steps (-1: this handle's kernels have no such phase)
     *value = h->robot == MZ_ROBOT_ANT ? (double)h->ant.ls_fast_iters : (h->robot == MZ_ROBOT_POINT ? (double)h->point.unit_steps : -1.0);
@@ -390,6 +452,21 @@ int32_t mz_bind_final_obs(mz_handle* h, float* final_obs_dev) {
 int32_t mz_bind_record(mz_handle* h, float* record_dev) {
   if (!h) return MZ_ERR_ARG;
   h->record = record_dev;
+  return MZ_OK;
+}
+
+// stores the two pointers and the clip and nothing else: no launch, no synchronisation (include/mazestep.h); a refused call leaves
+// the previous binding in place
+int32_t mz_bind_obs_norm(mz_handle* h, const float* mean_dev, const float* inv_std_dev, double clip, void* stream) {
+  (void)stream;
+  if (!h) return MZ_ERR_ARG;
+  if (!mean_dev && !inv_std_dev) { h->nrm_mean = h->nrm_inv_std = nullptr; h->nrm_clip = 0.0f; return MZ_OK; }
+  if (!mean_dev) return set_err(h, MZ_ERR_ARG, "mz_bind_obs_norm: mean_dev is NULL and inv_std_dev is not (both NULL unbinds)", hipSuccess);
+  if (!inv_std_dev) return set_err(h, MZ_ERR_ARG, "mz_bind_obs_norm: inv_std_dev is NULL and mean_dev is not (both NULL unbinds)", hipSuccess);
+  if (!(clip > 0.0)) return set_err(h, MZ_ERR_ARG, "mz_bind_obs_norm: clip must be > 0 (+inf switches the clip off) and not NaN", hipSuccess);
+  if (h->model.obs_dim > MZ_MAX_OBS + MZ_VIEW_DIM)  // the staged row of the NRM kernels; no handle mz_create makes is wider
+    return set_err(h, MZ_ERR_UNSUPPORTED, "mz_bind_obs_norm: obs_dim exceeds MZ_MAX_OBS + MZ_VIEW_DIM", hipSuccess);
+  h->nrm_mean = mean_dev; h->nrm_inv_std = inv_std_dev; h->nrm_clip = (float)clip;
   return MZ_OK;
 }
 
@@ -540,6 +617,17 @@ int32_t mz_rollout(mz_handle* h, int32_t n_steps, const float* actions_dev, int6
   return MZ_OK;
 }
 
+// A legacy network (int `hidden`, tanh) as the mz_net it is.  While a normaliser is bound (mz_bind_obs_norm) the legacy entries forward
+// to the network entries, which return the bits of the legacy ones for such a network and whose kernels have the NRM instantiations;
+// unbound handles launch what they always launched.
+static mz_net legacy_net(const float* params_dev, int64_t env_stride, int hidden, int squash, double action_scale) {
+  return mz_net{(uint32_t)sizeof(mz_net), hidden > 0 ? 1 : 0, {hidden, 0}, MZ_ACT_TANH, squash, action_scale, params_dev, env_stride};
+}
+static void net_act_launch(mz_handle* h, hipStream_t st, const mz_net* actor, int sample, uint64_t noise_seed, uint64_t noise_step,
+                           const float* obs_dev, float* actions_dev, float* logp_dev);
+static void net_value_launch(mz_handle* h, hipStream_t st, const mz_net* critic, const float* obs_dev, const float* final_obs_dev,
+                             const uint8_t* done_dev, float* values_dev);
+
 // the checks the four policy entries share (stochastic: the vector carries log_std[nu] behind the network); MZ_OK or MZ_ERR_ARG with
 // the message set
 static int policy_args(mz_handle* h, const char* who, const float* params_dev, int64_t param_env_stride, int32_t hidden, int32_t squash,
@@ -571,7 +659,12 @@ int32_t mz_policy_act(mz_handle* h, const float* params_dev, int64_t param_env_s
   const int rc = policy_args(h, "mz_policy_act", params_dev, param_env_stride, hidden, squash);
   if (rc != MZ_OK) return rc;
   DeviceScope scope(h->device);
-  policy_act_launch(h, (hipStream_t)stream, params_dev, param_env_stride, hidden, squash, (float)action_scale, obs_dev, actions_dev);
+  if (h->nrm_mean) {
+    const mz_net a = legacy_net(params_dev, param_env_stride, hidden, squash, action_scale);
+    net_act_launch(h, (hipStream_t)stream, &a, 0, 0, 0, obs_dev, actions_dev, NULL);
+  } else {
+    policy_act_launch(h, (hipStream_t)stream, params_dev, param_env_stride, hidden, squash, (float)action_scale, obs_dev, actions_dev);
+  }
   HIPCHK(h, hipGetLastError());
   return MZ_OK;
 }
@@ -587,6 +680,11 @@ int32_t mz_rollout_policy(mz_handle* h, int32_t n_steps, const float* params_dev
   if (n_steps < 1 || n_steps > 65536) return set_err(h, MZ_ERR_ARG, "mz_rollout_policy: n_steps must be 1 .. 65536", hipSuccess);
   int rc = policy_args(h, "mz_rollout_policy", params_dev, param_env_stride, hidden, squash);
   if (rc != MZ_OK) return rc;
+  if (h->nrm_mean) {
+    const mz_net a = legacy_net(params_dev, param_env_stride, hidden, squash, action_scale);
+    return mz_rollout_net(h, n_steps, &a, 0, 0, 0, NULL, NULL, NULL, obs_dev, reward_dev, done_dev, goal_idx_dev, info_dev, obs_seq_dev,
+                          actions_seq_dev, NULL, stream);
+  }
   const size_t n = (size_t)h->n, od = (size_t)h->model.obs_dim, nu = (size_t)h->model.nu;
   const float scale = (float)action_scale;
   DeviceScope scope(h->device);
@@ -629,8 +727,13 @@ int32_t mz_policy_sample(mz_handle* h, const float* params_dev, int64_t param_en
   const int rc = policy_args(h, "mz_policy_sample", params_dev, param_env_stride, hidden, squash, true);
   if (rc != MZ_OK) return rc;
   DeviceScope scope(h->device);
-  policy_sample_launch(h, (hipStream_t)stream, params_dev, param_env_stride, hidden, squash, (float)action_scale, noise_seed, noise_step, obs_dev,
-                       actions_dev, logp_dev);
+  if (h->nrm_mean) {
+    const mz_net a = legacy_net(params_dev, param_env_stride, hidden, squash, action_scale);
+    net_act_launch(h, (hipStream_t)stream, &a, 1, noise_seed, noise_step, obs_dev, actions_dev, logp_dev);
+  } else {
+    policy_sample_launch(h, (hipStream_t)stream, params_dev, param_env_stride, hidden, squash, (float)action_scale, noise_seed, noise_step, obs_dev,
+                         actions_dev, logp_dev);
+  }
   HIPCHK(h, hipGetLastError());
   return MZ_OK;
 }
@@ -646,6 +749,11 @@ int32_t mz_rollout_policy_sample(mz_handle* h, int32_t n_steps, const float* par
   if (n_steps < 1 || n_steps > 65536) return set_err(h, MZ_ERR_ARG, "mz_rollout_policy_sample: n_steps must be 1 .. 65536", hipSuccess);
   int rc = policy_args(h, "mz_rollout_policy_sample", params_dev, param_env_stride, hidden, squash, true);
   if (rc != MZ_OK) return rc;
+  if (h->nrm_mean) {
+    const mz_net a = legacy_net(params_dev, param_env_stride, hidden, squash, action_scale);
+    return mz_rollout_net(h, n_steps, &a, 1, noise_seed, noise_step, NULL, NULL, NULL, obs_dev, reward_dev, done_dev, goal_idx_dev, info_dev,
+                          obs_seq_dev, actions_seq_dev, logp_seq_dev, stream);
+  }
   const size_t n = (size_t)h->n, od = (size_t)h->model.obs_dim, nu = (size_t)h->model.nu;
   const float scale = (float)action_scale;
   DeviceScope scope(h->device);
@@ -702,7 +810,12 @@ int32_t mz_value(mz_handle* h, const float* vparams_dev, int64_t env_stride, int
   const int rc = critic_args(h, "mz_value", vparams_dev, env_stride, hidden);
   if (rc != MZ_OK) return rc;
   DeviceScope scope(h->device);
-  value_launch(h, (hipStream_t)stream, vparams_dev, env_stride, hidden, obs_dev, NULL, NULL, values_dev);
+  if (h->nrm_mean) {
+    const mz_net c = legacy_net(vparams_dev, env_stride, hidden, 0, 1.0);
+    net_value_launch(h, (hipStream_t)stream, &c, obs_dev, NULL, NULL, values_dev);
+  } else {
+    value_launch(h, (hipStream_t)stream, vparams_dev, env_stride, hidden, obs_dev, NULL, NULL, values_dev);
+  }
   HIPCHK(h, hipGetLastError());
   return MZ_OK;
 }
@@ -735,6 +848,12 @@ int32_t mz_rollout_actor_critic(mz_handle* h, int32_t n_steps, const float* para
   const size_t n = (size_t)h->n, od = (size_t)h->model.obs_dim, nu = (size_t)h->model.nu;
   const float scale = (float)action_scale;
   if (!sample) logp_seq_dev = NULL;
+  if (h->nrm_mean) {
+    const mz_net a = legacy_net(params_dev, param_env_stride, hidden, squash, action_scale);
+    const mz_net c = legacy_net(critic->params_dev, critic->env_stride, critic->hidden, 0, 1.0);
+    return mz_rollout_net(h, n_steps, &a, sample, noise_seed, noise_step, &c, critic->value_seq_dev, critic->next_value_seq_dev, obs_dev, reward_dev,
+                          done_dev, goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, logp_seq_dev, stream);
+  }
   DeviceScope scope(h->device);
   hipStream_t st = (hipStream_t)stream;
   if (mzk_planar_rollout_fused(h)) {
@@ -807,16 +926,24 @@ static bool net_shallow(const mz_net* net) { return net->n_hidden <= 1 && net->a
 static void net_act_launch(mz_handle* h, hipStream_t st, const mz_net* actor, int sample, uint64_t noise_seed, uint64_t noise_step,
                            const float* obs_dev, float* actions_dev, float* logp_dev) {
   const int rows = 256 / MZ_POLICY_LANES;
-  hipLaunchKernelGGL(net_act_kernel, dim3((unsigned)((h->n + rows - 1) / rows)), dim3(256), 0, st, h->n, h->model.obs_dim, h->model.nu, net_shape(actor),
-                     actor->squash, (float)actor->action_scale, actor->params_dev, (long)actor->env_stride, sample,
-                     sample ? mzp_noise_key(noise_seed, noise_step) : 0, h->env0, obs_dev, actions_dev, sample ? logp_dev : NULL);
+  const mzp_norm nm{h->nrm_mean, h->nrm_inv_std, h->nrm_clip};
+#define MZ_NET_ACT(NRM)                                                                                                                         \
+  hipLaunchKernelGGL(net_act_kernel<NRM>, dim3((unsigned)((h->n + rows - 1) / rows)), dim3(256), 0, st, h->n, h->model.obs_dim, h->model.nu,     \
+                     net_shape(actor), actor->squash, (float)actor->action_scale, actor->params_dev, (long)actor->env_stride, sample,           \
+                     sample ? mzp_noise_key(noise_seed, noise_step) : 0, h->env0, obs_dev, actions_dev, sample ? logp_dev : NULL, nm)
+  if (h->nrm_mean) MZ_NET_ACT(true); else MZ_NET_ACT(false);
+#undef MZ_NET_ACT
 }
 
 static void net_value_launch(mz_handle* h, hipStream_t st, const mz_net* critic, const float* obs_dev, const float* final_obs_dev,
                              const uint8_t* done_dev, float* values_dev) {
   const int rows = 256 / MZ_POLICY_LANES;
-  hipLaunchKernelGGL(net_value_kernel, dim3((unsigned)((h->n + rows - 1) / rows)), dim3(256), 0, st, h->n, h->model.obs_dim, net_shape(critic),
-                     critic->params_dev, (long)critic->env_stride, obs_dev, final_obs_dev, done_dev, values_dev);
+  const mzp_norm nm{h->nrm_mean, h->nrm_inv_std, h->nrm_clip};
+#define MZ_NET_VALUE(NRM)                                                                                                                        \
+  hipLaunchKernelGGL(net_value_kernel<NRM>, dim3((unsigned)((h->n + rows - 1) / rows)), dim3(256), 0, st, h->n, h->model.obs_dim, net_shape(critic), \
+                     critic->params_dev, (long)critic->env_stride, obs_dev, final_obs_dev, done_dev, values_dev, nm)
+  if (h->nrm_mean) MZ_NET_VALUE(true); else MZ_NET_VALUE(false);
+#undef MZ_NET_VALUE
 }
 
 int32_t mz_net_act(mz_handle* h, const mz_net* actor, int32_t sample, uint64_t noise_seed, uint64_t noise_step, const float* obs_dev,
@@ -845,7 +972,7 @@ int32_t mz_net_value(mz_handle* h, const mz_net* critic, const float* obs_dev, f
 
 // mz_rollout_actor_critic for networks described by mz_net (include/mazestep.h).  Fused handles evaluate both networks inside the
 // rollout kernels — the one-layer instantiations where both are at most one tanh hidden layer, the DEEP ones otherwise, which
-// compute the same bits for such a network —; every other handle runs the defining loop itself: net_value_kernel, net_act_kernel,
+// compute the same bits for such a network, and their NRM twins for every shape while a normaliser is bound —; every other handle runs the defining loop itself: net_value_kernel, net_act_kernel,
 // the step's own launches, net_value_kernel again with the final_obs row where the env finished under auto-reset.
 int32_t mz_rollout_net(mz_handle* h, int32_t n_steps, const mz_net* actor, int32_t sample, uint64_t noise_seed, uint64_t noise_step,
                        const mz_net* critic, float* value_seq_dev, float* next_value_seq_dev, float* obs_dev, float* reward_dev,
@@ -871,7 +998,7 @@ int32_t mz_rollout_net(mz_handle* h, int32_t n_steps, const mz_net* actor, int32
   DeviceScope scope(h->device);
   hipStream_t st = (hipStream_t)stream;
   if (mzk_planar_rollout_fused(h)) {
-    if (net_shallow(actor) && (!critic || net_shallow(critic))) {
+    if (!h->nrm_mean && net_shallow(actor) && (!critic || net_shallow(critic))) {
       const float* p = actor->params_dev;
       const long ps = (long)actor->env_stride;
       const int H = actor->hidden[0], sq = actor->squash;
@@ -928,6 +1055,22 @@ int32_t mz_gae(mz_handle* h, int32_t n_steps, const float* reward_dev, const uin
   DeviceScope scope(h->device);
   hipLaunchKernelGGL(gae_kernel, dim3((unsigned)((h->n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, h->n, n_steps, reward_dev, done_dev, value_dev,
                      next_value_dev, g, gl, adv_dev, ret_dev);
+  HIPCHK(h, hipGetLastError());
+  return MZ_OK;
+}
+
+int32_t mz_return_scan(mz_handle* h, int32_t n_steps, const float* reward_dev, const uint8_t* done_dev, double gamma, float* carry_dev,
+                       int32_t* len_carry_dev, float* ret_seq_dev, int32_t* len_seq_dev, void* stream) {
+  if (!h) return MZ_ERR_ARG;
+  if (!reward_dev || !done_dev) return set_err(h, MZ_ERR_ARG, "mz_return_scan: null array (reward_dev, done_dev)", hipSuccess);
+  if (!carry_dev) return set_err(h, MZ_ERR_ARG, "mz_return_scan: carry_dev is NULL", hipSuccess);
+  if (!ret_seq_dev) return set_err(h, MZ_ERR_ARG, "mz_return_scan: ret_seq_dev is NULL", hipSuccess);
+  if (len_seq_dev && !len_carry_dev)
+    return set_err(h, MZ_ERR_ARG, "mz_return_scan: len_seq_dev without len_carry_dev (a NULL len_carry_dev means the length is not tracked)", hipSuccess);
+  if (n_steps < 1 || n_steps > 65536) return set_err(h, MZ_ERR_ARG, "mz_return_scan: n_steps must be 1 .. 65536", hipSuccess);
+  DeviceScope scope(h->device);
+  hipLaunchKernelGGL(return_scan_kernel, dim3((unsigned)((h->n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, h->n, n_steps, reward_dev, done_dev,
+                     (float)gamma, carry_dev, len_carry_dev, ret_seq_dev, len_seq_dev);
   HIPCHK(h, hipGetLastError());
   return MZ_OK;
 }

@@ -60,6 +60,10 @@ struct mz_handle {
   long nsteps;
   float* render_qpos;  // [n][nq] scratch of mz_render without a caller's qpos (allocated on first use, freed by mz_destroy)
   float* policy_act;   // [n][nu] actions of mz_rollout_policy's launch-by-launch loop without a caller's actions_seq (allocated on first use, freed by mz_destroy)
+  // the caller's observation normaliser (mz_bind_obs_norm): [obs_dim] device arrays read by every network evaluation, or NULL both
+  const float* nrm_mean;
+  const float* nrm_inv_std;
+  float nrm_clip;
 };
 
 // ---- ant_kernels.hip
@@ -108,7 +112,8 @@ hipError_t mzk_planar_rollout_actor_critic(mz_handle* h, hipStream_t st, int nst
                                            float* obs, float* reward, uint8_t* done, int* goal_idx, float* info, float* obs_seq, float* actions_seq,
                                            float* logp_seq);
 // mz_rollout_net on the same handles where a network has two hidden layers or ReLU units: the same launches of the kernels' DEEP
-// instantiations, which evaluate networks of every shape mz_net describes (`actor`, `critic` — nullable — checked by the caller)
+// instantiations, which evaluate networks of every shape mz_net describes (`actor`, `critic` — nullable — checked by the caller);
+// with a normaliser bound (h->nrm_mean) their NRM twins, for every shape
 hipError_t mzk_planar_rollout_net(mz_handle* h, hipStream_t st, int nsteps, const mz_net* actor, int sample, uint64_t noise_seed,
                                   uint64_t noise_step, const mz_net* critic, float* value_seq, float* next_value_seq, float* obs, float* reward,
                                   uint8_t* done, int* goal_idx, float* info, float* obs_seq, float* actions_seq, float* logp_seq);

@@ -48,6 +48,16 @@
 // followed by log_std[nu] for a stochastic actor.  The same rules: one lane per unit, mzp_dot; a layer-2 unit reads the complete
 // layer-1 vector.  A one-layer tanh network through mzp_net_* runs the operations of the functions above in the same order and gives
 // the same bits; a ReLU network without squash is reproduced bit for bit by numpy at any depth (policy.py).
+//
+// Normalised observations (mz_bind_obs_norm; mzp_norm_elem below): while a normaliser is bound to the handle every network above reads
+// the row y in place of the raw row x — element i, fp32, every operation rounded separately:
+//     d = x[i] - mean[i];   y = d * inv_std[i];   y = y < -c ? -c : (y > c ? c : y)
+// A product with inv_std, not a quotient (mazestep.hip and planar_kernels.hip build with -freciprocal-math); two selects, not fminf /
+// fmaxf: a NaN passes through, c = +inf switches the clip off, x = +-inf becomes +-c, and a constant column (d == 0) becomes 0
+// whatever inv_std is — NaN and +-inf excepted, where 0 * inv_std is NaN.  Elementwise and pure, so the bits do not depend on the lane
+// that computes an element nor on whether a kernel stages the row (the NRM kernels: a second row in LDS) or computes it again; numpy
+// reproduces it bit for bit (policy.py normalize_reference), so an affine or ReLU network without squash on normalised rows stays
+// bit-reproducible.  The env itself never sees y: observations, the task predicate and info stay raw.
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -100,6 +110,20 @@ MZP_HD void mzp_policy_row(const float* par, int obs_dim, int nu, int H, int squ
   float hid[MZ_POLICY_MAX_HIDDEN];
   for (int j = 0; j < H; j++) hid[j] = mzp_hidden_unit(par, obs_dim, H, x, j);
   for (int u = 0; u < nu; u++) act[u] = mzp_output_unit(par, obs_dim, nu, H, squash, action_scale, H > 0 ? hid : x, u);
+}
+
+// element i of the normalised row (mz_bind_obs_norm; the head of this file): x = raw[i], mean = mean[i], inv_std = inv_std[i]
+MZP_HD float mzp_norm_elem(float x, float mean, float inv_std, float c) {
+#pragma clang fp contract(off) reassociate(off)
+  const float d = x - mean;
+  float y = d * inv_std;
+  y = y < -c ? -c : (y > c ? c : y);
+  return y;
+}
+
+// THE normalised row: y[obs_dim] from x[obs_dim] (the kernels spread the elements over the lanes of a group: mzp_group_norm)
+MZP_HD void mzp_norm_row(const float* x, const float* mean, const float* inv_std, float c, int obs_dim, float* y) {
+  for (int i = 0; i < obs_dim; i++) y[i] = mzp_norm_elem(x[i], mean[i], inv_std[i], c);
 }
 
 // ------------------------------------------------------------------ stochastic policies (definitions: the head of this file)
@@ -235,6 +259,19 @@ __device__ __forceinline__ void mzp_wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// the normaliser of one launch (mz_bind_obs_norm): [obs_dim] device arrays shared by all envs, read in stream order
+struct mzp_norm {
+  const float* mean;
+  const float* inv_std;
+  float clip;
+};
+
+// mzp_norm_row on a group: lanes l, l + G, ... each own the elements i = l, l + G, ... of y (LDS of this group), read from the raw
+// row x.  No lane of the group may still read y on entry, and the caller hands y over (mzp_wave_sync) before a unit reads it.
+__device__ __forceinline__ void mzp_group_norm(int l, int G, mzp_norm nm, int obs_dim, const float* x, float* y) {
+  for (int i = l; i < obs_dim; i += G) y[i] = mzp_norm_elem(x[i], nm.mean[i], nm.inv_std[i], nm.clip);
 }
 
 // One row on a group of G adjacent lanes of a wavefront (this lane: l): lanes l, l + G, ... each own one hidden unit, the hidden

@@ -270,12 +270,19 @@ struct PolicyCritic {
 struct PolicyShapes {
   mzp_shape actor, critic;
 };
-template <int NB, int NS, int G, bool SMP = false, bool CRT = false, bool DEEP = false>
+// NRM (a normaliser bound with mz_bind_obs_norm; instantiated for DEEP alone — bound handles route every shape there): the networks
+// read the normalised row of mz_policy.h, staged in a second LDS row per group (pnrm) beside the raw row `o`.  Every lane writes the
+// elements of pnrm it owns where it writes those of `o` — at the launch's start, after a step, after an in-kernel reset: the three
+// places after which a network reads the row — from the raw value it has just stored, so pnrm is rewritten exactly where `o` is and
+// the hand-offs that keep `o` from being rewritten under a reader keep pnrm.  Only the actor and the critic read pnrm; the task
+// predicate, every observation store and info read `o`.  NRM == false compiles the source as it was and never reads `nm`.
+template <int NB, int NS, int G, bool SMP = false, bool CRT = false, bool DEEP = false, bool NRM = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && NS == 0 && G == 32) ? 2 : 1))) void planar_policy_rollout_kernel(
     const PointDev* __restrict__ Pp, int n, PointState S, int nsteps, const float* __restrict__ params, long pstride, int hidden, int squash,
     float action_scale, float* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ done, int* __restrict__ goal_idx,
     float* __restrict__ info, float* __restrict__ obs_seq, float* __restrict__ actions_seq, int* __restrict__ status, int auto_reset,
-    uint64_t seed, uint64_t env0, float* __restrict__ final_obs, PolicyNoise ns, PolicyCritic cr, PolicyShapes sh) {
+    uint64_t seed, uint64_t env0, float* __restrict__ final_obs, PolicyNoise ns, PolicyCritic cr, PolicyShapes sh, mzp_norm nm) {
+  static_assert(!NRM || DEEP, "the normalised row is staged in the DEEP instantiations only");
   using D = PlanarDims<NB, NS>;
   constexpr int NV = D::NV, NOBS = D::NOBS, EPW = 64 / G;
   constexpr bool BARE = NB == 0 && NS == 0;
@@ -284,6 +291,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && 
   __shared__ float obuf[EPW][MZ_MAX_OBS];
   __shared__ float phid[EPW][DEEP ? 2 : 1][MZ_POLICY_MAX_HIDDEN];
   __shared__ float pact[EPW][2];
+  __shared__ float pnrm[NRM ? EPW : 1][NRM ? MZ_MAX_OBS : 1];  // (never referenced without NRM: no LDS is allocated for it)
   for (int i = threadIdx.x; i < (int)(sizeof(PointDev) / 4); i += blockDim.x) ((uint32_t*)&P)[i] = ((const uint32_t*)Pp)[i];
   __syncthreads();
   DevCtx<G> cx{(int)threadIdx.x % G};
@@ -293,16 +301,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && 
   if (!live) env = n - 1;  // idle groups shadow the last env (no stores), as in planar_step_kernel
   PlanarScratch<NB, NS>& s = scr[grp];
   float* o = obuf[grp];
+  auto stage = [&](int i) {  // element i of the normalised row from the raw element this lane has just written
+    if constexpr (NRM) pnrm[grp][i] = mzp_norm_elem(o[i], nm.mean[i], nm.inv_std[i], nm.clip);
+  };
   const float* par = params + (size_t)env * pstride;
   for (int k = cx.l; k < NV; k += G) { s.q[k] = (double)st_q(S, n, NV, k, env); s.v[k] = (double)st_v(S, n, NV, k, env); }
   if constexpr (BARE) { for (int k = cx.l; k < 3; k += G) s.wds[k] = (double)S.qv[(size_t)env * S.rec + PT_WARM_OFF + k]; }
-  for (int i = cx.l; i < NOBS; i += G) o[i] = obs[(size_t)env * NOBS + i];  // the observation the policy acts on first
+  for (int i = cx.l; i < NOBS; i += G) { o[i] = obs[(size_t)env * NOBS + i]; stage(i); }  // the observation the policy acts on first
   int t = st_t(S, NV, env), stacc = 0;
   uint32_t ep = st_ep(S, NV, env);
   const float* vpar = nullptr;
   float vcur = 0.0f;  // the group's first lane: V(the row in o)
   auto value_of_row = [&]() -> float {  // every lane of the group; phid must be free (mzp_group_value)
-    if constexpr (DEEP) return mzp_group_net_value(cx.l, G, vpar, NOBS, sh.critic, o, phid[grp][0], phid[grp][DEEP ? 1 : 0]);
+    if constexpr (NRM) return mzp_group_net_value(cx.l, G, vpar, NOBS, sh.critic, pnrm[grp], phid[grp][0], phid[grp][DEEP ? 1 : 0]);
+    else if constexpr (DEEP) return mzp_group_net_value(cx.l, G, vpar, NOBS, sh.critic, o, phid[grp][0], phid[grp][DEEP ? 1 : 0]);
     else return mzp_group_value(cx.l, G, vpar, NOBS, cr.hidden, o, phid[grp][0]);
   };
   if constexpr (CRT) {
@@ -314,7 +326,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && 
     const size_t row = (size_t)step * n + env;
     cx.sync();  // the row in o is complete (CRT: and the critic is done with phid)
     if constexpr (CRT) { if (live && cx.l == 0 && cr.value_seq) cr.value_seq[row] = vcur; }
-    if constexpr (DEEP)
+    if constexpr (NRM)
+      mzp_group_net_act(cx.l, G, par, NOBS, 2, sh.actor, squash, action_scale, SMP, SMP ? mzp_noise_key(ns.seed, ns.step + (uint64_t)step) : 0,
+                        env0 + (uint64_t)env, pnrm[grp], phid[grp][0], phid[grp][DEEP ? 1 : 0], pact[grp], true,
+                        SMP && live && ns.logp_seq ? ns.logp_seq + row : nullptr);
+    else if constexpr (DEEP)
       mzp_group_net_act(cx.l, G, par, NOBS, 2, sh.actor, squash, action_scale, SMP, SMP ? mzp_noise_key(ns.seed, ns.step + (uint64_t)step) : 0,
                         env0 + (uint64_t)env, o, phid[grp][0], phid[grp][DEEP ? 1 : 0], pact[grp], true,
                         SMP && live && ns.logp_seq ? ns.logp_seq + row : nullptr);
@@ -330,7 +346,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && 
     cx.sync();
     planar_env_step<NB, NS>(cx, P, s, a);
     const int t_new = t + 1;
-    for (int i = cx.l; i < NOBS; i += G) o[i] = planar_obs_elem<NB, NS>(P, s, i, t_new);
+    for (int i = cx.l; i < NOBS; i += G) { o[i] = planar_obs_elem<NB, NS>(P, s, i, t_new); stage(i); }
     cx.sync();
     float outer; int tm, gi;
     task_eval_dev(P.task, o, &outer, &tm, &gi, env);
@@ -371,7 +387,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && 
       }
       cx.sync();
       // the new episode's first row: what the policy acts on next (every lane stores the elements it has just written itself)
-      for (int i = cx.l; i < NOBS; i += G) o[i] = planar_obs_elem<NB, NS>(P, s, i, 0);
+      for (int i = cx.l; i < NOBS; i += G) { o[i] = planar_obs_elem<NB, NS>(P, s, i, 0); stage(i); }
       if (live) {
         if (oseq) for (int i = cx.l; i < NOBS; i += G) oseq[i] = o[i];
         if (olast) for (int i = cx.l; i < NOBS; i += G) olast[i] = o[i];
@@ -628,14 +644,18 @@ __global__ __launch_bounds__(256) void swimmer_rollout_kernel(const SwimmerDev* 
 // there (the fp32 row swimmer_store_row writes to final_obs when the env is about to reset: rows are NO floats apart here, so both
 // are o[0 .. NO - 1]), the group values it, and after a reset the new episode's first row follows and is valued once more.
 // DEEP: as in planar_policy_rollout_kernel; the second hidden row takes the block's LDS from 20 KB to 36 KB.
-template <int NL, int NB, int G, bool SMP = false, bool CRT = false, bool DEEP = false>
+// NRM: as in planar_policy_rollout_kernel.  Here the raw row lives in registers and px is what the networks read and nothing else
+// reads, so px IS the staged row: wherever a lane puts raw elements there it puts mzp_norm_elem of them (px_elem), at the places px
+// was written before, under the hand-offs it had before.  Stores, the task predicate and info go on reading the registers.
+template <int NL, int NB, int G, bool SMP = false, bool CRT = false, bool DEEP = false, bool NRM = false>
 __global__ __launch_bounds__(256) void swimmer_policy_rollout_kernel(const SwimmerDev* __restrict__ Pp, int n, PointState S, int nsteps,
                                                                       const float* __restrict__ params, long pstride, int hidden, int squash,
                                                                       float action_scale, float* __restrict__ obs, float* __restrict__ reward,
                                                                       uint8_t* __restrict__ done, int* __restrict__ goal_idx, float* __restrict__ info,
                                                                       float* __restrict__ obs_seq, float* __restrict__ actions_seq, int* __restrict__ status,
                                                                       int auto_reset, uint64_t seed, uint64_t env0, float* __restrict__ final_obs,
-                                                                      PolicyNoise ns, PolicyCritic cr, PolicyShapes sh) {
+                                                                      PolicyNoise ns, PolicyCritic cr, PolicyShapes sh, mzp_norm nm) {
+  static_assert(!NRM || DEEP, "the normalised row is staged in the DEEP instantiations only");
   constexpr int NR = NL + 2, NV = NR + NB, NH = NL - 1, NOMAX = 2 * NV + 4, GPB = 256 / G;
   __shared__ float px[GPB][NOMAX];
   __shared__ float phid[GPB][DEEP ? 2 : 1][MZ_POLICY_MAX_HIDDEN];
@@ -652,8 +672,12 @@ __global__ __launch_bounds__(256) void swimmer_policy_rollout_kernel(const Swimm
   double inner, inf4[4];
   const float* par = params + (size_t)env * pstride;
   float* x = px[grp];
+  auto px_elem = [&](float v, int i) -> float {  // what px holds for the raw element v of column i
+    if constexpr (NRM) return mzp_norm_elem(v, nm.mean[i], nm.inv_std[i], nm.clip);
+    else return v;
+  };
   for (int k = 0; k < NV; k++) { qf[k] = S.qv[(size_t)k * n + env]; vf[k] = S.qv[(size_t)(NV + k) * n + env]; }
-  for (int i = cx.l; i < NO; i += G) x[i] = obs[(size_t)env * NO + i];  // the observation the policy acts on first
+  for (int i = cx.l; i < NO; i += G) x[i] = px_elem(obs[(size_t)env * NO + i], i);  // the observation the policy acts on first
   int t = S.t[env], stacc = 0;
   uint32_t ep = S.ep[env];
   const int lane0 = (int)(threadIdx.x & 63u) - cx.l;
@@ -709,7 +733,7 @@ __global__ __launch_bounds__(256) void swimmer_policy_rollout_kernel(const Swimm
     if constexpr (CRT) {  // V(the row this step produced), before a reset replaces it; x and phid were handed over with the actions
       if (lead) {
 #pragma unroll
-        for (int k = 0; k < NOMAX; k++) if (k < NO) x[k] = o[k];
+        for (int k = 0; k < NOMAX; k++) if (k < NO) x[k] = px_elem(o[k], k);
       }
       mzp_wave_sync();
       vcur = value_of_row();
@@ -734,7 +758,7 @@ __global__ __launch_bounds__(256) void swimmer_policy_rollout_kernel(const Swimm
         mzp_wave_sync();  // the terminal row and its hidden units have been read
         if (lead) {
 #pragma unroll
-          for (int k = 0; k < NOMAX; k++) if (k < NO) x[k] = o[k];
+          for (int k = 0; k < NOMAX; k++) if (k < NO) x[k] = px_elem(o[k], k);
         }
         mzp_wave_sync();
         vcur = value_of_row();
@@ -742,7 +766,7 @@ __global__ __launch_bounds__(256) void swimmer_policy_rollout_kernel(const Swimm
     } else {
       if (lead) {
 #pragma unroll
-        for (int k = 0; k < NOMAX; k++) if (k < NO) x[k] = o[k];
+        for (int k = 0; k < NOMAX; k++) if (k < NO) x[k] = px_elem(o[k], k);
       }
     }
   }
@@ -962,7 +986,8 @@ hipError_t mzk_planar_rollout(mz_handle* h, hipStream_t st, int nsteps, const fl
 // its last step, and the next one reads its first observation there — and continues at noise_step + the steps done so far.
 // CRT (mz_rollout_actor_critic with a critic): `critic` holds the critic's parameters and the call's value_seq / next_value_seq.
 // DEEP (mz_rollout_net with a network of two hidden layers or ReLU units): `shapes` holds both networks' shapes.
-template <bool SMP, bool CRT = false, bool DEEP = false>
+// NRM (DEEP with a normaliser bound): the kernels' NRM instantiations, with the handle's normaliser.
+template <bool SMP, bool CRT = false, bool DEEP = false, bool NRM = false>
 static hipError_t planar_rollout_policy_launches(mz_handle* h, hipStream_t st, int nsteps, const float* params_dev, long pstride, int hidden,
                                                  int squash, float action_scale, float* obs_dev, float* reward_dev, uint8_t* done_dev,
                                                  int* goal_idx_dev, float* info_dev, float* obs_seq_dev, float* actions_seq_dev, PolicyNoise noise,
@@ -970,6 +995,7 @@ static hipError_t planar_rollout_policy_launches(mz_handle* h, hipStream_t st, i
                                                  PolicyShapes shapes = PolicyShapes{{0, 0, 0, 0}, {0, 0, 0, 0}}) {
   PointState S{h->state, h->pt_t, h->pt_ep, h->pt_rec};
   const size_t n = (size_t)h->n, od = (size_t)h->model.obs_dim, nu = (size_t)h->model.nu;
+  const mzp_norm nm{h->nrm_mean, h->nrm_inv_std, h->nrm_clip};
   for (int k0 = 0; k0 < nsteps; k0 += MZ_ROLLOUT_CHUNK) {
     const int ks = nsteps - k0 < MZ_ROLLOUT_CHUNK ? nsteps - k0 : MZ_ROLLOUT_CHUNK;
     float* rew = reward_dev + k0 * n;
@@ -983,9 +1009,9 @@ static hipError_t planar_rollout_policy_launches(mz_handle* h, hipStream_t st, i
                           critic.next_value_seq ? critic.next_value_seq + k0 * n : nullptr};
     if (h->robot == MZ_ROBOT_SWIMMER) {
 #define MZ_SW_ROLL(NL, NB)                                                                                                          \
-  hipLaunchKernelGGL((swimmer_policy_rollout_kernel<NL, NB, (NL <= 4 ? 4 : 8), SMP, CRT, DEEP>), dim3((unsigned)((n * (NL <= 4 ? 4 : 8) + sw_bd - 1) / sw_bd)), dim3(sw_bd), 0, st, \
+  hipLaunchKernelGGL((swimmer_policy_rollout_kernel<NL, NB, (NL <= 4 ? 4 : 8), SMP, CRT, DEEP, NRM>), dim3((unsigned)((n * (NL <= 4 ? 4 : 8) + sw_bd - 1) / sw_bd)), dim3(sw_bd), 0, st, \
                      h->swimmer_dev, h->n, S, ks, params_dev, pstride, hidden, squash, action_scale, obs_dev, rew, dn, gi, inf, oseq, aseq, h->status,         \
-                     h->auto_reset, h->seed, h->env0, h->final_obs, ns, cr, shapes)
+                     h->auto_reset, h->seed, h->env0, h->final_obs, ns, cr, shapes, nm)
       const int bd = h->swimmer.nblock ? h->swimmer.nbdof : 0;
       const unsigned sw_bd = 64u * (unsigned)(h->wpb_set ? h->waves_per_block : 4);
       if (h->swimmer.nlink == 3) { if (bd == 3) MZ_SW_ROLL(3, 3); else if (bd == 2) MZ_SW_ROLL(3, 2); else MZ_SW_ROLL(3, 0); }
@@ -996,8 +1022,8 @@ static hipError_t planar_rollout_policy_launches(mz_handle* h, hipStream_t st, i
 #undef MZ_SW_ROLL
     } else {
 #define MZ_PLANAR_ROLL(NB, NS, G)                                                                                                      \
-  hipLaunchKernelGGL((planar_policy_rollout_kernel<NB, NS, G, SMP, CRT, DEEP>), dim3((h->n + 64 / G - 1) / (64 / G)), dim3(64), 0, st, h->point_dev, h->n, S, ks, params_dev, \
-                     pstride, hidden, squash, action_scale, obs_dev, rew, dn, gi, inf, oseq, aseq, h->status, h->auto_reset, h->seed, h->env0, h->final_obs, ns, cr, shapes)
+  hipLaunchKernelGGL((planar_policy_rollout_kernel<NB, NS, G, SMP, CRT, DEEP, NRM>), dim3((h->n + 64 / G - 1) / (64 / G)), dim3(64), 0, st, h->point_dev, h->n, S, ks, params_dev, \
+                     pstride, hidden, squash, action_scale, obs_dev, rew, dn, gi, inf, oseq, aseq, h->status, h->auto_reset, h->seed, h->env0, h->final_obs, ns, cr, shapes, nm)
       if (h->point.nball) MZ_PLANAR_ROLL(0, 1, 32);
       else switch (h->point.nblock) {
         case 0: {
@@ -1058,12 +1084,16 @@ hipError_t mzk_planar_rollout_net(mz_handle* h, hipStream_t st, int nsteps, cons
     sh.critic = mzp_shape{critic->n_hidden, critic->hidden[0], critic->hidden[1], critic->activation};
     cr = PolicyCritic{critic->params_dev, (long)critic->env_stride, 0, value_seq_dev, next_value_seq_dev};
   }
-#define MZ_NET_ROLL(SMP, CRT)                                                                                                               \
-  planar_rollout_policy_launches<SMP, CRT, true>(h, st, nsteps, actor->params_dev, (long)actor->env_stride, 0, actor->squash,               \
-                                                 (float)actor->action_scale, obs_dev, reward_dev, done_dev, goal_idx_dev, info_dev, obs_seq_dev, \
-                                                 actions_seq_dev, ns, cr, sh)
-  if (critic) return sample ? MZ_NET_ROLL(true, true) : MZ_NET_ROLL(false, true);
-  return sample ? MZ_NET_ROLL(true, false) : MZ_NET_ROLL(false, false);
+#define MZ_NET_ROLL(SMP, CRT, NRM)                                                                                                          \
+  planar_rollout_policy_launches<SMP, CRT, true, NRM>(h, st, nsteps, actor->params_dev, (long)actor->env_stride, 0, actor->squash,          \
+                                                      (float)actor->action_scale, obs_dev, reward_dev, done_dev, goal_idx_dev, info_dev,    \
+                                                      obs_seq_dev, actions_seq_dev, ns, cr, sh)
+  if (h->nrm_mean) {
+    if (critic) return sample ? MZ_NET_ROLL(true, true, true) : MZ_NET_ROLL(false, true, true);
+    return sample ? MZ_NET_ROLL(true, false, true) : MZ_NET_ROLL(false, false, true);
+  }
+  if (critic) return sample ? MZ_NET_ROLL(true, true, false) : MZ_NET_ROLL(false, true, false);
+  return sample ? MZ_NET_ROLL(true, false, false) : MZ_NET_ROLL(false, false, false);
 #undef MZ_NET_ROLL
 }
 

@@ -191,6 +191,7 @@ class VecMazeEnv:
         self._final_obs = None
         self._host_mask = None
         self._record = None
+        self._obs_norm = None    # (mean, inv_std) of bind_obs_norm: the env holds a reference while the handle holds the pointers
         self._resampled_goals = False
         self._warned_goal_resampling = False
         self._env_goals = None   # float64 [N, MZ_MAX_GOAL, 3] once the task's sample_goals() said the goals move (per-env goal positions)
@@ -216,11 +217,12 @@ class VecMazeEnv:
 
     def launch_info(self) -> dict:
         """What the next step launches (mz_get_info): the engine (0 = the robot family's specialised kernel, 1 = the general engine),
-        lanes per env, waves per SIMD, the device's SIMD count, and whether rollout() runs this env on fused kernels ("rollout_fused":
-        1) or on the step's launches in a loop (0).  The instantiation depends on the batch size and the device; its
+        lanes per env, waves per SIMD, the device's SIMD count, whether rollout() runs this env on fused kernels ("rollout_fused":
+        1) or on the step's launches in a loop (0), and whether an observation normaliser is bound ("obs_norm": `bind_obs_norm`).  The
+        instantiation depends on the batch size and the device; its
         results agree across instantiations to fp32 round-off, not bit for bit (include/mazestep.h)."""
         out = {}
-        for key in ("engine", "lanes_per_env", "waves_per_simd", "device_simds", "ls_fast_iterations", "rollout_fused"):
+        for key in ("engine", "lanes_per_env", "waves_per_simd", "device_simds", "ls_fast_iterations", "rollout_fused", "obs_norm"):
             v = C.c_double(0.0)
             _capi.check(self._lib, self._h, self._lib.mz_get_info(self._h, key.encode(), C.byref(v)), f"mz_get_info({key})")
             out[key] = int(v.value)
@@ -252,6 +254,30 @@ class VecMazeEnv:
                 raise ValueError(f"record must be a contiguous float32 tensor of shape {(self.num_envs, self.obs_dim + 2)} on {self.device}")
         self._record = record
         _capi.check(self._lib, self._h, self._lib.mz_bind_record(self._h, _ptr(record)), "mz_bind_record")
+
+    def bind_obs_norm(self, mean, inv_std, clip: float = 10.0) -> None:
+        """Bind an observation normaliser to the device-side networks (mz_bind_obs_norm): while bound, `policy_act`, `policy_sample`,
+        `value` and every closed-loop rollout evaluate their networks on clip((obs - mean) * inv_std, -clip, clip) — float32,
+        elementwise, `policy.normalize_reference` bit for bit — in place of the raw row, the critic's terminal rows included.
+        Everything the env itself returns stays raw: observations, `info["observations"]`, `info["final_observation"]`, rewards, dones;
+        `step` and the open-loop `rollout` do not look at the binding.  mean, inv_std: contiguous float32 [obs_dim] tensors on the
+        env's device, one normaliser for all envs.  The env keeps a reference and the kernels read them at every call, so rewriting
+        them IN PLACE (`normalize.RunningMeanStd.update`) takes effect at the next call without binding again.
+        `bind_obs_norm(None, None)` unbinds.  A refused call leaves the previous binding in place."""
+        torch = self._torch
+        if mean is None and inv_std is None:
+            _capi.check(self._lib, self._h, self._lib.mz_bind_obs_norm(self._h, None, None, float(clip), self._stream()), "mz_bind_obs_norm")
+            self._obs_norm = None
+            return
+        for name, t in (("mean", mean), ("inv_std", inv_std)):
+            if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != (self.obs_dim,) or t.device != self.device \
+                    or not t.is_contiguous():
+                got = f"{tuple(t.shape)} {t.dtype} on {t.device}" if torch.is_tensor(t) else type(t).__name__
+                raise ValueError(f"{name} must be a contiguous float32 tensor of shape {(self.obs_dim,)} on {self.device} (the kernels read "
+                                 f"it in place at every call), got {got}")
+        _capi.check(self._lib, self._h, self._lib.mz_bind_obs_norm(self._h, _ptr(mean), _ptr(inv_std), float(clip), self._stream()),
+                    "mz_bind_obs_norm")
+        self._obs_norm = (mean, inv_std)
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -742,6 +768,41 @@ class VecMazeEnv:
         rc = self._lib.mz_gae(self._h, K, _ptr(r), _ptr(d), _ptr(v), _ptr(nv), float(gamma), float(lam), _ptr(adv), _ptr(ret), self._stream())
         _capi.check(self._lib, self._h, rc, "mz_gae")
         return adv, ret
+
+    def return_scan(self, rewards, dones, gamma: float = 1.0, carry=None, length_carry=None):
+        """Running discounted returns and episode step counts of a rollout in one kernel (mz_return_scan): rewards float32 [K, N],
+        dones uint8 [K, N].  Per env, from the first step on, in float32: ret = gamma * carry + reward; length += 1; an episode end
+        (done != 0) then clears both.  carry: float32 [N], length_carry: int32 [N] — contiguous tensors on the env's device, UPDATED IN
+        PLACE, so that the next rollout's scan continues where this one stopped; None: fresh zeros for this call.  With gamma = 1
+        `ret_seq[dones != 0]` are the returns of the episodes that ended and `len_seq[dones != 0]` their lengths; with gamma < 1
+        ret_seq is the series whose running variance reward scaling divides by (`normalize.RunningMeanStd`).
+        `policy.return_scan_reference` is the numpy model, bit-equal.  Returns (ret_seq float32 [K, N], len_seq int32 [K, N])."""
+        torch, n = self._torch, self.num_envs
+
+        def arr(t, dtype, what):
+            t = t if torch.is_tensor(t) else torch.as_tensor(np.asarray(t), device=self.device)
+            if t.dtype != dtype or not t.is_contiguous() or t.device != self.device:
+                t = t.to(device=self.device, dtype=dtype).contiguous()
+            if t.dim() != 2 or t.shape[1] != n:
+                raise ValueError(f"{what} must have shape (K, {n}), got {tuple(t.shape)}")
+            return t
+
+        def carried(t, dtype, what):
+            if t is None:
+                return torch.zeros(n, dtype=dtype, device=self.device)
+            if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != (n,) or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"{what} must be a contiguous {dtype} tensor of shape {(n,)} on {self.device} (it is updated in place)")
+            return t
+
+        r, d = arr(rewards, torch.float32, "rewards"), arr(dones, torch.uint8, "dones")
+        K = int(r.shape[0])
+        if d.shape != r.shape or not 1 <= K <= 65536:
+            raise ValueError(f"rewards and dones must share one (K, {n}) shape with 1 <= K <= 65536, got {tuple(r.shape)}, {tuple(d.shape)}")
+        c, lc = carried(carry, torch.float32, "carry"), carried(length_carry, torch.int32, "length_carry")
+        ret, ln = torch.empty_like(r), torch.empty((K, n), dtype=torch.int32, device=self.device)
+        rc = self._lib.mz_return_scan(self._h, K, _ptr(r), _ptr(d), float(gamma), _ptr(c), _ptr(lc), _ptr(ret), _ptr(ln), self._stream())
+        _capi.check(self._lib, self._h, rc, "mz_return_scan")
+        return ret, ln
 
     def _rollout_actor_critic(self, sample: bool, params, steps, hidden, squash, action_scale, obs, noise_seed, noise_step, return_obs,
                               return_actions, value_params, value_hidden, gae, activation="tanh", value_activation="tanh"):

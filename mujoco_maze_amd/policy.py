@@ -40,6 +40,11 @@ sequence of one or two widths, and `activation` is "tanh" or "relu", one choice 
 
 then log_std [nu] for a stochastic actor.  ReLU is `0 if acc < 0 else acc`: no rounding, -0.0 stays -0.0, NaN propagates — so a
 ReLU network without squash equals the device bit for bit at any depth.
+
+Normalised observations (VecMazeEnv.bind_obs_norm, mz_bind_obs_norm): while a normaliser is bound the device evaluates its networks
+on `normalize_reference(obs, mean, inv_std, clip)` — bit-equal to the device — so the model of a bound call is
+`reference(params, normalize_reference(obs, mean, inv_std, clip), ...)`, and likewise for `sample_reference` / `value_reference`.
+`return_scan_reference` is the forward scan of VecMazeEnv.return_scan / mz_return_scan (csrc/mz_returns.h), bit-equal too.
 """
 import numpy as np
 
@@ -286,3 +291,58 @@ def gae_reference(rewards, dones, values, next_values, gamma: float = 0.99, lam:
             adv[k] = carry
             ret[k] = (carry + v[k]).astype(np.float32)
     return adv, ret
+
+
+def normalize_reference(obs, mean, inv_std, clip: float = 10.0):
+    """The normalised rows of csrc/mz_policy.h (mzp_norm_elem) in float32, operation by operation, every operation rounded separately:
+
+        d = x - mean;  y = d * inv_std;  y = -c if y < -c else (c if y > c else y)        c = float32(clip)
+
+    A product with inv_std, not a quotient; two selects, not minimum / maximum: NaN passes through, clip = inf switches the clip off,
+    x = +-inf becomes +-c, a constant column (d == 0) becomes 0 for any finite inv_std.  obs [..., obs_dim]; mean, inv_std
+    [obs_dim].  Returns float32 of obs's shape; bit-equal to the device."""
+    x = _np(obs)
+    m, s = _np(mean), _np(inv_std)
+    if m.ndim != 1 or m.shape != s.shape or x.shape[-1:] != m.shape:
+        raise ValueError(f"mean and inv_std must be [obs_dim] = {x.shape[-1:]}, got {m.shape} and {s.shape}")
+    c = np.float32(clip)
+    if not c > 0:
+        raise ValueError(f"clip must be > 0, got {clip}")
+    with np.errstate(over="ignore", invalid="ignore"):
+        d = (x - m).astype(np.float32)
+        y = (d * s).astype(np.float32)
+        y = np.where(y < -c, -c, np.where(y > c, c, y)).astype(np.float32)
+    return y
+
+
+def return_scan_reference(rewards, dones, gamma: float = 1.0, carry=None, length_carry=None):
+    """The forward scan of csrc/mz_returns.h (mz_return_scan) on [K, N] rows, float32, every operation rounded separately, k from 0 up:
+
+        g = float32(gamma)
+        p = g * carry; s = p + reward; ret_seq[k] = s; len = len + 1; len_seq[k] = len
+        carry = 0 if done else s;  len = 0 if done else len
+
+    carry float32 [N] and length_carry int32 [N] are numpy arrays UPDATED IN PLACE as the device updates its tensors (None: fresh
+    zeros for this call), so two scans in a row equal one over the joined rows.  Returns (ret_seq float32 [K, N], len_seq int32
+    [K, N]); bit-equal to the device."""
+    r = np.asarray(rewards, dtype=np.float32)
+    d = np.asarray(dones, dtype=np.uint8)
+    if r.ndim != 2 or r.shape != d.shape:
+        raise ValueError(f"rewards and dones must share one [K, N] shape, got {r.shape}, {d.shape}")
+    N = r.shape[1]
+    for what, a, dt in (("carry", carry, np.float32), ("length_carry", length_carry, np.int32)):
+        if a is not None and (not isinstance(a, np.ndarray) or a.dtype != dt or a.shape != (N,)):
+            raise ValueError(f"{what} must be a numpy {np.dtype(dt).name} array of shape {(N,)} (it is updated in place)")
+    c = np.zeros(N, dtype=np.float32) if carry is None else carry
+    ln = np.zeros(N, dtype=np.int32) if length_carry is None else length_carry
+    g = np.float32(gamma)
+    ret, lens = np.empty_like(r), np.empty(r.shape, dtype=np.int32)
+    zero = np.float32(0.0)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for k in range(r.shape[0]):
+            s = ((g * c).astype(np.float32) + r[k]).astype(np.float32)
+            n = (ln + np.int32(1)).astype(np.int32)
+            ret[k], lens[k] = s, n
+            c[:] = np.where(d[k] != 0, zero, s)
+            ln[:] = np.where(d[k] != 0, np.int32(0), n)
+    return ret, lens

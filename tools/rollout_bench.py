@@ -18,6 +18,10 @@ closes — its cost is what this compares, not its result.)
 --policy and --critic also take two widths, `64,64`: a network with two hidden layers (mz_net_act / mz_rollout_net), the torch legs then
 run a two-layer torch MLP; --activation tanh|relu chooses the hidden units of both networks (relu goes through the same entries).
     python tools/rollout_bench.py --policy 64,64 --sample --critic 64,64 --activation relu --steps 128
+With --obs-norm every --policy mode binds an observation normaliser first (env.bind_obs_norm: mean and 1 / (std + 0.1) of the rows of
+a few random steps, clip 5), so that all its legs evaluate their networks on normalised rows; a torch network normalises and clamps
+in torch.
+    python tools/rollout_bench.py --policy 64,64 --sample --critic 64,64 --steps 128 --obs-norm --ids PointUMaze-v0,SwimmerUMaze-v0
 Kernel durations come from a run of their own:  rocprofv3 --kernel-trace --stats -d <dir> -- python tools/rollout_bench.py --seconds 0.2"""
 import argparse
 import json
@@ -73,6 +77,20 @@ def build_net(lin, obs_dim, nout, hidden, activation, dev, log_std=None):
     return params, fn
 
 
+def bind_norm(env, on, dev, g):
+    """With `on`: binds a normaliser built from the rows of four random steps and returns what a torch network applies to its rows;
+    else the identity.  The env is reset afterwards, so that every leg starts as it does without a normaliser."""
+    if not on:
+        return lambda obs: obs
+    lo, hi = torch.as_tensor(env.action_space.low, device=dev), torch.as_tensor(env.action_space.high, device=dev)
+    rows = torch.stack([env.step(lo + (hi - lo) * torch.rand((env.num_envs, env.nu), device=dev, generator=g))[0].clone() for _ in range(4)])
+    rows = torch.nan_to_num(rows.view(-1, env.obs_dim))
+    mean, inv_std, clip = rows.mean(dim=0).contiguous(), (1.0 / (rows.std(dim=0) + 0.1)).contiguous(), 5.0
+    env.bind_obs_norm(mean, inv_std, clip)
+    env.reset(seed=20260928)
+    return lambda obs: torch.clamp((obs - mean) * inv_std, -clip, clip)
+
+
 def bench(env_id, n, K, seconds, repeats):
     dev = torch.device("cuda", 0)
     env = mm.make(env_id, num_envs=n, auto_reset=True, device=dev, force_vec=True)
@@ -103,12 +121,13 @@ def bench(env_id, n, K, seconds, repeats):
             "step_env_steps_per_s": res["step"], "rollout_env_steps_per_s": res["rollout"]}
 
 
-def bench_policy(env_id, n, K, H, seconds, repeats, ACT="tanh"):
+def bench_policy(env_id, n, K, H, seconds, repeats, ACT="tanh", obs_norm=False):
     """K closed-loop steps of one shared policy, three ways: torch policy + step, policy_act + step, one rollout_policy."""
     dev = torch.device("cuda", 0)
     env = mm.make(env_id, num_envs=n, auto_reset=True, device=dev, force_vec=True)
     env.reset(seed=20260928)
     g = torch.Generator(device=dev).manual_seed(1234)
+    nrm = bind_norm(env, obs_norm, dev, g)
 
     def lin(out, fan_in):
         k = fan_in ** -0.5
@@ -119,7 +138,7 @@ def bench_policy(env_id, n, K, H, seconds, repeats, ACT="tanh"):
 
     def torch_step():
         for k in range(K):
-            state["obs"] = env.step(torch_policy(state["obs"]))[0]
+            state["obs"] = env.step(torch_policy(nrm(state["obs"])))[0]
 
     def act_step():
         for k in range(K):
@@ -140,17 +159,18 @@ def bench_policy(env_id, n, K, H, seconds, repeats, ACT="tanh"):
     bad = int((env.status() & 3).ne(0).sum())
     fused_flag = env.launch_info()["rollout_fused"]
     env.close()
-    return {"env": env_id, "envs": n, "steps_per_window": K, "hidden": H, "activation": ACT, "fused": fused_flag, "flagged_envs": bad,
+    return {"env": env_id, "envs": n, "steps_per_window": K, "hidden": H, "activation": ACT, "obs_norm": bool(obs_norm), "fused": fused_flag, "flagged_envs": bad,
             **{name + "_env_steps_per_s": v for name, v in res.items()}}
 
 
-def bench_sample(env_id, n, K, H, seconds, repeats, ACT="tanh"):
+def bench_sample(env_id, n, K, H, seconds, repeats, ACT="tanh", obs_norm=False):
     """K closed-loop steps of one shared Gaussian policy: policy_sample + step, one rollout_policy_sample; the deterministic
     rollout_policy of the same network as the yardstick."""
     dev = torch.device("cuda", 0)
     env = mm.make(env_id, num_envs=n, auto_reset=True, device=dev, force_vec=True)
     env.reset(seed=20260928)
     g = torch.Generator(device=dev).manual_seed(1234)
+    bind_norm(env, obs_norm, dev, g)  # (no torch network in this mode)
 
     def lin(out, fan_in):
         k = fan_in ** -0.5
@@ -182,17 +202,18 @@ def bench_sample(env_id, n, K, H, seconds, repeats, ACT="tanh"):
     bad = int((env.status() & 3).ne(0).sum())
     fused_flag = env.launch_info()["rollout_fused"]
     env.close()
-    return {"env": env_id, "envs": n, "steps_per_window": K, "hidden": H, "activation": ACT, "sample": True, "fused": fused_flag, "flagged_envs": bad,
+    return {"env": env_id, "envs": n, "steps_per_window": K, "hidden": H, "activation": ACT, "obs_norm": bool(obs_norm), "sample": True, "fused": fused_flag, "flagged_envs": bad,
             **{name + "_env_steps_per_s": v for name, v in res.items()}}
 
 
-def bench_critic(env_id, n, K, H, HV, seconds, repeats, ACT="tanh"):
+def bench_critic(env_id, n, K, H, HV, seconds, repeats, ACT="tanh", obs_norm=False):
     """One actor-critic collection window of K steps: policy_sample + step + torch critic + torch GAE loop; one
     rollout_policy_sample with value_params and gae; the same call without a critic."""
     dev = torch.device("cuda", 0)
     env = mm.make(env_id, num_envs=n, auto_reset=True, device=dev, force_vec=True)
     env.reset(seed=20260928)
     g = torch.Generator(device=dev).manual_seed(1234)
+    nrm = bind_norm(env, obs_norm, dev, g)
     gamma, lam = 0.99, 0.95
 
     def lin(out, fan_in):
@@ -211,7 +232,7 @@ def bench_critic(env_id, n, K, H, HV, seconds, repeats, ACT="tanh"):
         for k in range(K):
             o, r, d, _ = env.step(env.policy_sample(params, hidden=H, activation=ACT)[0])
             rows[k + 1], rew[k], done[k] = o, r, d
-        v = torch_critic(rows.view((K + 1) * n, env.obs_dim)).view(K + 1, n)
+        v = torch_critic(nrm(rows.view((K + 1) * n, env.obs_dim))).view(K + 1, n)
         carry = torch.zeros(n, device=dev)
         term, end = (done & 1) != 0, done != 0
         for k in range(K - 1, -1, -1):
@@ -238,7 +259,7 @@ def bench_critic(env_id, n, K, H, HV, seconds, repeats, ACT="tanh"):
     bad = int((env.status() & 3).ne(0).sum())
     fused_flag = env.launch_info()["rollout_fused"]
     env.close()
-    return {"env": env_id, "envs": n, "steps_per_window": K, "hidden": H, "critic_hidden": HV, "activation": ACT, "sample": True, "fused": fused_flag, "flagged_envs": bad,
+    return {"env": env_id, "envs": n, "steps_per_window": K, "hidden": H, "critic_hidden": HV, "activation": ACT, "obs_norm": bool(obs_norm), "sample": True, "fused": fused_flag, "flagged_envs": bad,
             **{name + "_env_steps_per_s": v for name, v in res.items()}}
 
 
@@ -249,7 +270,7 @@ def main_critic(args):
           f"window, {args.envs} envs, auto-reset, >= {args.seconds} s per leg, {args.repeats} alternating repeats; M env-steps/s, median (max - min)")
     print("%-18s %5s %26s %26s %26s" % ("env", "fused", "sample+step, torch V, GAE", "one call, critic + gae", "one call, no critic"))
     for env_id in args.ids.split(","):
-        r = bench_critic(env_id, args.envs, args.steps, args.policy, args.critic, args.seconds, args.repeats, args.activation)
+        r = bench_critic(env_id, args.envs, args.steps, args.policy, args.critic, args.seconds, args.repeats, args.activation, args.obs_norm)
         out.append(r)
         cell = lambda v: "%10.3f (%6.3f)" % (med(v) / 1e6, (max(v) - min(v)) / 1e6)
         print("%-18s %5d %26s %26s %26s" % (env_id, r["fused"], cell(r["torch_critic_gae_env_steps_per_s"]), cell(r["rollout_actor_critic_gae_env_steps_per_s"]),
@@ -267,7 +288,7 @@ def main_sample(args):
           f">= {args.seconds} s per leg, {args.repeats} alternating repeats; M env-steps/s, median (max - min)")
     print("%-18s %5s %24s %24s %24s" % ("env", "fused", "policy_sample + step", "rollout_policy_sample", "rollout_policy (det.)"))
     for env_id in args.ids.split(","):
-        r = bench_sample(env_id, args.envs, args.steps, args.policy, args.seconds, args.repeats, args.activation)
+        r = bench_sample(env_id, args.envs, args.steps, args.policy, args.seconds, args.repeats, args.activation, args.obs_norm)
         out.append(r)
         cell = lambda v: "%10.3f (%6.3f)" % (med(v) / 1e6, (max(v) - min(v)) / 1e6)
         print("%-18s %5d %24s %24s %24s" % (env_id, r["fused"], cell(r["sample_step_env_steps_per_s"]), cell(r["rollout_policy_sample_env_steps_per_s"]),
@@ -285,7 +306,7 @@ def main_policy(args):
           f"{args.repeats} alternating repeats; M env-steps/s, median (max - min)")
     print("%-18s %5s %24s %24s %24s" % ("env", "fused", "torch policy + step", "policy_act + step", "rollout_policy"))
     for env_id in args.ids.split(","):
-        r = bench_policy(env_id, args.envs, args.steps, args.policy, args.seconds, args.repeats, args.activation)
+        r = bench_policy(env_id, args.envs, args.steps, args.policy, args.seconds, args.repeats, args.activation, args.obs_norm)
         out.append(r)
         cell = lambda v: "%10.3f (%6.3f)" % (med(v) / 1e6, (max(v) - min(v)) / 1e6)
         print("%-18s %5d %24s %24s %24s" % (env_id, r["fused"], cell(r["torch_step_env_steps_per_s"]), cell(r["act_step_env_steps_per_s"]),
@@ -308,12 +329,17 @@ def main():
     ap.add_argument("--sample", action="store_true", help="with --policy: Gaussian policies, a sampled action every step")
     ap.add_argument("--critic", type=hidden_arg, default=None, metavar="HV", help="with --policy H --sample: a critic with HV hidden units (0 = affine; or HV1,HV2) and GAE")
     ap.add_argument("--activation", choices=("tanh", "relu"), default="tanh", help="with --policy: the hidden units of policy and critic")
+    ap.add_argument("--obs-norm", action="store_true", help="with --policy: bind an observation normaliser (env.bind_obs_norm) in every leg")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "rollout_bench.py measures on the GPU only"
     if args.sample and args.policy is None:
         ap.error("--sample goes with --policy H")
     if args.critic is not None and not args.sample:
         ap.error("--critic goes with --policy H --sample")
+    if args.obs_norm and args.policy is None:
+        ap.error("--obs-norm goes with --policy H")
+    if args.obs_norm:
+        print("observation normaliser bound (clip 5): every network below reads normalised rows")
     if args.critic is not None:
         return main_critic(args)
     if args.policy is not None:
