@@ -550,6 +550,69 @@ int32_t mz_rollout_net(mz_handle* h, int32_t n_steps, const mz_net* actor, int32
                        uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev, float* obs_seq_dev, float* actions_seq_dev,
                        float* logp_seq_dev, void* stream);
 
+/* Off-policy collection (TD3 / DDPG / SAC-style replay): every step's transition (s_k, a_k, r_k, s'_k, d_k) from one call, and
+ * exploration noise on the action.  Additive entries: MZ_ABI_VERSION does not change for them; both structs carry their own size.
+ *
+ * next_obs_seq_dev [n_steps, N, obs_dim] fp32 (nullable): the row step k produced, BEFORE any auto-reset — raw, never normalised:
+ *     after mz_step k:  next_obs_seq[k][i] = (auto_reset && done[k][i]) ? final_obs[i] : obs_dev[i]
+ * Where done[k][i] == 0, and everywhere without auto-reset, it holds the bits of obs_seq[k][i]; where the env finished under
+ * auto-reset it is that step's terminal row (the view entries of a top-down-view task included), which obs_seq never holds and of
+ * which the bound final_obs buffer keeps only the env's latest.  s_k is the row the policy acted on: the entry observation for
+ * k = 0, obs_seq[k - 1] afterwards.  Handles with "rollout_fused" = 1 store the row from inside the fused kernels, where it is on
+ * chip; every other handle launches one select kernel per step (a plain copy without auto-reset).  With auto-reset on and no
+ * final_obs buffer bound the request is MZ_ERR_ARG on every handle — the rule of next_value_seq_dev.
+ *
+ * mz_noise: how a sampled action is formed from the actor's pre-squash output m_u, s = expf(log_std[u]) and eps_u (above):
+ *   MZ_NOISE_PRE_SQUASH  z = m + s * eps;  a = squash ? A * tanhf(z) : z                     (mz_policy_sample: the noise is squashed)
+ *   MZ_NOISE_ACTION      p = s * eps;  b = squash ? A * tanhf(m) : m;  z = b + p;
+ *                        a = squash ? (z < -A ? -A : (z > A ? A : z)) : z                    (the tanh belongs to the deterministic actor
+ *                        a learner trains, the noise goes on the action, the result is clipped to the action range: TD3 / DDPG)
+ * A = (float)action_scale; fp32, every operation rounded separately, selects (a NaN passes).  eps, the key schedule (step k draws
+ * with step + k) and logp are the same in both modes — logp is the density of the unclipped z around b, bit-equal to the other
+ * mode's for the same seed and step — and with squash == 0 the two modes return the same bits.
+ *
+ * mz_net_sample: mz_net_act with sample == 1 and the noise of `noise` (required); logp_dev nullable.
+ *
+ * mz_rollout_ex: the open-loop and the closed-loop rollouts behind one struct.  Exactly one of io->actions_dev (then it is
+ * mz_rollout with action_step_stride) and io->actor (then it is mz_rollout_net: noise NULL means sample == 0, critic nullable,
+ * value_seq_dev / next_value_seq_dev ignored without a critic) is non-NULL; the remaining fields are the arrays of those two
+ * entries and next_obs_seq_dev.  With next_obs_seq_dev == NULL and mode MZ_NOISE_PRE_SQUASH the call runs the launches of
+ * mz_rollout / mz_rollout_net and returns their bits; next_obs_seq_dev and the mode change nothing else the call returns.
+ * MZ_ERR_ARG, with a message that names the argument: a NULL io; a wrong struct_size in either struct; both action sources or
+ * neither; noise or critic without an actor; noise->mode outside {MZ_NOISE_PRE_SQUASH, MZ_NOISE_ACTION}; next_obs_seq_dev under
+ * auto-reset without a bound final_obs buffer; and everything mz_rollout / mz_rollout_net refuse.  A refused call leaves the
+ * handle as it was. */
+#define MZ_NOISE_PRE_SQUASH 0
+#define MZ_NOISE_ACTION 1
+typedef struct mz_noise {
+  uint32_t struct_size;      /* sizeof(mz_noise); anything else: MZ_ERR_ARG */
+  int32_t mode;              /* MZ_NOISE_* */
+  uint64_t seed, step;       /* noise_seed; noise_step of the first step */
+} mz_noise;
+typedef struct mz_rollout_io {
+  uint32_t struct_size;      /* sizeof(mz_rollout_io); anything else: MZ_ERR_ARG */
+  int32_t n_steps;           /* 1 .. 65536 */
+  const float* actions_dev;  /* open loop: step k reads its [N, nu] actions at actions_dev + k * action_step_stride ... */
+  int64_t action_step_stride;
+  const mz_net* actor;       /* ... or closed loop: a_k = actor(obs) */
+  const mz_noise* noise;     /* NULL: deterministic */
+  const mz_net* critic;      /* nullable */
+  float* obs_dev;            /* [N, obs_dim]; IN/OUT with an actor */
+  float* reward_dev;         /* [n_steps, N] */
+  uint8_t* done_dev;         /* [n_steps, N] */
+  int32_t* goal_idx_dev;     /* [n_steps, N]           (nullable) */
+  float* info_dev;           /* [n_steps, N, 4]        (nullable) */
+  float* obs_seq_dev;        /* [n_steps, N, obs_dim]  (nullable) */
+  float* actions_seq_dev;    /* [n_steps, N, nu]       (nullable; closed loop) */
+  float* logp_seq_dev;       /* [n_steps, N]           (nullable; with noise) */
+  float* value_seq_dev;      /* [n_steps, N]           (nullable; with a critic) */
+  float* next_value_seq_dev; /* [n_steps, N]           (nullable; with a critic) */
+  float* next_obs_seq_dev;   /* [n_steps, N, obs_dim]  (nullable) */
+} mz_rollout_io;
+int32_t mz_net_sample(mz_handle* h, const mz_net* actor, const mz_noise* noise, const float* obs_dev, float* actions_dev, float* logp_dev,
+                      void* stream);
+int32_t mz_rollout_ex(mz_handle* h, const mz_rollout_io* io, void* stream);
+
 /* Normalised observations for the device-side networks (the observation half of VecNormalize; ARS-V2's state normalisation), and the
  * forward return scan that reward scaling and episode logging need.  Additive entries: MZ_ABI_VERSION does not change for them.
  *

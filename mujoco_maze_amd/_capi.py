@@ -26,6 +26,7 @@ SYMBOLS = [
     "mz_value", "mz_rollout_actor_critic", "mz_gae",
     "mz_net_act", "mz_net_value", "mz_rollout_net",
     "mz_bind_obs_norm", "mz_return_scan",
+    "mz_net_sample", "mz_rollout_ex",
 ]
 
 
@@ -49,6 +50,53 @@ def make_net(params_ptr, env_stride: int, widths, activation: int, squash: bool 
     w = tuple(int(x) for x in widths)
     return MzNet(C.sizeof(MzNet), len(w), (C.c_int32 * 2)(*(w + (0, 0))[:2]), int(activation), 1 if squash else 0, float(action_scale), params_ptr,
                  int(env_stride))
+
+
+NOISE_PRE_SQUASH, NOISE_ACTION = 0, 1  # MZ_NOISE_* (include/mazestep.h)
+NOISE_MODES = {"pre_squash": NOISE_PRE_SQUASH, "action": NOISE_ACTION}
+
+
+def noise_mode(noise: str) -> int:
+    """MZ_NOISE_* of the `noise=` argument of policy_sample / rollout_policy_sample / policy.sample_reference."""
+    try:
+        return NOISE_MODES[noise]
+    except (KeyError, TypeError):
+        raise ValueError(f"noise must be one of {sorted(NOISE_MODES)}, got {noise!r}") from None
+
+
+class MzNoise(C.Structure):
+    """`mz_noise` of include/mazestep.h: the noise of one mz_net_sample / mz_rollout_ex call."""
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("seed", C.c_uint64), ("step", C.c_uint64)]
+
+
+class MzRolloutIo(C.Structure):
+    """`mz_rollout_io` of include/mazestep.h: the arguments of one mz_rollout_ex call."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_steps", C.c_int32), ("actions_dev", C.c_void_p), ("action_step_stride", C.c_int64),
+                ("actor", C.POINTER(MzNet)), ("noise", C.POINTER(MzNoise)), ("critic", C.POINTER(MzNet)),
+                ("obs_dev", C.c_void_p), ("reward_dev", C.c_void_p), ("done_dev", C.c_void_p), ("goal_idx_dev", C.c_void_p),
+                ("info_dev", C.c_void_p), ("obs_seq_dev", C.c_void_p), ("actions_seq_dev", C.c_void_p), ("logp_seq_dev", C.c_void_p),
+                ("value_seq_dev", C.c_void_p), ("next_value_seq_dev", C.c_void_p), ("next_obs_seq_dev", C.c_void_p)]
+
+
+def make_noise(mode: int, seed: int, step: int) -> MzNoise:
+    """An MzNoise with struct_size set; seed and step wrap to uint64."""
+    return MzNoise(C.sizeof(MzNoise), int(mode), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF)
+
+
+def make_rollout_io(n_steps: int, **fields) -> MzRolloutIo:
+    """An MzRolloutIo with struct_size set; fields by name (pointers: ints or None; actor / noise / critic: the structs, kept alive by
+    the returned object)."""
+    io = MzRolloutIo(struct_size=C.sizeof(MzRolloutIo), n_steps=int(n_steps))
+    keep = []
+    for name, value in fields.items():
+        if name in ("actor", "noise", "critic"):
+            if value is not None:
+                keep.append(value)
+                setattr(io, name, C.pointer(value))
+        else:
+            setattr(io, name, value.value if isinstance(value, C.c_void_p) else value)
+    io._keep = keep
+    return io
 
 
 _lib = None
@@ -123,6 +171,10 @@ def load():
     lib.mz_net_value.argtypes = [vp, C.POINTER(MzNet), vp, vp, vp]
     lib.mz_rollout_net.restype = i32
     lib.mz_rollout_net.argtypes = [vp, i32, C.POINTER(MzNet), i32, u64, u64, C.POINTER(MzNet), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.mz_net_sample.restype = i32
+    lib.mz_net_sample.argtypes = [vp, C.POINTER(MzNet), C.POINTER(MzNoise), vp, vp, vp, vp]
+    lib.mz_rollout_ex.restype = i32
+    lib.mz_rollout_ex.argtypes = [vp, C.POINTER(MzRolloutIo), vp]
     lib.mz_bind_obs_norm.restype = i32
     lib.mz_bind_obs_norm.argtypes = [vp, vp, vp, C.c_double, vp]
     lib.mz_return_scan.restype = i32

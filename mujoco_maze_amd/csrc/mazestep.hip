@@ -33,6 +33,16 @@ __global__ void pack_record_kernel(int n, int obs_dim, const float* __restrict__
   record[idx] = i < obs_dim ? obs[(size_t)env * obs_dim + i] : (i == obs_dim ? reward[env] : (float)done[env]);
 }
 
+// next_obs_seq row of one step where the handle steps launch by launch (mz_rollout_ex: the Ant, the general engine, top-down-view
+// tasks): out[i][j] = done[i] ? final_obs[i][j] : obs[i][j], one thread per element — the row step k produced before any auto-reset,
+// its view entries included (mzk_view_fill has completed both rows).  Runs under auto-reset only; without it the row is a copy.
+__global__ __launch_bounds__(256) void next_obs_kernel(int n, int obs_dim, const float* __restrict__ obs, const float* __restrict__ final_obs,
+                                                       const uint8_t* __restrict__ done, float* __restrict__ out) {
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (size_t)n * obs_dim) return;
+  out[idx] = done[idx / obs_dim] ? final_obs[idx] : obs[idx];
+}
+
 // actions[r] = policy(obs[r]) for n rows (mz_policy_act; mz_rollout_policy where it steps launch by launch): the policy of mz_policy.h,
 // one group of MZ_POLICY_LANES adjacent lanes per row — lanes l, l + 16, .. own hidden units, lanes 0 .. nu - 1 the outputs.  Engine-
 // independent.  params: one policy (pstride = 0) or row r's own at params + r * pstride.  Surplus groups shadow the last row (no stores).
@@ -51,18 +61,18 @@ __global__ __launch_bounds__(256) void policy_act_kernel(int n, int obs_dim, int
 
 // policy_act_kernel for a stochastic policy (mz_policy_sample; mz_rollout_policy_sample where it steps launch by launch): the same
 // groups, lanes 0 .. nu - 1 own the outputs and their eps, lane 0 the row's log-prob (logp nullable).  key: mzp_noise_key of the
-// draw; row r is global env slot env0 + r.
+// draw; row r is global env slot env0 + r; mode: MZ_NOISE_* (mz_net_sample; every older entry passes MZ_NOISE_PRE_SQUASH).
 __global__ __launch_bounds__(256) void policy_sample_kernel(int n, int obs_dim, int nu, int hidden, int squash, float action_scale,
                                                             const float* __restrict__ params, long pstride, uint64_t key, uint64_t env0,
                                                             const float* __restrict__ obs, float* __restrict__ actions,
-                                                            float* __restrict__ logp) {
+                                                            float* __restrict__ logp, int mode) {
   __shared__ float hid[256 / MZ_POLICY_LANES][MZ_POLICY_MAX_HIDDEN];
   const int l = (int)threadIdx.x % MZ_POLICY_LANES, grp = (int)threadIdx.x / MZ_POLICY_LANES;
   size_t row = (size_t)blockIdx.x * (256 / MZ_POLICY_LANES) + grp;
   const bool live = row < (size_t)n;
   if (!live) row = (size_t)n - 1;
   mzp_group_sample(l, MZ_POLICY_LANES, params + row * pstride, obs_dim, nu, hidden, squash, action_scale, key, env0 + row, obs + row * obs_dim,
-                   hid[grp], actions + row * nu, live, live && logp ? logp + row : nullptr);
+                   hid[grp], actions + row * nu, live, live && logp ? logp + row : nullptr, mode);
 }
 
 // values[r] = V(obs[r]) for n rows (mz_value; mz_rollout_actor_critic where it steps launch by launch): the critic of mz_policy.h on
@@ -87,12 +97,12 @@ __global__ __launch_bounds__(256) void value_kernel(int n, int obs_dim, int hidd
 // NRM (a normaliser bound with mz_bind_obs_norm; every entry, the legacy ones included, then runs these two kernels): the group first
 // stages the normalised row of mz_policy.h in a third LDS row — lanes l, l + 16, .. own its elements —, hands it over and evaluates
 // the network on it.  obs_dim <= MZ_MAX_OBS + MZ_VIEW_DIM on every handle (mz_create; mz_bind_obs_norm checks it again).  NRM == false
-// compiles the source as it was and never reads `nm`.
+// compiles the source as it was and never reads `nm`.  mode: MZ_NOISE_* of a sampled action.
 template <bool NRM = false>
 __global__ __launch_bounds__(256) void net_act_kernel(int n, int obs_dim, int nu, mzp_shape s, int squash, float action_scale,
                                                       const float* __restrict__ params, long pstride, int sample, uint64_t key, uint64_t env0,
                                                       const float* __restrict__ obs, float* __restrict__ actions, float* __restrict__ logp,
-                                                      mzp_norm nm) {
+                                                      mzp_norm nm, int mode) {
   __shared__ float hid[256 / MZ_POLICY_LANES][MZ_NET_MAX_HIDDEN_LAYERS][MZ_POLICY_MAX_HIDDEN];
   const int l = (int)threadIdx.x % MZ_POLICY_LANES, grp = (int)threadIdx.x / MZ_POLICY_LANES;
   size_t row = (size_t)blockIdx.x * (256 / MZ_POLICY_LANES) + grp;
@@ -103,10 +113,10 @@ __global__ __launch_bounds__(256) void net_act_kernel(int n, int obs_dim, int nu
     mzp_group_norm(l, MZ_POLICY_LANES, nm, obs_dim, obs + row * obs_dim, xn[grp]);
     mzp_wave_sync();
     mzp_group_net_act(l, MZ_POLICY_LANES, params + row * pstride, obs_dim, nu, s, squash, action_scale, sample != 0, key, env0 + row, xn[grp],
-                      hid[grp][0], hid[grp][1], actions + row * nu, live, live && logp ? logp + row : nullptr);
+                      hid[grp][0], hid[grp][1], actions + row * nu, live, live && logp ? logp + row : nullptr, mode);
   } else {
     mzp_group_net_act(l, MZ_POLICY_LANES, params + row * pstride, obs_dim, nu, s, squash, action_scale, sample != 0, key, env0 + row,
-                      obs + row * obs_dim, hid[grp][0], hid[grp][1], actions + row * nu, live, live && logp ? logp + row : nullptr);
+                      obs + row * obs_dim, hid[grp][0], hid[grp][1], actions + row * nu, live, live && logp ? logp + row : nullptr, mode);
   }
 }
 
@@ -586,11 +596,22 @@ int32_t mz_step(mz_handle* h, const float* actions_dev, float* obs_dev, float* r
   return MZ_OK;
 }
 
+// row k of next_obs_seq_dev on a handle that steps launch by launch: behind the step's launches, before anything overwrites obs_dev or
+// the final_obs row (the caller has checked that final_obs is bound under auto-reset)
+static hipError_t next_obs_row(mz_handle* h, hipStream_t st, const float* obs_dev, const uint8_t* done_dev, float* out) {
+  const size_t tot = (size_t)h->n * h->model.obs_dim;
+  if (!h->auto_reset) return hipMemcpyAsync(out, obs_dev, tot * sizeof(float), hipMemcpyDeviceToDevice, st);
+  hipLaunchKernelGGL(next_obs_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, h->n, h->model.obs_dim, obs_dev, h->final_obs, done_dev, out);
+  return hipGetLastError();
+}
+
 // n_steps successive mz_step calls in one (include/mazestep.h).  Fused handles (mzk_planar_rollout_fused) advance up to
 // MZ_ROLLOUT_CHUNK steps per launch on a state that stays on chip; every other handle runs the step's own launches n_steps times
 // with the output pointers advanced, which is sequential stepping by construction.
-int32_t mz_rollout(mz_handle* h, int32_t n_steps, const float* actions_dev, int64_t action_step_stride, float* obs_dev, float* reward_dev,
-                   uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev, float* obs_seq_dev, void* stream) {
+// next_obs_seq_dev (mz_rollout_ex; NULL from mz_rollout): the row every step produced before any auto-reset — from inside the fused
+// kernels, else one next_obs_row per step.
+static int32_t rollout_open(mz_handle* h, int32_t n_steps, const float* actions_dev, int64_t action_step_stride, float* obs_dev, float* reward_dev,
+                            uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev, float* obs_seq_dev, float* next_obs_seq_dev, void* stream) {
   if (!h || !actions_dev || !obs_dev || !reward_dev || !done_dev) return h ? set_err(h, MZ_ERR_ARG, "mz_rollout: null array", hipSuccess) : MZ_ERR_ARG;
   if (n_steps < 1 || n_steps > 65536) return set_err(h, MZ_ERR_ARG, "mz_rollout: n_steps must be 1 .. 65536", hipSuccess);
   const size_t n = (size_t)h->n, od = (size_t)h->model.obs_dim;
@@ -599,7 +620,8 @@ int32_t mz_rollout(mz_handle* h, int32_t n_steps, const float* actions_dev, int6
   DeviceScope scope(h->device);
   hipStream_t st = (hipStream_t)stream;
   if (mzk_planar_rollout_fused(h)) {
-    HIPCHK(h, mzk_planar_rollout(h, st, n_steps, actions_dev, (long)action_step_stride, obs_dev, reward_dev, done_dev, goal_idx_dev, info_dev, obs_seq_dev));
+    HIPCHK(h, mzk_planar_rollout(h, st, n_steps, actions_dev, (long)action_step_stride, obs_dev, reward_dev, done_dev, goal_idx_dev, info_dev, obs_seq_dev,
+                                 next_obs_seq_dev));
     if (h->record) {  // the last step's row
       const size_t tot = n * (od + 2), last = (size_t)(n_steps - 1) * n;
       hipLaunchKernelGGL(pack_record_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, h->n, h->model.obs_dim, obs_dev, reward_dev + last, done_dev + last, h->record);
@@ -610,11 +632,17 @@ int32_t mz_rollout(mz_handle* h, int32_t n_steps, const float* actions_dev, int6
       const int rc = step_launches(h, st, actions_dev + k * (size_t)action_step_stride, obs_dev, reward_dev + k * n, done_dev + k * n,
                                    goal_idx_dev ? goal_idx_dev + k * n : NULL, info_dev ? info_dev + k * n * 4 : NULL);
       if (rc != MZ_OK) return rc;
+      if (next_obs_seq_dev) HIPCHK(h, next_obs_row(h, st, obs_dev, done_dev + k * n, next_obs_seq_dev + k * n * od));
       if (obs_seq_dev) HIPCHK(h, hipMemcpyAsync(obs_seq_dev + k * n * od, obs_dev, n * od * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
   }
   h->nsteps += n_steps;
   return MZ_OK;
+}
+
+int32_t mz_rollout(mz_handle* h, int32_t n_steps, const float* actions_dev, int64_t action_step_stride, float* obs_dev, float* reward_dev,
+                   uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev, float* obs_seq_dev, void* stream) {
+  return rollout_open(h, n_steps, actions_dev, action_step_stride, obs_dev, reward_dev, done_dev, goal_idx_dev, info_dev, obs_seq_dev, NULL, stream);
 }
 
 // A legacy network (int `hidden`, tanh) as the mz_net it is.  While a normaliser is bound (mz_bind_obs_norm) the legacy entries forward
@@ -624,7 +652,7 @@ static mz_net legacy_net(const float* params_dev, int64_t env_stride, int hidden
   return mz_net{(uint32_t)sizeof(mz_net), hidden > 0 ? 1 : 0, {hidden, 0}, MZ_ACT_TANH, squash, action_scale, params_dev, env_stride};
 }
 static void net_act_launch(mz_handle* h, hipStream_t st, const mz_net* actor, int sample, uint64_t noise_seed, uint64_t noise_step,
-                           const float* obs_dev, float* actions_dev, float* logp_dev);
+                           const float* obs_dev, float* actions_dev, float* logp_dev, int noise_mode = MZ_NOISE_PRE_SQUASH);
 static void net_value_launch(mz_handle* h, hipStream_t st, const mz_net* critic, const float* obs_dev, const float* final_obs_dev,
                              const uint8_t* done_dev, float* values_dev);
 
@@ -717,7 +745,8 @@ static void policy_sample_launch(mz_handle* h, hipStream_t st, const float* para
                                  uint64_t noise_seed, uint64_t noise_step, const float* obs_dev, float* actions_dev, float* logp_dev) {
   const int rows = 256 / MZ_POLICY_LANES;
   hipLaunchKernelGGL(policy_sample_kernel, dim3((unsigned)((h->n + rows - 1) / rows)), dim3(256), 0, st, h->n, h->model.obs_dim, h->model.nu, hidden,
-                     squash, scale, params_dev, (long)pstride, mzp_noise_key(noise_seed, noise_step), h->env0, obs_dev, actions_dev, logp_dev);
+                     squash, scale, params_dev, (long)pstride, mzp_noise_key(noise_seed, noise_step), h->env0, obs_dev, actions_dev, logp_dev,
+                     MZ_NOISE_PRE_SQUASH);
 }
 
 int32_t mz_policy_sample(mz_handle* h, const float* params_dev, int64_t param_env_stride, int32_t hidden, int32_t squash, double action_scale,
@@ -924,13 +953,13 @@ static mzp_shape net_shape(const mz_net* net) { return mzp_shape{net->n_hidden, 
 static bool net_shallow(const mz_net* net) { return net->n_hidden <= 1 && net->activation == MZ_ACT_TANH; }
 
 static void net_act_launch(mz_handle* h, hipStream_t st, const mz_net* actor, int sample, uint64_t noise_seed, uint64_t noise_step,
-                           const float* obs_dev, float* actions_dev, float* logp_dev) {
+                           const float* obs_dev, float* actions_dev, float* logp_dev, int noise_mode) {
   const int rows = 256 / MZ_POLICY_LANES;
   const mzp_norm nm{h->nrm_mean, h->nrm_inv_std, h->nrm_clip};
 #define MZ_NET_ACT(NRM)                                                                                                                         \
   hipLaunchKernelGGL(net_act_kernel<NRM>, dim3((unsigned)((h->n + rows - 1) / rows)), dim3(256), 0, st, h->n, h->model.obs_dim, h->model.nu,     \
                      net_shape(actor), actor->squash, (float)actor->action_scale, actor->params_dev, (long)actor->env_stride, sample,           \
-                     sample ? mzp_noise_key(noise_seed, noise_step) : 0, h->env0, obs_dev, actions_dev, sample ? logp_dev : NULL, nm)
+                     sample ? mzp_noise_key(noise_seed, noise_step) : 0, h->env0, obs_dev, actions_dev, sample ? logp_dev : NULL, nm, noise_mode)
   if (h->nrm_mean) MZ_NET_ACT(true); else MZ_NET_ACT(false);
 #undef MZ_NET_ACT
 }
@@ -974,10 +1003,11 @@ int32_t mz_net_value(mz_handle* h, const mz_net* critic, const float* obs_dev, f
 // rollout kernels — the one-layer instantiations where both are at most one tanh hidden layer, the DEEP ones otherwise, which
 // compute the same bits for such a network, and their NRM twins for every shape while a normaliser is bound —; every other handle runs the defining loop itself: net_value_kernel, net_act_kernel,
 // the step's own launches, net_value_kernel again with the final_obs row where the env finished under auto-reset.
-int32_t mz_rollout_net(mz_handle* h, int32_t n_steps, const mz_net* actor, int32_t sample, uint64_t noise_seed, uint64_t noise_step,
-                       const mz_net* critic, float* value_seq_dev, float* next_value_seq_dev, float* obs_dev, float* reward_dev,
-                       uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev, float* obs_seq_dev, float* actions_seq_dev,
-                       float* logp_seq_dev, void* stream) {
+// noise_mode / next_obs_seq_dev: MZ_NOISE_PRE_SQUASH / NULL from mz_rollout_net, the caller's from mz_rollout_ex, which has checked them.
+static int32_t rollout_net(mz_handle* h, int32_t n_steps, const mz_net* actor, int32_t sample, uint64_t noise_seed, uint64_t noise_step,
+                           const mz_net* critic, float* value_seq_dev, float* next_value_seq_dev, float* obs_dev, float* reward_dev,
+                           uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev, float* obs_seq_dev, float* actions_seq_dev,
+                           float* logp_seq_dev, int noise_mode, float* next_obs_seq_dev, void* stream) {
   if (!h) return MZ_ERR_ARG;
   if (sample != 0 && sample != 1) return set_err(h, MZ_ERR_ARG, "mz_rollout_net: sample must be 0 or 1", hipSuccess);
   if (!obs_dev || !reward_dev || !done_dev) return set_err(h, MZ_ERR_ARG, "mz_rollout_net: null array", hipSuccess);
@@ -1006,17 +1036,18 @@ int32_t mz_rollout_net(mz_handle* h, int32_t n_steps, const mz_net* actor, int32
       if (critic) {
         const mz_critic c{critic->params_dev, critic->env_stride, critic->hidden[0], 0, value_seq_dev, next_value_seq_dev};
         HIPCHK(h, mzk_planar_rollout_actor_critic(h, st, n_steps, p, ps, H, sq, scale, sample, noise_seed, noise_step, &c, obs_dev, reward_dev, done_dev,
-                                                  goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, logp_seq_dev));
+                                                  goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, logp_seq_dev, noise_mode, next_obs_seq_dev));
       } else if (sample) {
         HIPCHK(h, mzk_planar_rollout_policy_sample(h, st, n_steps, p, ps, H, sq, scale, noise_seed, noise_step, obs_dev, reward_dev, done_dev,
-                                                   goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, logp_seq_dev));
+                                                   goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, logp_seq_dev, noise_mode, next_obs_seq_dev));
       } else {
         HIPCHK(h, mzk_planar_rollout_policy(h, st, n_steps, p, ps, H, sq, scale, obs_dev, reward_dev, done_dev, goal_idx_dev, info_dev, obs_seq_dev,
-                                            actions_seq_dev));
+                                            actions_seq_dev, next_obs_seq_dev));
       }
     } else {
       HIPCHK(h, mzk_planar_rollout_net(h, st, n_steps, actor, sample, noise_seed, noise_step, critic, value_seq_dev, next_value_seq_dev, obs_dev,
-                                       reward_dev, done_dev, goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, logp_seq_dev));
+                                       reward_dev, done_dev, goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, logp_seq_dev, noise_mode,
+                                       next_obs_seq_dev));
     }
     if (h->record) {  // the last step's row
       const size_t tot = n * (od + 2), last = (size_t)(n_steps - 1) * n;
@@ -1028,7 +1059,7 @@ int32_t mz_rollout_net(mz_handle* h, int32_t n_steps, const mz_net* actor, int32
     for (size_t k = 0; k < (size_t)n_steps; k++) {
       float* a = actions_seq_dev ? actions_seq_dev + k * n * nu : h->policy_act;
       if (value_seq_dev) net_value_launch(h, st, critic, obs_dev, NULL, NULL, value_seq_dev + k * n);
-      net_act_launch(h, st, actor, sample, noise_seed, noise_step + k, obs_dev, a, logp_seq_dev ? logp_seq_dev + k * n : NULL);
+      net_act_launch(h, st, actor, sample, noise_seed, noise_step + k, obs_dev, a, logp_seq_dev ? logp_seq_dev + k * n : NULL, noise_mode);
       HIPCHK(h, hipGetLastError());
       rc = step_launches(h, st, a, obs_dev, reward_dev + k * n, done_dev + k * n, goal_idx_dev ? goal_idx_dev + k * n : NULL,
                          info_dev ? info_dev + k * n * 4 : NULL);
@@ -1038,11 +1069,75 @@ int32_t mz_rollout_net(mz_handle* h, int32_t n_steps, const mz_net* actor, int32
                          next_value_seq_dev + k * n);
         HIPCHK(h, hipGetLastError());
       }
+      if (next_obs_seq_dev) HIPCHK(h, next_obs_row(h, st, obs_dev, done_dev + k * n, next_obs_seq_dev + k * n * od));
       if (obs_seq_dev) HIPCHK(h, hipMemcpyAsync(obs_seq_dev + k * n * od, obs_dev, n * od * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
   }
   h->nsteps += n_steps;
   return MZ_OK;
+}
+
+int32_t mz_rollout_net(mz_handle* h, int32_t n_steps, const mz_net* actor, int32_t sample, uint64_t noise_seed, uint64_t noise_step,
+                       const mz_net* critic, float* value_seq_dev, float* next_value_seq_dev, float* obs_dev, float* reward_dev,
+                       uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev, float* obs_seq_dev, float* actions_seq_dev,
+                       float* logp_seq_dev, void* stream) {
+  return rollout_net(h, n_steps, actor, sample, noise_seed, noise_step, critic, value_seq_dev, next_value_seq_dev, obs_dev, reward_dev, done_dev,
+                     goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, logp_seq_dev, MZ_NOISE_PRE_SQUASH, NULL, stream);
+}
+
+// the checks mz_net_sample and mz_rollout_ex share; MZ_OK or MZ_ERR_ARG with the message set
+static int noise_args(mz_handle* h, const char* who, const mz_noise* noise) {
+  char msg[160];
+  const char* why = nullptr;
+  if (noise->struct_size != sizeof(mz_noise)) why = "noise->struct_size must be sizeof(mz_noise)";
+  else if (noise->mode != MZ_NOISE_PRE_SQUASH && noise->mode != MZ_NOISE_ACTION) why = "noise->mode must be MZ_NOISE_PRE_SQUASH (0) or MZ_NOISE_ACTION (1)";
+  if (!why) return MZ_OK;
+  snprintf(msg, sizeof(msg), "%s: %s", who, why);
+  return set_err(h, MZ_ERR_ARG, msg, hipSuccess);
+}
+
+// mz_net_act with sample == 1 and the noise of `noise`, mode included (include/mazestep.h)
+int32_t mz_net_sample(mz_handle* h, const mz_net* actor, const mz_noise* noise, const float* obs_dev, float* actions_dev, float* logp_dev,
+                      void* stream) {
+  if (!h) return MZ_ERR_ARG;
+  if (!noise) return set_err(h, MZ_ERR_ARG, "mz_net_sample: noise is NULL", hipSuccess);
+  if (!obs_dev || !actions_dev) return set_err(h, MZ_ERR_ARG, "mz_net_sample: null array", hipSuccess);
+  int rc = noise_args(h, "mz_net_sample", noise);
+  if (rc != MZ_OK) return rc;
+  rc = net_args(h, "mz_net_sample", "actor", actor, h->model.nu, true, false);
+  if (rc != MZ_OK) return rc;
+  DeviceScope scope(h->device);
+  net_act_launch(h, (hipStream_t)stream, actor, 1, noise->seed, noise->step, obs_dev, actions_dev, logp_dev, noise->mode);
+  HIPCHK(h, hipGetLastError());
+  return MZ_OK;
+}
+
+// mz_rollout / mz_rollout_net behind one struct, with the per-step pre-reset rows and the noise mode (include/mazestep.h).  The
+// checks here are those the struct adds; everything else is refused by the entry the call stands for, whose launches it runs.
+int32_t mz_rollout_ex(mz_handle* h, const mz_rollout_io* io, void* stream) {
+  if (!h) return MZ_ERR_ARG;
+  if (!io) return set_err(h, MZ_ERR_ARG, "mz_rollout_ex: io is NULL", hipSuccess);
+  if (io->struct_size != sizeof(mz_rollout_io)) return set_err(h, MZ_ERR_ARG, "mz_rollout_ex: io->struct_size must be sizeof(mz_rollout_io)", hipSuccess);
+  if (io->actions_dev && io->actor)
+    return set_err(h, MZ_ERR_ARG, "mz_rollout_ex: both io->actions_dev and io->actor are given: exactly one is the action source", hipSuccess);
+  if (!io->actions_dev && !io->actor)
+    return set_err(h, MZ_ERR_ARG, "mz_rollout_ex: neither io->actions_dev nor io->actor is given: exactly one is the action source", hipSuccess);
+  if (!io->actor && io->noise) return set_err(h, MZ_ERR_ARG, "mz_rollout_ex: io->noise without io->actor", hipSuccess);
+  if (!io->actor && io->critic) return set_err(h, MZ_ERR_ARG, "mz_rollout_ex: io->critic without io->actor", hipSuccess);
+  if (io->noise) {
+    const int rc = noise_args(h, "mz_rollout_ex", io->noise);
+    if (rc != MZ_OK) return rc;
+  }
+  if (io->next_obs_seq_dev && h->auto_reset && !h->final_obs)
+    return set_err(h, MZ_ERR_ARG, "mz_rollout_ex: next_obs_seq_dev under auto-reset needs a bound final_obs buffer (mz_bind_final_obs): "
+                                  "the contract is the same on every handle", hipSuccess);
+  if (!io->actor)
+    return rollout_open(h, io->n_steps, io->actions_dev, io->action_step_stride, io->obs_dev, io->reward_dev, io->done_dev, io->goal_idx_dev,
+                        io->info_dev, io->obs_seq_dev, io->next_obs_seq_dev, stream);
+  return rollout_net(h, io->n_steps, io->actor, io->noise ? 1 : 0, io->noise ? io->noise->seed : 0, io->noise ? io->noise->step : 0, io->critic,
+                     io->value_seq_dev, io->next_value_seq_dev, io->obs_dev, io->reward_dev, io->done_dev, io->goal_idx_dev, io->info_dev,
+                     io->obs_seq_dev, io->actions_seq_dev, io->logp_seq_dev, io->noise ? io->noise->mode : MZ_NOISE_PRE_SQUASH, io->next_obs_seq_dev,
+                     stream);
 }
 
 int32_t mz_gae(mz_handle* h, int32_t n_steps, const float* reward_dev, const uint8_t* done_dev, const float* value_dev,

@@ -93,30 +93,34 @@ hipError_t mzk_view_fill(mz_handle* h, hipStream_t st, float* obs, float* final_
 // MZ_ROLLOUT_CHUNK steps, which bounds a kernel's duration
 constexpr int MZ_ROLLOUT_CHUNK = 256;
 int mzk_planar_rollout_fused(const mz_handle* h);
+// the trailing arguments of the five launchers below serve mz_rollout_ex alone: next_obs_seq [nsteps][n][obs_dim] (nullable) gets the
+// raw row every step produced, before any auto-reset, from inside the kernels; noise_mode: MZ_NOISE_* of the sampled actions
 hipError_t mzk_planar_rollout(mz_handle* h, hipStream_t st, int nsteps, const float* actions, long astride, float* obs, float* reward,
-                              uint8_t* done, int* goal_idx, float* info, float* obs_seq);
+                              uint8_t* done, int* goal_idx, float* info, float* obs_seq, float* next_obs_seq = nullptr);
 // mz_rollout_policy on the same handles, with the same launch geometry and split: the policy of csrc/mz_policy.h (params: [npar], or
 // [n][npar] with pstride = npar) is evaluated between two steps on the observation row on chip; every launch writes obs at its last step
 hipError_t mzk_planar_rollout_policy(mz_handle* h, hipStream_t st, int nsteps, const float* params, long pstride, int hidden, int squash,
                                      float action_scale, float* obs, float* reward, uint8_t* done, int* goal_idx, float* info, float* obs_seq,
-                                     float* actions_seq);
+                                     float* actions_seq, float* next_obs_seq = nullptr);
 // mz_rollout_policy_sample on the same handles: the same launches, every step's actions drawn from the policy's Gaussian with the
 // noise of (noise_seed, noise_step + k); logp_seq [nsteps][n] nullable
 hipError_t mzk_planar_rollout_policy_sample(mz_handle* h, hipStream_t st, int nsteps, const float* params, long pstride, int hidden, int squash,
                                             float action_scale, uint64_t noise_seed, uint64_t noise_step, float* obs, float* reward, uint8_t* done,
-                                            int* goal_idx, float* info, float* obs_seq, float* actions_seq, float* logp_seq);
+                                            int* goal_idx, float* info, float* obs_seq, float* actions_seq, float* logp_seq,
+                                            int noise_mode = MZ_NOISE_PRE_SQUASH, float* next_obs_seq = nullptr);
 // mz_rollout_actor_critic with a critic on the same handles: the same launches (sample: the Gaussian policy), the critic of `critic`
 // (checked by the caller) evaluated on the on-chip row at every step and on the terminal row before an auto-reset overwrites it
 hipError_t mzk_planar_rollout_actor_critic(mz_handle* h, hipStream_t st, int nsteps, const float* params, long pstride, int hidden, int squash,
                                            float action_scale, int sample, uint64_t noise_seed, uint64_t noise_step, const mz_critic* critic,
                                            float* obs, float* reward, uint8_t* done, int* goal_idx, float* info, float* obs_seq, float* actions_seq,
-                                           float* logp_seq);
+                                           float* logp_seq, int noise_mode = MZ_NOISE_PRE_SQUASH, float* next_obs_seq = nullptr);
 // mz_rollout_net on the same handles where a network has two hidden layers or ReLU units: the same launches of the kernels' DEEP
 // instantiations, which evaluate networks of every shape mz_net describes (`actor`, `critic` — nullable — checked by the caller);
 // with a normaliser bound (h->nrm_mean) their NRM twins, for every shape
 hipError_t mzk_planar_rollout_net(mz_handle* h, hipStream_t st, int nsteps, const mz_net* actor, int sample, uint64_t noise_seed,
                                   uint64_t noise_step, const mz_net* critic, float* value_seq, float* next_value_seq, float* obs, float* reward,
-                                  uint8_t* done, int* goal_idx, float* info, float* obs_seq, float* actions_seq, float* logp_seq);
+                                  uint8_t* done, int* goal_idx, float* info, float* obs_seq, float* actions_seq, float* logp_seq,
+                                  int noise_mode = MZ_NOISE_PRE_SQUASH, float* next_obs_seq = nullptr);
 int mzk_planar_state_width(const mz_handle* h);  // coordinates per env of the state (NV)
 int mzk_planar_record_width(const mz_handle* h); // Point: floats per env-major record; 0 for the chains (SoA)
 

@@ -34,6 +34,11 @@
 //              acc = 0.0f;  for u = 0 .. nu - 1:  q = eps_u * eps_u;  h = -0.5f * q;  t = h - log_std[u];  t = t - 0.9189385f;
 //              acc = acc + t                                                                                           mzp_logp
 // NaN in log_std propagates to that unit's action and to the row's logp; log_std = -inf gives s = 0, z = m + (+-0) and logp = +inf.
+//   noise on the action (mode MZ_NOISE_ACTION; TD3 / DDPG exploration): the tanh belongs to the deterministic actor and the noise goes
+//            on its output — b = squash ? action_scale * tanhf(m_u) : m_u, z = b + p, every operation rounded separately, and with
+//            squash the action is z clipped to +-action_scale by two selects (z < -A ? -A : (z > A ? A : z): a NaN passes).  eps, the
+//            key schedule and logp are those of the default mode MZ_NOISE_PRE_SQUASH — logp is the density of the unclipped z around
+//            b, the same bits for the same seed and step —, and without squash the two modes are the same operations.
 // mujoco_maze_amd/policy.py mirrors all of it operation by operation (noise, sample_reference).
 //
 // Critics (mz_value / mz_rollout_actor_critic; value_kernel in mazestep.hip, the CRT instantiations of the fused kernels, the host
@@ -140,11 +145,17 @@ MZP_HD float mzp_eps(uint64_t key, uint64_t slot, int u) {
   return r * c;
 }
 
-// the action of output unit u from its pre-squash mean m
-MZP_HD float mzp_sample_unit(float m, float log_std, float eps, int squash, float action_scale) {
+// the action of output unit u from its pre-squash mean m; mode: MZ_NOISE_PRE_SQUASH (the noise goes through the squash) or
+// MZ_NOISE_ACTION (the noise goes on the squashed action, which is then clipped to +-action_scale: the head of this file)
+MZP_HD float mzp_sample_unit(float m, float log_std, float eps, int squash, float action_scale, int mode = MZ_NOISE_PRE_SQUASH) {
 #pragma clang fp contract(off) reassociate(off)
   const float s = expf(log_std);
   const float p = s * eps;
+  if (mode == MZ_NOISE_ACTION && squash) {
+    const float b = action_scale * tanhf(m);
+    const float z = b + p;
+    return z < -action_scale ? -action_scale : (z > action_scale ? action_scale : z);
+  }
   const float z = m + p;
   return squash ? action_scale * tanhf(z) : z;
 }
@@ -166,13 +177,13 @@ MZP_HD float mzp_logp(const float* log_std, int nu, uint64_t key, uint64_t slot)
 
 // THE stochastic policy: act[nu] ~ N(mean(x), diag(exp(log_std))^2) with the noise of (noise_seed, noise_step, slot); *logp (nullable)
 MZP_HD void mzp_sample_row(const float* par, int obs_dim, int nu, int H, int squash, float action_scale, uint64_t noise_seed,
-                           uint64_t noise_step, uint64_t slot, const float* x, float* act, float* logp) {
+                           uint64_t noise_step, uint64_t slot, const float* x, float* act, float* logp, int mode = MZ_NOISE_PRE_SQUASH) {
   float hid[MZ_POLICY_MAX_HIDDEN];
   const float* ls = par + mzp_param_count(obs_dim, nu, H);
   const uint64_t key = mzp_noise_key(noise_seed, noise_step);
   for (int j = 0; j < H; j++) hid[j] = mzp_hidden_unit(par, obs_dim, H, x, j);
   for (int u = 0; u < nu; u++)
-    act[u] = mzp_sample_unit(mzp_output_pre(par, obs_dim, nu, H, H > 0 ? hid : x, u), ls[u], mzp_eps(key, slot, u), squash, action_scale);
+    act[u] = mzp_sample_unit(mzp_output_pre(par, obs_dim, nu, H, H > 0 ? hid : x, u), ls[u], mzp_eps(key, slot, u), squash, action_scale, mode);
   if (logp) *logp = mzp_logp(ls, nu, key, slot);
 }
 
@@ -237,13 +248,13 @@ MZP_HD void mzp_net_policy_row(const float* par, int obs_dim, int nu, mzp_shape 
 }
 
 MZP_HD void mzp_net_sample_row(const float* par, int obs_dim, int nu, mzp_shape s, int squash, float action_scale, uint64_t noise_seed,
-                               uint64_t noise_step, uint64_t slot, const float* x, float* act, float* logp) {
+                               uint64_t noise_step, uint64_t slot, const float* x, float* act, float* logp, int mode = MZ_NOISE_PRE_SQUASH) {
   float hid1[MZ_POLICY_MAX_HIDDEN], hid2[MZ_POLICY_MAX_HIDDEN];
   const float* ls = par + mzp_net_param_count(obs_dim, nu, s);
   const uint64_t key = mzp_noise_key(noise_seed, noise_step);
   const float* in = mzp_net_hidden_row(par, obs_dim, s, x, hid1, hid2);
   for (int u = 0; u < nu; u++)
-    act[u] = mzp_sample_unit(mzp_net_output_pre(par, obs_dim, nu, s, in, u), ls[u], mzp_eps(key, slot, u), squash, action_scale);
+    act[u] = mzp_sample_unit(mzp_net_output_pre(par, obs_dim, nu, s, in, u), ls[u], mzp_eps(key, slot, u), squash, action_scale, mode);
   if (logp) *logp = mzp_logp(ls, nu, key, slot);
 }
 
@@ -293,9 +304,10 @@ __device__ __forceinline__ void mzp_group_eval(int l, int G, const float* par, i
 }
 
 // mzp_group_eval for a stochastic policy: lanes 0 .. nu - 1 own the outputs and their eps, the group's first lane the row's log-prob,
-// which it stores to *logp unless that is NULL.  key: mzp_noise_key of the step; slot: the row's global env slot.
+// which it stores to *logp unless that is NULL.  key: mzp_noise_key of the step; slot: the row's global env slot; mode: MZ_NOISE_*.
 __device__ __forceinline__ void mzp_group_sample(int l, int G, const float* par, int obs_dim, int nu, int H, int squash, float action_scale,
-                                                 uint64_t key, uint64_t slot, const float* x, float* hid, float* act, bool store, float* logp) {
+                                                 uint64_t key, uint64_t slot, const float* x, float* hid, float* act, bool store, float* logp,
+                                                 int mode) {
   if (H > 0) {
     for (int j = l; j < H; j += G) hid[j] = mzp_hidden_unit(par, obs_dim, H, x, j);
     mzp_wave_sync();
@@ -303,7 +315,7 @@ __device__ __forceinline__ void mzp_group_sample(int l, int G, const float* par,
   const float* ls = par + mzp_param_count(obs_dim, nu, H);
   for (int u = l; u < nu; u += G) {
     const float m = H > 0 ? mzp_output_pre(par, obs_dim, nu, H, hid, u) : mzp_output_pre(par, obs_dim, nu, H, x, u);
-    const float a = mzp_sample_unit(m, ls[u], mzp_eps(key, slot, u), squash, action_scale);
+    const float a = mzp_sample_unit(m, ls[u], mzp_eps(key, slot, u), squash, action_scale, mode);
     if (store) act[u] = a;
   }
   if (l == 0 && logp) *logp = mzp_logp(ls, nu, key, slot);
@@ -348,15 +360,15 @@ __device__ __forceinline__ float mzp_group_net_pre(const float* par, int obs_dim
   return mzp_net_output_pre(par, obs_dim, nout, s, x, u);
 }
 
-// mzp_group_eval (sample == false: key, slot and logp are not read) and mzp_group_sample (sample == true) for a network of shape s
+// mzp_group_eval (sample == false: key, slot, logp and mode are not read) and mzp_group_sample (sample == true) for a network of shape s
 __device__ __forceinline__ void mzp_group_net_act(int l, int G, const float* par, int obs_dim, int nu, mzp_shape s, int squash, float action_scale,
                                                   bool sample, uint64_t key, uint64_t slot, const float* x, float* hid, float* hid2, float* act,
-                                                  bool store, float* logp) {
+                                                  bool store, float* logp, int mode) {
   mzp_group_net_hidden(l, G, par, obs_dim, s, x, hid, hid2);
   const float* ls = par + mzp_net_param_count(obs_dim, nu, s);
   for (int u = l; u < nu; u += G) {
     const float m = mzp_group_net_pre(par, obs_dim, nu, s, x, hid, hid2, u);
-    const float a = sample ? mzp_sample_unit(m, ls[u], mzp_eps(key, slot, u), squash, action_scale) : (squash ? action_scale * tanhf(m) : m);
+    const float a = sample ? mzp_sample_unit(m, ls[u], mzp_eps(key, slot, u), squash, action_scale, mode) : (squash ? action_scale * tanhf(m) : m);
     if (store) act[u] = a;
   }
   if (sample && l == 0 && logp) *logp = mzp_logp(ls, nu, key, slot);

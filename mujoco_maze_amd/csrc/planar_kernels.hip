@@ -141,11 +141,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && 
 // counter carried as ints — so the outputs equal those of sequential stepping bit for bit.  Step k reads its actions at
 // actions + k * astride and writes row k of reward / done / goal_idx / info / obs_seq ([nsteps][n][..]; obs_seq nullable); `obs` gets
 // the row of step last_obs_step only (-1: none — a later launch of the same rollout writes it).  No top-down view: rows are NOBS floats apart.
-template <int NB, int NS, int G>
+// EXT (mz_rollout_ex with next_obs_seq_dev): every step also stores the row it produced, before any auto-reset, to row k of
+// next_obs_seq — from `o`, inside the `if (live)` block, before the reset rewrites it.  A template flag, not a nullable argument alone:
+// the extra pointer cost the existing instantiations registers or scratch (profiles/rollout/transitions.md).  EXT == false compiles
+// the source as it was and never reads next_obs_seq.
+template <int NB, int NS, int G, bool EXT = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && NS == 0 && G == 32) ? 2 : 1))) void planar_rollout_kernel(
     const PointDev* __restrict__ Pp, int n, PointState S, int nsteps, const float* __restrict__ actions, long astride, float* __restrict__ obs,
     int last_obs_step, float* __restrict__ reward, uint8_t* __restrict__ done, int* __restrict__ goal_idx, float* __restrict__ info,
-    float* __restrict__ obs_seq, int* __restrict__ status, int auto_reset, uint64_t seed, uint64_t env0, float* __restrict__ final_obs) {
+    float* __restrict__ obs_seq, int* __restrict__ status, int auto_reset, uint64_t seed, uint64_t env0, float* __restrict__ final_obs,
+    float* __restrict__ next_obs_seq) {
   using D = PlanarDims<NB, NS>;
   constexpr int NV = D::NV, NOBS = D::NOBS, EPW = 64 / G;
   constexpr bool BARE = NB == 0 && NS == 0;
@@ -181,6 +186,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && 
     float* oseq = obs_seq ? obs_seq + row * NOBS : nullptr;
     float* olast = step == last_obs_step ? obs + (size_t)env * NOBS : nullptr;
     if (live) {
+      if constexpr (EXT) {  // the row this step produced, before a reset rewrites o
+        if (next_obs_seq) for (int i = cx.l; i < NOBS; i += G) next_obs_seq[row * NOBS + i] = o[i];
+      }
       if (rst) {
         if (final_obs) for (int i = cx.l; i < NOBS; i += G) final_obs[(size_t)env * NOBS + i] = o[i];
       } else {
@@ -247,6 +255,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && 
 struct PolicyNoise {
   uint64_t seed, step;  // noise_seed; noise_step of the launch's first step
   float* logp_seq;      // [nsteps][n] rows of the launch (nullable)
+  int mode;             // MZ_NOISE_* (mz_policy.h mzp_sample_unit), read by the EXT instantiations alone
 };
 // CRT (mz_rollout_actor_critic with a critic): the group also evaluates the critic of mz_policy.h (mzp_group_value: the unit functions
 // value_kernel, mazestep.hip, runs) on the rows in `o` — at the launch's start on its first row; after every step on the row the step
@@ -276,12 +285,15 @@ struct PolicyShapes {
 // places after which a network reads the row — from the raw value it has just stored, so pnrm is rewritten exactly where `o` is and
 // the hand-offs that keep `o` from being rewritten under a reader keep pnrm.  Only the actor and the critic read pnrm; the task
 // predicate, every observation store and info read `o`.  NRM == false compiles the source as it was and never reads `nm`.
-template <int NB, int NS, int G, bool SMP = false, bool CRT = false, bool DEEP = false, bool NRM = false>
+// EXT (mz_rollout_ex with next_obs_seq_dev or MZ_NOISE_ACTION): as in planar_rollout_kernel, and the sampled actions are formed in
+// the mode ns.mode.  EXT == false compiles the source as it was: it never reads next_obs_seq, and samples in MZ_NOISE_PRE_SQUASH.
+template <int NB, int NS, int G, bool SMP = false, bool CRT = false, bool DEEP = false, bool NRM = false, bool EXT = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && NS == 0 && G == 32) ? 2 : 1))) void planar_policy_rollout_kernel(
     const PointDev* __restrict__ Pp, int n, PointState S, int nsteps, const float* __restrict__ params, long pstride, int hidden, int squash,
     float action_scale, float* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ done, int* __restrict__ goal_idx,
     float* __restrict__ info, float* __restrict__ obs_seq, float* __restrict__ actions_seq, int* __restrict__ status, int auto_reset,
-    uint64_t seed, uint64_t env0, float* __restrict__ final_obs, PolicyNoise ns, PolicyCritic cr, PolicyShapes sh, mzp_norm nm) {
+    uint64_t seed, uint64_t env0, float* __restrict__ final_obs, PolicyNoise ns, PolicyCritic cr, PolicyShapes sh, mzp_norm nm,
+    float* __restrict__ next_obs_seq) {
   static_assert(!NRM || DEEP, "the normalised row is staged in the DEEP instantiations only");
   using D = PlanarDims<NB, NS>;
   constexpr int NV = D::NV, NOBS = D::NOBS, EPW = 64 / G;
@@ -329,14 +341,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && 
     if constexpr (NRM)
       mzp_group_net_act(cx.l, G, par, NOBS, 2, sh.actor, squash, action_scale, SMP, SMP ? mzp_noise_key(ns.seed, ns.step + (uint64_t)step) : 0,
                         env0 + (uint64_t)env, pnrm[grp], phid[grp][0], phid[grp][DEEP ? 1 : 0], pact[grp], true,
-                        SMP && live && ns.logp_seq ? ns.logp_seq + row : nullptr);
+                        SMP && live && ns.logp_seq ? ns.logp_seq + row : nullptr, EXT ? ns.mode : MZ_NOISE_PRE_SQUASH);
     else if constexpr (DEEP)
       mzp_group_net_act(cx.l, G, par, NOBS, 2, sh.actor, squash, action_scale, SMP, SMP ? mzp_noise_key(ns.seed, ns.step + (uint64_t)step) : 0,
                         env0 + (uint64_t)env, o, phid[grp][0], phid[grp][DEEP ? 1 : 0], pact[grp], true,
-                        SMP && live && ns.logp_seq ? ns.logp_seq + row : nullptr);
+                        SMP && live && ns.logp_seq ? ns.logp_seq + row : nullptr, EXT ? ns.mode : MZ_NOISE_PRE_SQUASH);
     else if constexpr (SMP)
       mzp_group_sample(cx.l, G, par, NOBS, 2, hidden, squash, action_scale, mzp_noise_key(ns.seed, ns.step + (uint64_t)step), env0 + (uint64_t)env, o,
-                       phid[grp][0], pact[grp], true, live && ns.logp_seq ? ns.logp_seq + row : nullptr);
+                       phid[grp][0], pact[grp], true, live && ns.logp_seq ? ns.logp_seq + row : nullptr, EXT ? ns.mode : MZ_NOISE_PRE_SQUASH);
     else
       mzp_group_eval(cx.l, G, par, NOBS, 2, hidden, squash, action_scale, o, phid[grp][0], pact[grp], true);
     cx.sync();
@@ -355,6 +367,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && 
     float* oseq = obs_seq ? obs_seq + row * NOBS : nullptr;
     float* olast = step == nsteps - 1 ? obs + (size_t)env * NOBS : nullptr;
     if (live) {
+      if constexpr (EXT) {  // the raw row this step produced, before a reset rewrites o
+        if (next_obs_seq) for (int i = cx.l; i < NOBS; i += G) next_obs_seq[row * NOBS + i] = o[i];
+      }
       if (rst) {
         if (final_obs) for (int i = cx.l; i < NOBS; i += G) final_obs[(size_t)env * NOBS + i] = o[i];
       } else {
@@ -564,13 +579,14 @@ __global__ __launch_bounds__(256) void swimmer_step_kernel(const SwimmerDev* __r
 // `nsteps` successive swimmer_step_kernel launches in one (mz_rollout; arguments as planar_rollout_kernel): the fp32 state stays in
 // registers.  A separate launch hands every lane of a group the state its first lane stored, so after each step the group takes its
 // first lane's state (and the episode verdict that follows from it) before it goes on.
-template <int NL, int NB, int G>
+// EXT: as in planar_rollout_kernel, through swimmer_store_row (rows are NO floats apart).
+template <int NL, int NB, int G, bool EXT = false>
 __global__ __launch_bounds__(256) void swimmer_rollout_kernel(const SwimmerDev* __restrict__ Pp, int n, PointState S, int nsteps,
                                                                const float* __restrict__ actions, long astride, float* __restrict__ obs,
                                                                int last_obs_step, float* __restrict__ reward, uint8_t* __restrict__ done,
                                                                int* __restrict__ goal_idx, float* __restrict__ info, float* __restrict__ obs_seq,
                                                                int* __restrict__ status, int auto_reset, uint64_t seed, uint64_t env0,
-                                                               float* __restrict__ final_obs) {
+                                                               float* __restrict__ final_obs, float* __restrict__ next_obs_seq) {
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   int env = gid / G;
   const SwimmerCtx<G> cx{(int)(threadIdx.x % G)};
@@ -600,6 +616,9 @@ __global__ __launch_bounds__(256) void swimmer_rollout_kernel(const SwimmerDev* 
     float* oseq = obs_seq ? obs_seq + row * NO : nullptr;
     float* olast = step == last_obs_step ? obs + (size_t)env * NO : nullptr;
     if (live) {
+      if constexpr (EXT) {  // the row this step produced, before any reset
+        if (next_obs_seq) swimmer_store_row<NL, NB>(P, qf, o, NO, NO, next_obs_seq + row * NO);
+      }
       if (rst) {
         if (final_obs) swimmer_store_row<NL, NB>(P, qf, o, NO, NO, final_obs + (size_t)env * NO);
       } else {
@@ -647,14 +666,16 @@ __global__ __launch_bounds__(256) void swimmer_rollout_kernel(const SwimmerDev* 
 // NRM: as in planar_policy_rollout_kernel.  Here the raw row lives in registers and px is what the networks read and nothing else
 // reads, so px IS the staged row: wherever a lane puts raw elements there it puts mzp_norm_elem of them (px_elem), at the places px
 // was written before, under the hand-offs it had before.  Stores, the task predicate and info go on reading the registers.
-template <int NL, int NB, int G, bool SMP = false, bool CRT = false, bool DEEP = false, bool NRM = false>
+// EXT: as in planar_policy_rollout_kernel.
+template <int NL, int NB, int G, bool SMP = false, bool CRT = false, bool DEEP = false, bool NRM = false, bool EXT = false>
 __global__ __launch_bounds__(256) void swimmer_policy_rollout_kernel(const SwimmerDev* __restrict__ Pp, int n, PointState S, int nsteps,
                                                                       const float* __restrict__ params, long pstride, int hidden, int squash,
                                                                       float action_scale, float* __restrict__ obs, float* __restrict__ reward,
                                                                       uint8_t* __restrict__ done, int* __restrict__ goal_idx, float* __restrict__ info,
                                                                       float* __restrict__ obs_seq, float* __restrict__ actions_seq, int* __restrict__ status,
                                                                       int auto_reset, uint64_t seed, uint64_t env0, float* __restrict__ final_obs,
-                                                                      PolicyNoise ns, PolicyCritic cr, PolicyShapes sh, mzp_norm nm) {
+                                                                      PolicyNoise ns, PolicyCritic cr, PolicyShapes sh, mzp_norm nm,
+                                                                      float* __restrict__ next_obs_seq) {
   static_assert(!NRM || DEEP, "the normalised row is staged in the DEEP instantiations only");
   constexpr int NR = NL + 2, NV = NR + NB, NH = NL - 1, NOMAX = 2 * NV + 4, GPB = 256 / G;
   __shared__ float px[GPB][NOMAX];
@@ -699,10 +720,10 @@ __global__ __launch_bounds__(256) void swimmer_policy_rollout_kernel(const Swimm
     if constexpr (DEEP)
       mzp_group_net_act(cx.l, G, par, NO, NH, sh.actor, squash, action_scale, SMP, SMP ? mzp_noise_key(ns.seed, ns.step + (uint64_t)step) : 0,
                         env0 + (uint64_t)env, x, phid[grp][0], phid[grp][DEEP ? 1 : 0], pact[grp], true,
-                        SMP && live && ns.logp_seq ? ns.logp_seq + row : nullptr);
+                        SMP && live && ns.logp_seq ? ns.logp_seq + row : nullptr, EXT ? ns.mode : MZ_NOISE_PRE_SQUASH);
     else if constexpr (SMP)
       mzp_group_sample(cx.l, G, par, NO, NH, hidden, squash, action_scale, mzp_noise_key(ns.seed, ns.step + (uint64_t)step), env0 + (uint64_t)env, x,
-                       phid[grp][0], pact[grp], true, live && ns.logp_seq ? ns.logp_seq + row : nullptr);
+                       phid[grp][0], pact[grp], true, live && ns.logp_seq ? ns.logp_seq + row : nullptr, EXT ? ns.mode : MZ_NOISE_PRE_SQUASH);
     else
       mzp_group_eval(cx.l, G, par, NO, NH, hidden, squash, action_scale, x, phid[grp][0], pact[grp], true);
     mzp_wave_sync();
@@ -719,6 +740,9 @@ __global__ __launch_bounds__(256) void swimmer_policy_rollout_kernel(const Swimm
     float* oseq = obs_seq ? obs_seq + row * NO : nullptr;
     float* olast = step == nsteps - 1 ? obs + (size_t)env * NO : nullptr;
     if (live) {
+      if constexpr (EXT) {  // the raw row this step produced, before any reset
+        if (next_obs_seq) swimmer_store_row<NL, NB>(P, qf, o, NO, NO, next_obs_seq + row * NO);
+      }
       if (rst) {
         if (final_obs) swimmer_store_row<NL, NB>(P, qf, o, NO, NO, final_obs + (size_t)env * NO);
       } else {
@@ -932,7 +956,7 @@ int mzk_planar_rollout_fused(const mz_handle* h) {
 // steps k = 0 .. nsteps - 1 of a rollout in launches of at most MZ_ROLLOUT_CHUNK steps, each with the launch geometry of the step
 // kernel it stands for; arrays as in mz_rollout (include/mazestep.h)
 hipError_t mzk_planar_rollout(mz_handle* h, hipStream_t st, int nsteps, const float* actions_dev, long astride, float* obs_dev, float* reward_dev,
-                              uint8_t* done_dev, int* goal_idx_dev, float* info_dev, float* obs_seq_dev) {
+                              uint8_t* done_dev, int* goal_idx_dev, float* info_dev, float* obs_seq_dev, float* next_obs_seq_dev) {
   PointState S{h->state, h->pt_t, h->pt_ep, h->pt_rec};
   const size_t n = (size_t)h->n, od = (size_t)h->model.obs_dim;
   for (int k0 = 0; k0 < nsteps; k0 += MZ_ROLLOUT_CHUNK) {
@@ -944,10 +968,12 @@ hipError_t mzk_planar_rollout(mz_handle* h, hipStream_t st, int nsteps, const fl
     int* gi = goal_idx_dev ? goal_idx_dev + k0 * n : nullptr;
     float* inf = info_dev ? info_dev + k0 * n * 4 : nullptr;
     float* oseq = obs_seq_dev ? obs_seq_dev + k0 * n * od : nullptr;
+    float* nseq = next_obs_seq_dev ? next_obs_seq_dev + k0 * n * od : nullptr;  // this launch writes rows k0 .. k0 + ks - 1
     if (h->robot == MZ_ROBOT_SWIMMER) {
-#define MZ_SW_ROLL(NL, NB)                                                                                                          \
-  hipLaunchKernelGGL((swimmer_rollout_kernel<NL, NB, (NL <= 4 ? 4 : 8)>), dim3((unsigned)((n * (NL <= 4 ? 4 : 8) + sw_bd - 1) / sw_bd)), dim3(sw_bd), 0, st, \
-                     h->swimmer_dev, h->n, S, ks, act, astride, obs_dev, last, rew, dn, gi, inf, oseq, h->status, h->auto_reset, h->seed, h->env0, h->final_obs)
+#define MZ_SW_ROLL(NL, NB) do { if (nseq) MZ_SW_ROLL_(NL, NB, true); else MZ_SW_ROLL_(NL, NB, false); } while (0)
+#define MZ_SW_ROLL_(NL, NB, EXT)                                                                                                    \
+  hipLaunchKernelGGL((swimmer_rollout_kernel<NL, NB, (NL <= 4 ? 4 : 8), EXT>), dim3((unsigned)((n * (NL <= 4 ? 4 : 8) + sw_bd - 1) / sw_bd)), dim3(sw_bd), 0, st, \
+                     h->swimmer_dev, h->n, S, ks, act, astride, obs_dev, last, rew, dn, gi, inf, oseq, h->status, h->auto_reset, h->seed, h->env0, h->final_obs, nseq)
       const int bd = h->swimmer.nblock ? h->swimmer.nbdof : 0;
       const unsigned sw_bd = 64u * (unsigned)(h->wpb_set ? h->waves_per_block : 4);
       if (h->swimmer.nlink == 3) { if (bd == 3) MZ_SW_ROLL(3, 3); else if (bd == 2) MZ_SW_ROLL(3, 2); else MZ_SW_ROLL(3, 0); }
@@ -956,10 +982,12 @@ hipError_t mzk_planar_rollout(mz_handle* h, hipStream_t st, int nsteps, const fl
       else if (h->swimmer.nlink == 5) MZ_SW_ROLL(5, 0);
       else MZ_SW_ROLL(6, 0);
 #undef MZ_SW_ROLL
+#undef MZ_SW_ROLL_
     } else {
-#define MZ_PLANAR_ROLL(NB, NS, G)                                                                                                      \
-  hipLaunchKernelGGL((planar_rollout_kernel<NB, NS, G>), dim3((h->n + 64 / G - 1) / (64 / G)), dim3(64), 0, st, h->point_dev, h->n, S, ks, act, astride, \
-                     obs_dev, last, rew, dn, gi, inf, oseq, h->status, h->auto_reset, h->seed, h->env0, h->final_obs)
+#define MZ_PLANAR_ROLL(NB, NS, G) do { if (nseq) MZ_PLANAR_ROLL_(NB, NS, G, true); else MZ_PLANAR_ROLL_(NB, NS, G, false); } while (0)
+#define MZ_PLANAR_ROLL_(NB, NS, G, EXT)                                                                                                \
+  hipLaunchKernelGGL((planar_rollout_kernel<NB, NS, G, EXT>), dim3((h->n + 64 / G - 1) / (64 / G)), dim3(64), 0, st, h->point_dev, h->n, S, ks, act, astride, \
+                     obs_dev, last, rew, dn, gi, inf, oseq, h->status, h->auto_reset, h->seed, h->env0, h->final_obs, nseq)
       if (h->point.nball) MZ_PLANAR_ROLL(0, 1, 32);
       else switch (h->point.nblock) {
         case 0: {
@@ -974,6 +1002,7 @@ hipError_t mzk_planar_rollout(mz_handle* h, hipStream_t st, int nsteps, const fl
         default: MZ_PLANAR_ROLL(3, 0, 64); break;
       }
 #undef MZ_PLANAR_ROLL
+#undef MZ_PLANAR_ROLL_
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -987,15 +1016,18 @@ hipError_t mzk_planar_rollout(mz_handle* h, hipStream_t st, int nsteps, const fl
 // CRT (mz_rollout_actor_critic with a critic): `critic` holds the critic's parameters and the call's value_seq / next_value_seq.
 // DEEP (mz_rollout_net with a network of two hidden layers or ReLU units): `shapes` holds both networks' shapes.
 // NRM (DEEP with a normaliser bound): the kernels' NRM instantiations, with the handle's normaliser.
+// next_obs_seq_dev / noise.mode (mz_rollout_ex): see `ext` below.
 template <bool SMP, bool CRT = false, bool DEEP = false, bool NRM = false>
 static hipError_t planar_rollout_policy_launches(mz_handle* h, hipStream_t st, int nsteps, const float* params_dev, long pstride, int hidden,
                                                  int squash, float action_scale, float* obs_dev, float* reward_dev, uint8_t* done_dev,
                                                  int* goal_idx_dev, float* info_dev, float* obs_seq_dev, float* actions_seq_dev, PolicyNoise noise,
                                                  PolicyCritic critic = PolicyCritic{nullptr, 0, 0, nullptr, nullptr},
-                                                 PolicyShapes shapes = PolicyShapes{{0, 0, 0, 0}, {0, 0, 0, 0}}) {
+                                                 PolicyShapes shapes = PolicyShapes{{0, 0, 0, 0}, {0, 0, 0, 0}}, float* next_obs_seq_dev = nullptr) {
   PointState S{h->state, h->pt_t, h->pt_ep, h->pt_rec};
   const size_t n = (size_t)h->n, od = (size_t)h->model.obs_dim, nu = (size_t)h->model.nu;
   const mzp_norm nm{h->nrm_mean, h->nrm_inv_std, h->nrm_clip};
+  // what mz_rollout_ex adds runs the kernels' EXT instantiations; every other call launches what it always launched
+  const bool ext = next_obs_seq_dev || (SMP && noise.mode != MZ_NOISE_PRE_SQUASH);
   for (int k0 = 0; k0 < nsteps; k0 += MZ_ROLLOUT_CHUNK) {
     const int ks = nsteps - k0 < MZ_ROLLOUT_CHUNK ? nsteps - k0 : MZ_ROLLOUT_CHUNK;
     float* rew = reward_dev + k0 * n;
@@ -1004,14 +1036,16 @@ static hipError_t planar_rollout_policy_launches(mz_handle* h, hipStream_t st, i
     float* inf = info_dev ? info_dev + k0 * n * 4 : nullptr;
     float* oseq = obs_seq_dev ? obs_seq_dev + k0 * n * od : nullptr;
     float* aseq = actions_seq_dev ? actions_seq_dev + k0 * n * nu : nullptr;
-    const PolicyNoise ns{noise.seed, noise.step + (uint64_t)k0, noise.logp_seq ? noise.logp_seq + k0 * n : nullptr};
+    float* nseq = next_obs_seq_dev ? next_obs_seq_dev + k0 * n * od : nullptr;
+    const PolicyNoise ns{noise.seed, noise.step + (uint64_t)k0, noise.logp_seq ? noise.logp_seq + k0 * n : nullptr, noise.mode};
     const PolicyCritic cr{critic.params, critic.stride, critic.hidden, critic.value_seq ? critic.value_seq + k0 * n : nullptr,
                           critic.next_value_seq ? critic.next_value_seq + k0 * n : nullptr};
     if (h->robot == MZ_ROBOT_SWIMMER) {
-#define MZ_SW_ROLL(NL, NB)                                                                                                          \
-  hipLaunchKernelGGL((swimmer_policy_rollout_kernel<NL, NB, (NL <= 4 ? 4 : 8), SMP, CRT, DEEP, NRM>), dim3((unsigned)((n * (NL <= 4 ? 4 : 8) + sw_bd - 1) / sw_bd)), dim3(sw_bd), 0, st, \
+#define MZ_SW_ROLL(NL, NB) do { if (ext) MZ_SW_ROLL_(NL, NB, true); else MZ_SW_ROLL_(NL, NB, false); } while (0)
+#define MZ_SW_ROLL_(NL, NB, EXT)                                                                                                    \
+  hipLaunchKernelGGL((swimmer_policy_rollout_kernel<NL, NB, (NL <= 4 ? 4 : 8), SMP, CRT, DEEP, NRM, EXT>), dim3((unsigned)((n * (NL <= 4 ? 4 : 8) + sw_bd - 1) / sw_bd)), dim3(sw_bd), 0, st, \
                      h->swimmer_dev, h->n, S, ks, params_dev, pstride, hidden, squash, action_scale, obs_dev, rew, dn, gi, inf, oseq, aseq, h->status,         \
-                     h->auto_reset, h->seed, h->env0, h->final_obs, ns, cr, shapes, nm)
+                     h->auto_reset, h->seed, h->env0, h->final_obs, ns, cr, shapes, nm, nseq)
       const int bd = h->swimmer.nblock ? h->swimmer.nbdof : 0;
       const unsigned sw_bd = 64u * (unsigned)(h->wpb_set ? h->waves_per_block : 4);
       if (h->swimmer.nlink == 3) { if (bd == 3) MZ_SW_ROLL(3, 3); else if (bd == 2) MZ_SW_ROLL(3, 2); else MZ_SW_ROLL(3, 0); }
@@ -1020,10 +1054,12 @@ static hipError_t planar_rollout_policy_launches(mz_handle* h, hipStream_t st, i
       else if (h->swimmer.nlink == 5) MZ_SW_ROLL(5, 0);
       else MZ_SW_ROLL(6, 0);
 #undef MZ_SW_ROLL
+#undef MZ_SW_ROLL_
     } else {
-#define MZ_PLANAR_ROLL(NB, NS, G)                                                                                                      \
-  hipLaunchKernelGGL((planar_policy_rollout_kernel<NB, NS, G, SMP, CRT, DEEP, NRM>), dim3((h->n + 64 / G - 1) / (64 / G)), dim3(64), 0, st, h->point_dev, h->n, S, ks, params_dev, \
-                     pstride, hidden, squash, action_scale, obs_dev, rew, dn, gi, inf, oseq, aseq, h->status, h->auto_reset, h->seed, h->env0, h->final_obs, ns, cr, shapes, nm)
+#define MZ_PLANAR_ROLL(NB, NS, G) do { if (ext) MZ_PLANAR_ROLL_(NB, NS, G, true); else MZ_PLANAR_ROLL_(NB, NS, G, false); } while (0)
+#define MZ_PLANAR_ROLL_(NB, NS, G, EXT)                                                                                                \
+  hipLaunchKernelGGL((planar_policy_rollout_kernel<NB, NS, G, SMP, CRT, DEEP, NRM, EXT>), dim3((h->n + 64 / G - 1) / (64 / G)), dim3(64), 0, st, h->point_dev, h->n, S, ks, params_dev, \
+                     pstride, hidden, squash, action_scale, obs_dev, rew, dn, gi, inf, oseq, aseq, h->status, h->auto_reset, h->seed, h->env0, h->final_obs, ns, cr, shapes, nm, nseq)
       if (h->point.nball) MZ_PLANAR_ROLL(0, 1, 32);
       else switch (h->point.nblock) {
         case 0: {
@@ -1038,6 +1074,7 @@ static hipError_t planar_rollout_policy_launches(mz_handle* h, hipStream_t st, i
         default: MZ_PLANAR_ROLL(3, 0, 64); break;
       }
 #undef MZ_PLANAR_ROLL
+#undef MZ_PLANAR_ROLL_
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -1047,37 +1084,42 @@ static hipError_t planar_rollout_policy_launches(mz_handle* h, hipStream_t st, i
 
 hipError_t mzk_planar_rollout_policy(mz_handle* h, hipStream_t st, int nsteps, const float* params_dev, long pstride, int hidden, int squash,
                                      float action_scale, float* obs_dev, float* reward_dev, uint8_t* done_dev, int* goal_idx_dev, float* info_dev,
-                                     float* obs_seq_dev, float* actions_seq_dev) {
+                                     float* obs_seq_dev, float* actions_seq_dev, float* next_obs_seq_dev) {
   return planar_rollout_policy_launches<false>(h, st, nsteps, params_dev, pstride, hidden, squash, action_scale, obs_dev, reward_dev, done_dev,
-                                               goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, PolicyNoise{0, 0, nullptr});
+                                               goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, PolicyNoise{0, 0, nullptr, 0},
+                                               PolicyCritic{nullptr, 0, 0, nullptr, nullptr}, PolicyShapes{{0, 0, 0, 0}, {0, 0, 0, 0}}, next_obs_seq_dev);
 }
 
 hipError_t mzk_planar_rollout_policy_sample(mz_handle* h, hipStream_t st, int nsteps, const float* params_dev, long pstride, int hidden, int squash,
                                             float action_scale, uint64_t noise_seed, uint64_t noise_step, float* obs_dev, float* reward_dev,
                                             uint8_t* done_dev, int* goal_idx_dev, float* info_dev, float* obs_seq_dev, float* actions_seq_dev,
-                                            float* logp_seq_dev) {
+                                            float* logp_seq_dev, int noise_mode, float* next_obs_seq_dev) {
   return planar_rollout_policy_launches<true>(h, st, nsteps, params_dev, pstride, hidden, squash, action_scale, obs_dev, reward_dev, done_dev,
-                                              goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, PolicyNoise{noise_seed, noise_step, logp_seq_dev});
+                                              goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev,
+                                              PolicyNoise{noise_seed, noise_step, logp_seq_dev, noise_mode},
+                                              PolicyCritic{nullptr, 0, 0, nullptr, nullptr}, PolicyShapes{{0, 0, 0, 0}, {0, 0, 0, 0}}, next_obs_seq_dev);
 }
 
 hipError_t mzk_planar_rollout_actor_critic(mz_handle* h, hipStream_t st, int nsteps, const float* params_dev, long pstride, int hidden, int squash,
                                            float action_scale, int sample, uint64_t noise_seed, uint64_t noise_step, const mz_critic* critic,
                                            float* obs_dev, float* reward_dev, uint8_t* done_dev, int* goal_idx_dev, float* info_dev, float* obs_seq_dev,
-                                           float* actions_seq_dev, float* logp_seq_dev) {
+                                           float* actions_seq_dev, float* logp_seq_dev, int noise_mode, float* next_obs_seq_dev) {
   const PolicyCritic cr{critic->params_dev, (long)critic->env_stride, critic->hidden, critic->value_seq_dev, critic->next_value_seq_dev};
+  const PolicyShapes none{{0, 0, 0, 0}, {0, 0, 0, 0}};
   if (sample)
     return planar_rollout_policy_launches<true, true>(h, st, nsteps, params_dev, pstride, hidden, squash, action_scale, obs_dev, reward_dev, done_dev,
                                                       goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev,
-                                                      PolicyNoise{noise_seed, noise_step, logp_seq_dev}, cr);
+                                                      PolicyNoise{noise_seed, noise_step, logp_seq_dev, noise_mode}, cr, none, next_obs_seq_dev);
   return planar_rollout_policy_launches<false, true>(h, st, nsteps, params_dev, pstride, hidden, squash, action_scale, obs_dev, reward_dev, done_dev,
-                                                     goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, PolicyNoise{0, 0, nullptr}, cr);
+                                                     goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, PolicyNoise{0, 0, nullptr, 0}, cr, none,
+                                                     next_obs_seq_dev);
 }
 
 hipError_t mzk_planar_rollout_net(mz_handle* h, hipStream_t st, int nsteps, const mz_net* actor, int sample, uint64_t noise_seed,
                                   uint64_t noise_step, const mz_net* critic, float* value_seq_dev, float* next_value_seq_dev, float* obs_dev,
                                   float* reward_dev, uint8_t* done_dev, int* goal_idx_dev, float* info_dev, float* obs_seq_dev,
-                                  float* actions_seq_dev, float* logp_seq_dev) {
-  const PolicyNoise ns = sample ? PolicyNoise{noise_seed, noise_step, logp_seq_dev} : PolicyNoise{0, 0, nullptr};
+                                  float* actions_seq_dev, float* logp_seq_dev, int noise_mode, float* next_obs_seq_dev) {
+  const PolicyNoise ns = sample ? PolicyNoise{noise_seed, noise_step, logp_seq_dev, noise_mode} : PolicyNoise{0, 0, nullptr, 0};
   PolicyShapes sh{{actor->n_hidden, actor->hidden[0], actor->hidden[1], actor->activation}, {0, 0, 0, 0}};
   PolicyCritic cr{nullptr, 0, 0, nullptr, nullptr};
   if (critic) {
@@ -1087,7 +1129,7 @@ hipError_t mzk_planar_rollout_net(mz_handle* h, hipStream_t st, int nsteps, cons
 #define MZ_NET_ROLL(SMP, CRT, NRM)                                                                                                          \
   planar_rollout_policy_launches<SMP, CRT, true, NRM>(h, st, nsteps, actor->params_dev, (long)actor->env_stride, 0, actor->squash,          \
                                                       (float)actor->action_scale, obs_dev, reward_dev, done_dev, goal_idx_dev, info_dev,    \
-                                                      obs_seq_dev, actions_seq_dev, ns, cr, sh)
+                                                      obs_seq_dev, actions_seq_dev, ns, cr, sh, next_obs_seq_dev)
   if (h->nrm_mean) {
     if (critic) return sample ? MZ_NET_ROLL(true, true, true) : MZ_NET_ROLL(false, true, true);
     return sample ? MZ_NET_ROLL(true, false, true) : MZ_NET_ROLL(false, false, true);

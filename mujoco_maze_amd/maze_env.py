@@ -438,7 +438,13 @@ class VecMazeEnv:
             info["final_observation"] = self._final_obs  # valid in the rows where done != 0
         return self._obs, self._reward, self._done, info
 
-    def rollout(self, actions, repeat: Optional[int] = None, return_obs: bool = False):
+    def _next_obs_row(self, obs, done, info):
+        """The row a step produced before any auto-reset, from what `step()` returned: the terminal row where the env finished."""
+        if not self._auto_reset:
+            return obs
+        return self._torch.where((done != 0).unsqueeze(1), info["final_observation"], obs)
+
+    def rollout(self, actions, repeat: Optional[int] = None, return_obs: bool = False, return_next_obs: bool = False):
         """K steps in one call, for callers that need nothing from the host between steps (sampling planners on pre-drawn action
         sequences, action repeat, random walks): the results and the env's state afterwards are exactly those of K `step()` calls.
 
@@ -447,6 +453,11 @@ class VecMazeEnv:
         "goal_index" [K, N], "position" [K, N, 2], "reward_forward" / "reward_ctrl" [K, N], "observations" [K, N, obs_dim] with
         `return_obs`, and under auto-reset "final_observation" (row i: the last terminal observation of env i).  The output tensors
         are reused by the next rollout of the same K.
+
+        With `return_next_obs`, info["next_observations"] [K, N, obs_dim]: the row step k produced BEFORE any auto-reset — equal to
+        "observations"[k] wherever dones[k] == 0, the step's terminal row where the env finished (every one of them, where
+        "final_observation" keeps only the env's last).  It is the s' of the transition (s, a, r, s', d); s is the row before:
+        the entry observation, then "observations"[k - 1].  One mz_rollout_ex call.
 
         One mz_rollout call (fused kernels for the Point, Swimmer and Reacher: `launch_info()["rollout_fused"]`) — except where the
         host has work between steps (Python reward()/termination() overrides; per-env goals under auto-reset, which are resampled
@@ -465,13 +476,22 @@ class VecMazeEnv:
             K = int(a.shape[0])
         if not 1 <= K <= 65536:
             raise ValueError(f"a rollout takes 1 .. 65536 steps, got {K}")
-        buf = self._rollout_buffers(K, return_obs)
+        buf = self._rollout_buffers(K, return_obs, return_next_obs)
         if self._host_rewards or (self._env_goals is not None and self._auto_reset):
             for k in range(K):
                 obs, rew, done, inf = self.step(a if repeat is not None else a[k])
                 buf["reward"][k], buf["done"][k], buf["goal"][k], buf["info"][k] = rew, done, inf["goal_index"], self._info
                 if return_obs:
                     buf["obs_seq"][k] = obs
+                if return_next_obs:
+                    buf["next_obs_seq"][k] = self._next_obs_row(obs, done, inf)
+        elif return_next_obs:
+            io = _capi.make_rollout_io(K, actions_dev=_ptr(a), action_step_stride=0 if repeat is not None else n * self.nu, obs_dev=_ptr(self._obs),
+                                       reward_dev=_ptr(buf["reward"]), done_dev=_ptr(buf["done"]), goal_idx_dev=_ptr(buf["goal"]),
+                                       info_dev=_ptr(buf["info"]), obs_seq_dev=_ptr(buf["obs_seq"]) if return_obs else None,
+                                       next_obs_seq_dev=_ptr(buf["next_obs_seq"]))
+            rc = self._lib.mz_rollout_ex(self._h, C.byref(io), self._stream())
+            _capi.check(self._lib, self._h, rc, "mz_rollout_ex")
         else:
             rc = self._lib.mz_rollout(self._h, K, _ptr(a), 0 if repeat is not None else n * self.nu, _ptr(self._obs), _ptr(buf["reward"]),
                                       _ptr(buf["done"]), _ptr(buf["goal"]), _ptr(buf["info"]), _ptr(buf["obs_seq"]) if return_obs else None,
@@ -481,6 +501,8 @@ class VecMazeEnv:
                 "goal_index": buf["goal"]}
         if return_obs:
             info["observations"] = buf["obs_seq"]
+        if return_next_obs:
+            info["next_observations"] = buf["next_obs_seq"]
         if self._auto_reset:
             info["final_observation"] = self._final_obs
         return self._obs, buf["reward"], buf["done"], info
@@ -541,7 +563,7 @@ class VecMazeEnv:
 
     def rollout_policy(self, params, steps: int, hidden=0, squash: bool = False, action_scale: float = 1.0, obs=None,
                        return_obs: bool = False, return_actions: bool = False, value_params=None, value_hidden=0, gae=None,
-                       activation: str = "tanh", value_activation: str = "tanh"):
+                       activation: str = "tanh", value_activation: str = "tanh", return_next_obs: bool = False):
         """K = `steps` closed-loop steps in one call: a = policy(obs); obs, reward, done = step(a) — exactly what K times
         (`policy_act`, `step`) give, state and outputs bit for bit.  params / hidden / squash / action_scale as in `policy_act`.
         The policy acts first on the env's last returned observation (what reset / step / rollout left in the observation buffer),
@@ -558,10 +580,13 @@ class VecMazeEnv:
 
         value_params / value_hidden / gae: a critic evaluated along the way and the advantages from it, see `rollout_policy_sample`.
         hidden / activation as in `policy_act`, value_hidden / value_activation as in `value`: a network with two hidden layers or
-        ReLU units, actor or critic, makes the call one mz_rollout_net."""
-        if value_params is not None or gae is not None or not self._net_kind(hidden, activation)[2]:
+        ReLU units, actor or critic, makes the call one mz_rollout_net.
+
+        return_next_obs: info["next_observations"] [K, N, obs_dim] as in `rollout` (raw rows, whether or not a normaliser is bound);
+        the call is then one mz_rollout_ex."""
+        if value_params is not None or gae is not None or return_next_obs or not self._net_kind(hidden, activation)[2]:
             return self._rollout_actor_critic(False, params, steps, hidden, squash, action_scale, obs, None, None, return_obs, return_actions,
-                                              value_params, value_hidden, gae, activation, value_activation)
+                                              value_params, value_hidden, gae, activation, value_activation, return_next_obs)
         torch, n = self._torch, self.num_envs
         p, stride = self._policy_params(params, hidden)
         K = int(steps)
@@ -611,7 +636,7 @@ class VecMazeEnv:
         return C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), C.c_uint64(step & 0xFFFFFFFFFFFFFFFF)
 
     def policy_sample(self, params, obs=None, hidden=0, squash: bool = False, action_scale: float = 1.0, noise_seed: Optional[int] = None,
-                      noise_step: Optional[int] = None, activation: str = "tanh"):
+                      noise_step: Optional[int] = None, activation: str = "tanh", noise: str = "pre_squash"):
         """One draw from a diagonal-Gaussian policy on the device (mz_policy_sample): (actions [N, nu], logp [N]).  params: float32
         [npar_s] or [N, npar_s], the vector of `policy_act` followed by log_std [nu] (`policy.pack(..., log_std=)`).  With m the
         network's pre-squash output, a = m + exp(log_std) * eps, or action_scale * tanh(.) of that with `squash`; logp is the density
@@ -622,7 +647,12 @@ class VecMazeEnv:
         constructor's; noise_step to an env-held counter that starts at 0 (again after `reset(seed=...)`) and advances by 1 per call
         and by K per `rollout_policy_sample`.  Explicit values are used as given and leave the counter alone.
 
-        hidden / activation as in `policy_act`; the noise and logp do not depend on the network's shape."""
+        hidden / activation as in `policy_act`; the noise and logp do not depend on the network's shape.
+
+        noise="action" (TD3 / DDPG exploration, mz_net_sample): the noise goes on the action instead of through the squash —
+        a = clip(action_scale * tanh(m) + exp(log_std) * eps, +-action_scale) with `squash`; without it the two modes are the same.
+        eps and logp are those of the default "pre_squash" (logp: the density of the unclipped sum around the deterministic action)."""
+        mode = _capi.noise_mode(noise)
         widths, act, legacy = self._net_kind(hidden, activation)
         p, stride = self._policy_params(params, hidden, stochastic=True)
         o = self._obs if obs is None else self._policy_obs(obs)
@@ -630,7 +660,12 @@ class VecMazeEnv:
         out = torch.empty((self.num_envs, self.nu), dtype=torch.float32, device=self.device)
         logp = torch.empty(self.num_envs, dtype=torch.float32, device=self.device)
         seed, step = self._noise_args(noise_seed, noise_step, 1)
-        if legacy:
+        if mode != _capi.NOISE_PRE_SQUASH:
+            net = _capi.make_net(_ptr(p), stride, widths, act, squash, action_scale)
+            nz = _capi.make_noise(mode, seed.value, step.value)
+            rc = self._lib.mz_net_sample(self._h, C.byref(net), C.byref(nz), _ptr(o), _ptr(out), _ptr(logp), self._stream())
+            _capi.check(self._lib, self._h, rc, "mz_net_sample")
+        elif legacy:
             rc = self._lib.mz_policy_sample(self._h, _ptr(p), stride, int(hidden), 1 if squash else 0, float(action_scale), seed, step, _ptr(o), _ptr(out),
                                             _ptr(logp), self._stream())
             _capi.check(self._lib, self._h, rc, "mz_policy_sample")
@@ -643,7 +678,7 @@ class VecMazeEnv:
     def rollout_policy_sample(self, params, steps: int, hidden=0, squash: bool = False, action_scale: float = 1.0, obs=None,
                               noise_seed: Optional[int] = None, noise_step: Optional[int] = None, return_obs: bool = False,
                               return_actions: bool = False, value_params=None, value_hidden=0, gae=None, activation: str = "tanh",
-                              value_activation: str = "tanh"):
+                              value_activation: str = "tanh", noise: str = "pre_squash", return_next_obs: bool = False):
         """K = `steps` closed-loop steps with a sampled action each, in one call: exactly what K times (`policy_sample` with
         noise_step + k, `step`) give, state and outputs bit for bit.  Everything as in `rollout_policy`, plus info["logp"] [K, N], the
         log-probabilities of the draws (see `policy_sample`); info["actions"] [K, N, nu] with `return_actions` holds the sampled
@@ -663,10 +698,16 @@ class VecMazeEnv:
 
         hidden / activation as in `policy_act`, value_hidden / value_activation as in `value`: `hidden=(64, 64)`,
         `value_hidden=(64, 64)` is the default network of PPO / A2C code.  A network with two hidden layers or ReLU units, actor or
-        critic, makes the call one mz_rollout_net — the same loop, the same fused kernels on the Point, Swimmer and Reacher."""
-        if value_params is not None or gae is not None or not self._net_kind(hidden, activation)[2]:
+        critic, makes the call one mz_rollout_net — the same loop, the same fused kernels on the Point, Swimmer and Reacher.
+
+        noise as in `policy_sample` ("action": TD3 / DDPG exploration), return_next_obs as in `rollout`: either makes the call one
+        mz_rollout_ex, which runs the same kernels.  Together they collect an off-policy batch in one call: s = the entry observation
+        followed by "observations"[:-1], a = "actions", r, s' = "next_observations", terminated = dones & 1."""
+        mode = _capi.noise_mode(noise)
+        if value_params is not None or gae is not None or return_next_obs or mode != _capi.NOISE_PRE_SQUASH or not self._net_kind(hidden, activation)[2]:
             return self._rollout_actor_critic(True, params, steps, hidden, squash, action_scale, obs, noise_seed, noise_step, return_obs,
-                                              return_actions, value_params, value_hidden, gae, activation, value_activation)
+                                              return_actions, value_params, value_hidden, gae, activation, value_activation, return_next_obs,
+                                              noise)
         torch, n = self._torch, self.num_envs
         p, stride = self._policy_params(params, hidden, stochastic=True)
         K = int(steps)
@@ -805,11 +846,14 @@ class VecMazeEnv:
         return ret, ln
 
     def _rollout_actor_critic(self, sample: bool, params, steps, hidden, squash, action_scale, obs, noise_seed, noise_step, return_obs,
-                              return_actions, value_params, value_hidden, gae, activation="tanh", value_activation="tanh"):
+                              return_actions, value_params, value_hidden, gae, activation="tanh", value_activation="tanh",
+                              return_next_obs=False, noise="pre_squash"):
         """rollout_policy (sample False) / rollout_policy_sample (sample True) with a critic, or with a network that needs mz_net
-        (then the critic is optional): one mz_rollout_actor_critic or mz_rollout_net call, or the defining loop where the host has
-        work between steps."""
+        (then the critic is optional): one mz_rollout_actor_critic or mz_rollout_net call — one mz_rollout_ex with return_next_obs or
+        noise="action" —, or the defining loop where the host has work between steps."""
         torch, n = self._torch, self.num_envs
+        mode = _capi.noise_mode(noise)
+        extended = return_next_obs or mode != _capi.NOISE_PRE_SQUASH
         with_critic = value_params is not None
         if gae is not None and not with_critic:
             raise ValueError("gae=(gamma, lam) needs a critic: pass value_params")
@@ -828,7 +872,7 @@ class VecMazeEnv:
             o = self._policy_obs(obs)
             if o.data_ptr() != self._obs.data_ptr():
                 self._obs.copy_(o)
-        buf = self._rollout_buffers(K, return_obs)
+        buf = self._rollout_buffers(K, return_obs, return_next_obs)
         if return_actions and "actions" not in buf:
             buf["actions"] = torch.empty((K, n, self.nu), dtype=torch.float32, device=self.device)
         for key in (("logp",) if sample else ()) + (("values", "next_values") if with_critic else ()) + (("advantages", "returns") if gae is not None else ()):
@@ -840,7 +884,7 @@ class VecMazeEnv:
                 if with_critic:
                     buf["values"][k] = self.value(vp, None, value_hidden, value_activation)
                 if sample:
-                    a, buf["logp"][k] = self.policy_sample(p, None, hidden, squash, action_scale, seed.value, step.value + k, activation)
+                    a, buf["logp"][k] = self.policy_sample(p, None, hidden, squash, action_scale, seed.value, step.value + k, activation, noise)
                 else:
                     a = self.policy_act(p, None, hidden, squash, action_scale, activation)
                 o, rew, done, inf = self.step(a)
@@ -852,8 +896,24 @@ class VecMazeEnv:
                     buf["next_values"][k] = nv
                 if return_obs:
                     buf["obs_seq"][k] = o
+                if return_next_obs:
+                    buf["next_obs_seq"][k] = self._next_obs_row(o, done, inf)
                 if return_actions:
                     buf["actions"][k] = a
+        elif extended:
+            io = _capi.make_rollout_io(K, actor=_capi.make_net(_ptr(p), stride, widths, act, squash, action_scale),
+                                       noise=_capi.make_noise(mode, seed.value, step.value) if sample else None,
+                                       critic=_capi.make_net(_ptr(vp), vstride, vwidths, vact) if with_critic else None,
+                                       obs_dev=_ptr(self._obs), reward_dev=_ptr(buf["reward"]), done_dev=_ptr(buf["done"]),
+                                       goal_idx_dev=_ptr(buf["goal"]), info_dev=_ptr(buf["info"]),
+                                       obs_seq_dev=_ptr(buf["obs_seq"]) if return_obs else None,
+                                       actions_seq_dev=_ptr(buf["actions"]) if return_actions else None,
+                                       logp_seq_dev=_ptr(buf["logp"]) if sample else None,
+                                       value_seq_dev=_ptr(buf["values"]) if with_critic else None,
+                                       next_value_seq_dev=_ptr(buf["next_values"]) if with_critic else None,
+                                       next_obs_seq_dev=_ptr(buf["next_obs_seq"]) if return_next_obs else None)
+            rc = self._lib.mz_rollout_ex(self._h, C.byref(io), self._stream())
+            _capi.check(self._lib, self._h, rc, "mz_rollout_ex")
         elif not legacy:
             actor = _capi.make_net(_ptr(p), stride, widths, act, squash, action_scale)
             critic = _capi.make_net(_ptr(vp), vstride, vwidths, vact) if with_critic else None
@@ -882,13 +942,15 @@ class VecMazeEnv:
                                                            out=(buf["advantages"], buf["returns"]))
         if return_obs:
             info["observations"] = buf["obs_seq"]
+        if return_next_obs:
+            info["next_observations"] = buf["next_obs_seq"]
         if return_actions:
             info["actions"] = buf["actions"]
         if self._auto_reset:
             info["final_observation"] = self._final_obs
         return self._obs, buf["reward"], buf["done"], info
 
-    def _rollout_buffers(self, K: int, with_obs: bool) -> dict:
+    def _rollout_buffers(self, K: int, with_obs: bool, with_next_obs: bool = False) -> dict:
         """Output tensors of rollout(), allocated per K and kept."""
         torch, n, dev = self._torch, self.num_envs, self.device
         cache = self.__dict__.setdefault("_rollout_cache", {})
@@ -898,6 +960,8 @@ class VecMazeEnv:
                               "goal": torch.empty((K, n), dtype=torch.int32, device=dev), "info": torch.empty((K, n, 4), dtype=torch.float32, device=dev)}
         if with_obs and "obs_seq" not in buf:
             buf["obs_seq"] = torch.empty((K, n, self.obs_dim), dtype=torch.float32, device=dev)
+        if with_next_obs and "next_obs_seq" not in buf:
+            buf["next_obs_seq"] = torch.empty((K, n, self.obs_dim), dtype=torch.float32, device=dev)
         return buf
 
     def _apply_host_task(self):

@@ -213,11 +213,20 @@ def noise(noise_seed: int, noise_step: int, slots, nu: int):
     return (r * c).astype(np.float32)
 
 
+_eps = noise  # (sample_reference has an argument of that name)
+
+
 def sample_reference(params, obs, nu: int, hidden=0, squash: bool = False, action_scale: float = 1.0, noise_seed: int = 0,
-                     noise_step: int = 0, slots=None, activation: str = "tanh"):
+                     noise_step: int = 0, slots=None, activation: str = "tanh", noise: str = "pre_squash"):
     """The stochastic policy of csrc/mz_policy.h on rows of observations: obs [R, obs_dim] (or [obs_dim]); params [npar_s] shared by
     the rows or [R, npar_s]; slots: the rows' global env slots, default 0 .. R - 1.  Returns (actions float32 [R, nu], logp float32
-    [R]) — or ([nu], scalar) for a single row."""
+    [R]) — or ([nu], scalar) for a single row.
+
+    noise="pre_squash" (MZ_NOISE_PRE_SQUASH): z = m + s * eps, a = action_scale * tanh(z) with `squash`.  noise="action"
+    (MZ_NOISE_ACTION, TD3 / DDPG exploration): b = action_scale * tanh(m) with `squash` else m, z = b + s * eps, and with `squash`
+    a = z clipped to +-action_scale by two selects (NaN passes).  eps and logp are the same in both modes."""
+    if noise not in ("pre_squash", "action"):
+        raise ValueError(f"noise must be 'pre_squash' or 'action', got {noise!r}")
     x = np.asarray(obs, dtype=np.float32)
     single = x.ndim == 1
     x = np.atleast_2d(x)
@@ -231,11 +240,16 @@ def sample_reference(params, obs, nu: int, hidden=0, squash: bool = False, actio
         raise ValueError(f"slots must name one global env slot per row ({R}), got {len(sl)}")
     ls = np.broadcast_to(p[..., npar:], (R, nu))
     m = _pre_squash(x, p[..., :npar], nu, shape)
-    eps = noise(noise_seed, noise_step, sl, nu)
+    eps = _eps(noise_seed, noise_step, sl, nu)
     with np.errstate(over="ignore", invalid="ignore"):
         s = np.exp(ls.astype(np.float64)).astype(np.float32)
-        z = (m + (s * eps).astype(np.float32)).astype(np.float32)
-        act = _squashed(z, squash, action_scale)
+        if noise == "action" and squash:
+            A = np.float32(action_scale)
+            z = (_squashed(m, True, action_scale) + (s * eps).astype(np.float32)).astype(np.float32)
+            act = np.where(z < -A, -A, np.where(z > A, A, z)).astype(np.float32)
+        else:
+            z = (m + (s * eps).astype(np.float32)).astype(np.float32)
+            act = _squashed(z, squash, action_scale)
         logp = np.zeros(R, dtype=np.float32)
         for u in range(nu):
             q = (eps[:, u] * eps[:, u]).astype(np.float32)

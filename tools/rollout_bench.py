@@ -22,6 +22,11 @@ With --obs-norm every --policy mode binds an observation normaliser first (env.b
 a few random steps, clip 5), so that all its legs evaluate their networks on normalised rows; a torch network normalises and clamps
 in torch.
     python tools/rollout_bench.py --policy 64,64 --sample --critic 64,64 --steps 128 --obs-norm --ids PointUMaze-v0,SwimmerUMaze-v0
+With --policy H --sample --next-obs one off-policy collection window, the transitions (s, a, r, s', d) of K steps: K x (env.policy_sample +
+env.step + torch.where(done, final_observation, obs)) with the rows kept — the only way to the per-step terminal rows without
+return_next_obs —; one env.rollout_policy_sample(..., return_obs, return_actions, return_next_obs); and the same call without the next
+rows beside them.  --noise action puts the noise on the action in every leg (TD3 / DDPG exploration; log_std = log(0.1) on every unit).
+    python tools/rollout_bench.py --policy 64,64 --activation relu --sample --next-obs --noise action --steps 128 --ids PointUMaze-v0,SwimmerUMaze-v0,AntUMaze-v0
 Kernel durations come from a run of their own:  rocprofv3 --kernel-trace --stats -d <dir> -- python tools/rollout_bench.py --seconds 0.2"""
 import argparse
 import json
@@ -263,6 +268,75 @@ def bench_critic(env_id, n, K, H, HV, seconds, repeats, ACT="tanh", obs_norm=Fal
             **{name + "_env_steps_per_s": v for name, v in res.items()}}
 
 
+def bench_transitions(env_id, n, K, H, seconds, repeats, ACT="tanh", obs_norm=False, noise="pre_squash"):
+    """One off-policy collection window of K steps: policy_sample + step + torch.where on the terminal rows; one
+    rollout_policy_sample with return_next_obs; the same call without the next rows."""
+    import math
+
+    dev = torch.device("cuda", 0)
+    env = mm.make(env_id, num_envs=n, auto_reset=True, device=dev, force_vec=True)
+    env.reset(seed=20260928)
+    g = torch.Generator(device=dev).manual_seed(1234)
+    bind_norm(env, obs_norm, dev, g)  # (no torch network in this mode)
+
+    def lin(out, fan_in):
+        k = fan_in ** -0.5
+        return (2 * torch.rand((out, fan_in), device=dev, generator=g) - 1) * k, (2 * torch.rand(out, device=dev, generator=g) - 1) * k
+
+    log_std = torch.full((env.nu,), math.log(0.1) if noise == "action" else -0.5)
+    params, _ = build_net(lin, env.obs_dim, env.nu, H, ACT, dev, log_std=log_std)
+    kw = dict(hidden=H, activation=ACT, squash=True, noise=noise)
+    obs_rows, next_rows = torch.empty((K, n, env.obs_dim), device=dev), torch.empty((K, n, env.obs_dim), device=dev)
+    act_rows = torch.empty((K, n, env.nu), device=dev)
+    rew, done = torch.empty((K, n), device=dev), torch.empty((K, n), dtype=torch.uint8, device=dev)
+
+    def step_where():
+        for k in range(K):
+            a = env.policy_sample(params, **kw)[0]
+            o, r, d, info = env.step(a)
+            act_rows[k], obs_rows[k], rew[k], done[k] = a, o, r, d
+            next_rows[k] = torch.where((d != 0).unsqueeze(1), info["final_observation"], o)
+
+    def one_call():
+        env.rollout_policy_sample(params, K, return_obs=True, return_actions=True, return_next_obs=True, **kw)
+
+    def no_next():
+        env.rollout_policy_sample(params, K, return_obs=True, return_actions=True, **kw)
+
+    legs = (("sample_step_where", step_where), ("rollout_next_obs", one_call), ("rollout_no_next_obs", no_next))
+    for _ in range(4):
+        for _, fn in legs:
+            fn()
+    res = {name: [] for name, _ in legs}
+    for _ in range(repeats):
+        for name, fn in legs:
+            w, dt = leg(fn, 4, seconds, dev)
+            res[name].append(n * K * w / dt)
+    bad = int((env.status() & 3).ne(0).sum())
+    fused_flag = env.launch_info()["rollout_fused"]
+    env.close()
+    return {"env": env_id, "envs": n, "steps_per_window": K, "hidden": H, "activation": ACT, "obs_norm": bool(obs_norm), "noise": noise, "fused": fused_flag,
+            "flagged_envs": bad, **{name + "_env_steps_per_s": v for name, v in res.items()}}
+
+
+def main_transitions(args):
+    out = []
+    med = lambda v: sorted(v)[len(v) // 2]
+    print(f"off-policy window (s, a, r, s', d), shared squashed Gaussian policy (hidden {args.policy}, {args.activation} units, noise {args.noise}), {args.steps} steps per "
+          f"window, {args.envs} envs, auto-reset, >= {args.seconds} s per leg, {args.repeats} alternating repeats; M env-steps/s, median (max - min)")
+    print("%-18s %5s %26s %26s %26s" % ("env", "fused", "sample + step + where", "one call, next rows", "one call, no next rows"))
+    for env_id in args.ids.split(","):
+        r = bench_transitions(env_id, args.envs, args.steps, args.policy, args.seconds, args.repeats, args.activation, args.obs_norm, args.noise)
+        out.append(r)
+        cell = lambda v: "%10.3f (%6.3f)" % (med(v) / 1e6, (max(v) - min(v)) / 1e6)
+        print("%-18s %5d %26s %26s %26s" % (env_id, r["fused"], cell(r["sample_step_where_env_steps_per_s"]), cell(r["rollout_next_obs_env_steps_per_s"]),
+                                            cell(r["rollout_no_next_obs_env_steps_per_s"])), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            for r in out:
+                f.write(json.dumps(r) + "\n")
+
+
 def main_critic(args):
     out = []
     med = lambda v: sorted(v)[len(v) // 2]
@@ -330,6 +404,8 @@ def main():
     ap.add_argument("--critic", type=hidden_arg, default=None, metavar="HV", help="with --policy H --sample: a critic with HV hidden units (0 = affine; or HV1,HV2) and GAE")
     ap.add_argument("--activation", choices=("tanh", "relu"), default="tanh", help="with --policy: the hidden units of policy and critic")
     ap.add_argument("--obs-norm", action="store_true", help="with --policy: bind an observation normaliser (env.bind_obs_norm) in every leg")
+    ap.add_argument("--next-obs", action="store_true", help="with --policy H --sample: the off-policy window, with every step's pre-reset row")
+    ap.add_argument("--noise", choices=("pre_squash", "action"), default="pre_squash", help="with --next-obs: where the exploration noise goes")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "rollout_bench.py measures on the GPU only"
     if args.sample and args.policy is None:
@@ -340,6 +416,12 @@ def main():
         ap.error("--obs-norm goes with --policy H")
     if args.obs_norm:
         print("observation normaliser bound (clip 5): every network below reads normalised rows")
+    if args.next_obs and (not args.sample or args.critic is not None):
+        ap.error("--next-obs goes with --policy H --sample, without --critic")
+    if args.noise != "pre_squash" and not args.next_obs:
+        ap.error("--noise goes with --next-obs")
+    if args.next_obs:
+        return main_transitions(args)
     if args.critic is not None:
         return main_critic(args)
     if args.policy is not None:
