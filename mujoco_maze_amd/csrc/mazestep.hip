@@ -596,58 +596,9 @@ int32_t mz_step(mz_handle* h, const float* actions_dev, float* obs_dev, float* r
   return MZ_OK;
 }
 
-// row k of next_obs_seq_dev on a handle that steps launch by launch: behind the step's launches, before anything overwrites obs_dev or
-// the final_obs row (the caller has checked that final_obs is bound under auto-reset)
-static hipError_t next_obs_row(mz_handle* h, hipStream_t st, const float* obs_dev, const uint8_t* done_dev, float* out) {
-  const size_t tot = (size_t)h->n * h->model.obs_dim;
-  if (!h->auto_reset) return hipMemcpyAsync(out, obs_dev, tot * sizeof(float), hipMemcpyDeviceToDevice, st);
-  hipLaunchKernelGGL(next_obs_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, h->n, h->model.obs_dim, obs_dev, h->final_obs, done_dev, out);
-  return hipGetLastError();
-}
-
-// n_steps successive mz_step calls in one (include/mazestep.h).  Fused handles (mzk_planar_rollout_fused) advance up to
-// MZ_ROLLOUT_CHUNK steps per launch on a state that stays on chip; every other handle runs the step's own launches n_steps times
-// with the output pointers advanced, which is sequential stepping by construction.
-// next_obs_seq_dev (mz_rollout_ex; NULL from mz_rollout): the row every step produced before any auto-reset — from inside the fused
-// kernels, else one next_obs_row per step.
-static int32_t rollout_open(mz_handle* h, int32_t n_steps, const float* actions_dev, int64_t action_step_stride, float* obs_dev, float* reward_dev,
-                            uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev, float* obs_seq_dev, float* next_obs_seq_dev, void* stream) {
-  if (!h || !actions_dev || !obs_dev || !reward_dev || !done_dev) return h ? set_err(h, MZ_ERR_ARG, "mz_rollout: null array", hipSuccess) : MZ_ERR_ARG;
-  if (n_steps < 1 || n_steps > 65536) return set_err(h, MZ_ERR_ARG, "mz_rollout: n_steps must be 1 .. 65536", hipSuccess);
-  const size_t n = (size_t)h->n, od = (size_t)h->model.obs_dim;
-  if (action_step_stride != 0 && action_step_stride != (int64_t)n * h->model.nu)
-    return set_err(h, MZ_ERR_ARG, "mz_rollout: action_step_stride must be num_envs * nu ([K, N, nu] actions) or 0 (one [N, nu] block repeated)", hipSuccess);
-  DeviceScope scope(h->device);
-  hipStream_t st = (hipStream_t)stream;
-  if (mzk_planar_rollout_fused(h)) {
-    HIPCHK(h, mzk_planar_rollout(h, st, n_steps, actions_dev, (long)action_step_stride, obs_dev, reward_dev, done_dev, goal_idx_dev, info_dev, obs_seq_dev,
-                                 next_obs_seq_dev));
-    if (h->record) {  // the last step's row
-      const size_t tot = n * (od + 2), last = (size_t)(n_steps - 1) * n;
-      hipLaunchKernelGGL(pack_record_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, h->n, h->model.obs_dim, obs_dev, reward_dev + last, done_dev + last, h->record);
-      HIPCHK(h, hipGetLastError());
-    }
-  } else {
-    for (size_t k = 0; k < (size_t)n_steps; k++) {
-      const int rc = step_launches(h, st, actions_dev + k * (size_t)action_step_stride, obs_dev, reward_dev + k * n, done_dev + k * n,
-                                   goal_idx_dev ? goal_idx_dev + k * n : NULL, info_dev ? info_dev + k * n * 4 : NULL);
-      if (rc != MZ_OK) return rc;
-      if (next_obs_seq_dev) HIPCHK(h, next_obs_row(h, st, obs_dev, done_dev + k * n, next_obs_seq_dev + k * n * od));
-      if (obs_seq_dev) HIPCHK(h, hipMemcpyAsync(obs_seq_dev + k * n * od, obs_dev, n * od * sizeof(float), hipMemcpyDeviceToDevice, st));
-    }
-  }
-  h->nsteps += n_steps;
-  return MZ_OK;
-}
-
-int32_t mz_rollout(mz_handle* h, int32_t n_steps, const float* actions_dev, int64_t action_step_stride, float* obs_dev, float* reward_dev,
-                   uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev, float* obs_seq_dev, void* stream) {
-  return rollout_open(h, n_steps, actions_dev, action_step_stride, obs_dev, reward_dev, done_dev, goal_idx_dev, info_dev, obs_seq_dev, NULL, stream);
-}
-
-// A legacy network (int `hidden`, tanh) as the mz_net it is.  While a normaliser is bound (mz_bind_obs_norm) the legacy entries forward
-// to the network entries, which return the bits of the legacy ones for such a network and whose kernels have the NRM instantiations;
-// unbound handles launch what they always launched.
+// A legacy network (int `hidden`, tanh) as the mz_net it is.  While a normaliser is bound (mz_bind_obs_norm) the legacy entries run
+// the network entries' kernels, which return the bits of the legacy ones for such a network and have the NRM instantiations; unbound
+// handles launch what they always launched (the single calls below; the rollouts: mzk_rollout_kernels).
 static mz_net legacy_net(const float* params_dev, int64_t env_stride, int hidden, int squash, double action_scale) {
   return mz_net{(uint32_t)sizeof(mz_net), hidden > 0 ? 1 : 0, {hidden, 0}, MZ_ACT_TANH, squash, action_scale, params_dev, env_stride};
 }
@@ -697,50 +648,6 @@ int32_t mz_policy_act(mz_handle* h, const float* params_dev, int64_t param_env_s
   return MZ_OK;
 }
 
-// n_steps times a = policy(obs); step(a) in one call (include/mazestep.h).  Fused handles evaluate the policy inside the rollout
-// kernels (planar_kernels.hip); every other handle runs the defining loop itself: policy_act_kernel into row k of actions_seq_dev (or
-// the handle's scratch), then the step's own launches.
-int32_t mz_rollout_policy(mz_handle* h, int32_t n_steps, const float* params_dev, int64_t param_env_stride, int32_t hidden, int32_t squash,
-                          double action_scale, float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev,
-                          float* obs_seq_dev, float* actions_seq_dev, void* stream) {
-  if (!h) return MZ_ERR_ARG;
-  if (!obs_dev || !reward_dev || !done_dev) return set_err(h, MZ_ERR_ARG, "mz_rollout_policy: null array", hipSuccess);
-  if (n_steps < 1 || n_steps > 65536) return set_err(h, MZ_ERR_ARG, "mz_rollout_policy: n_steps must be 1 .. 65536", hipSuccess);
-  int rc = policy_args(h, "mz_rollout_policy", params_dev, param_env_stride, hidden, squash);
-  if (rc != MZ_OK) return rc;
-  if (h->nrm_mean) {
-    const mz_net a = legacy_net(params_dev, param_env_stride, hidden, squash, action_scale);
-    return mz_rollout_net(h, n_steps, &a, 0, 0, 0, NULL, NULL, NULL, obs_dev, reward_dev, done_dev, goal_idx_dev, info_dev, obs_seq_dev,
-                          actions_seq_dev, NULL, stream);
-  }
-  const size_t n = (size_t)h->n, od = (size_t)h->model.obs_dim, nu = (size_t)h->model.nu;
-  const float scale = (float)action_scale;
-  DeviceScope scope(h->device);
-  hipStream_t st = (hipStream_t)stream;
-  if (mzk_planar_rollout_fused(h)) {
-    HIPCHK(h, mzk_planar_rollout_policy(h, st, n_steps, params_dev, (long)param_env_stride, hidden, squash, scale, obs_dev, reward_dev, done_dev,
-                                        goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev));
-    if (h->record) {  // the last step's row
-      const size_t tot = n * (od + 2), last = (size_t)(n_steps - 1) * n;
-      hipLaunchKernelGGL(pack_record_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, h->n, h->model.obs_dim, obs_dev, reward_dev + last, done_dev + last, h->record);
-      HIPCHK(h, hipGetLastError());
-    }
-  } else {
-    if (!actions_seq_dev && !h->policy_act) HIPCHK(h, hipMalloc(&h->policy_act, n * nu * sizeof(float)));
-    for (size_t k = 0; k < (size_t)n_steps; k++) {
-      float* a = actions_seq_dev ? actions_seq_dev + k * n * nu : h->policy_act;
-      policy_act_launch(h, st, params_dev, param_env_stride, hidden, squash, scale, obs_dev, a);
-      HIPCHK(h, hipGetLastError());
-      rc = step_launches(h, st, a, obs_dev, reward_dev + k * n, done_dev + k * n, goal_idx_dev ? goal_idx_dev + k * n : NULL,
-                         info_dev ? info_dev + k * n * 4 : NULL);
-      if (rc != MZ_OK) return rc;
-      if (obs_seq_dev) HIPCHK(h, hipMemcpyAsync(obs_seq_dev + k * n * od, obs_dev, n * od * sizeof(float), hipMemcpyDeviceToDevice, st));
-    }
-  }
-  h->nsteps += n_steps;
-  return MZ_OK;
-}
-
 static void policy_sample_launch(mz_handle* h, hipStream_t st, const float* params_dev, int64_t pstride, int hidden, int squash, float scale,
                                  uint64_t noise_seed, uint64_t noise_step, const float* obs_dev, float* actions_dev, float* logp_dev) {
   const int rows = 256 / MZ_POLICY_LANES;
@@ -764,51 +671,6 @@ int32_t mz_policy_sample(mz_handle* h, const float* params_dev, int64_t param_en
                          actions_dev, logp_dev);
   }
   HIPCHK(h, hipGetLastError());
-  return MZ_OK;
-}
-
-// n_steps times a ~ policy(obs); step(a) in one call, step k with the noise of noise_step + k (include/mazestep.h).  Fused handles
-// sample inside the rollout kernels (planar_kernels.hip); every other handle runs the defining loop itself, as mz_rollout_policy does.
-int32_t mz_rollout_policy_sample(mz_handle* h, int32_t n_steps, const float* params_dev, int64_t param_env_stride, int32_t hidden, int32_t squash,
-                                 double action_scale, uint64_t noise_seed, uint64_t noise_step, float* obs_dev, float* reward_dev,
-                                 uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev, float* obs_seq_dev, float* actions_seq_dev,
-                                 float* logp_seq_dev, void* stream) {
-  if (!h) return MZ_ERR_ARG;
-  if (!obs_dev || !reward_dev || !done_dev) return set_err(h, MZ_ERR_ARG, "mz_rollout_policy_sample: null array", hipSuccess);
-  if (n_steps < 1 || n_steps > 65536) return set_err(h, MZ_ERR_ARG, "mz_rollout_policy_sample: n_steps must be 1 .. 65536", hipSuccess);
-  int rc = policy_args(h, "mz_rollout_policy_sample", params_dev, param_env_stride, hidden, squash, true);
-  if (rc != MZ_OK) return rc;
-  if (h->nrm_mean) {
-    const mz_net a = legacy_net(params_dev, param_env_stride, hidden, squash, action_scale);
-    return mz_rollout_net(h, n_steps, &a, 1, noise_seed, noise_step, NULL, NULL, NULL, obs_dev, reward_dev, done_dev, goal_idx_dev, info_dev,
-                          obs_seq_dev, actions_seq_dev, logp_seq_dev, stream);
-  }
-  const size_t n = (size_t)h->n, od = (size_t)h->model.obs_dim, nu = (size_t)h->model.nu;
-  const float scale = (float)action_scale;
-  DeviceScope scope(h->device);
-  hipStream_t st = (hipStream_t)stream;
-  if (mzk_planar_rollout_fused(h)) {
-    HIPCHK(h, mzk_planar_rollout_policy_sample(h, st, n_steps, params_dev, (long)param_env_stride, hidden, squash, scale, noise_seed, noise_step, obs_dev,
-                                               reward_dev, done_dev, goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, logp_seq_dev));
-    if (h->record) {  // the last step's row
-      const size_t tot = n * (od + 2), last = (size_t)(n_steps - 1) * n;
-      hipLaunchKernelGGL(pack_record_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, h->n, h->model.obs_dim, obs_dev, reward_dev + last, done_dev + last, h->record);
-      HIPCHK(h, hipGetLastError());
-    }
-  } else {
-    if (!actions_seq_dev && !h->policy_act) HIPCHK(h, hipMalloc(&h->policy_act, n * nu * sizeof(float)));
-    for (size_t k = 0; k < (size_t)n_steps; k++) {
-      float* a = actions_seq_dev ? actions_seq_dev + k * n * nu : h->policy_act;
-      policy_sample_launch(h, st, params_dev, param_env_stride, hidden, squash, scale, noise_seed, noise_step + k, obs_dev, a,
-                           logp_seq_dev ? logp_seq_dev + k * n : NULL);
-      HIPCHK(h, hipGetLastError());
-      rc = step_launches(h, st, a, obs_dev, reward_dev + k * n, done_dev + k * n, goal_idx_dev ? goal_idx_dev + k * n : NULL,
-                         info_dev ? info_dev + k * n * 4 : NULL);
-      if (rc != MZ_OK) return rc;
-      if (obs_seq_dev) HIPCHK(h, hipMemcpyAsync(obs_seq_dev + k * n * od, obs_dev, n * od * sizeof(float), hipMemcpyDeviceToDevice, st));
-    }
-  }
-  h->nsteps += n_steps;
   return MZ_OK;
 }
 
@@ -849,77 +711,6 @@ int32_t mz_value(mz_handle* h, const float* vparams_dev, int64_t env_stride, int
   return MZ_OK;
 }
 
-// mz_rollout_policy / mz_rollout_policy_sample with a critic evaluated where the rows sit (include/mazestep.h).  Without a critic the
-// call IS one of those two.  Fused handles evaluate the critic inside the rollout kernels (planar_kernels.hip, CRT); every other
-// handle runs the defining loop itself: value_kernel, the policy's kernel, the step's own launches — mzk_view_fill among them, so the
-// view entries of both rows are in place —, then value_kernel again with the final_obs row where the env finished under auto-reset.
-int32_t mz_rollout_actor_critic(mz_handle* h, int32_t n_steps, const float* params_dev, int64_t param_env_stride, int32_t hidden, int32_t squash,
-                                double action_scale, int32_t sample, uint64_t noise_seed, uint64_t noise_step, const mz_critic* critic,
-                                float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev, float* obs_seq_dev,
-                                float* actions_seq_dev, float* logp_seq_dev, void* stream) {
-  if (!h) return MZ_ERR_ARG;
-  if (sample != 0 && sample != 1) return set_err(h, MZ_ERR_ARG, "mz_rollout_actor_critic: sample must be 0 or 1", hipSuccess);
-  if (!critic)
-    return sample ? mz_rollout_policy_sample(h, n_steps, params_dev, param_env_stride, hidden, squash, action_scale, noise_seed, noise_step, obs_dev,
-                                             reward_dev, done_dev, goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, logp_seq_dev, stream)
-                  : mz_rollout_policy(h, n_steps, params_dev, param_env_stride, hidden, squash, action_scale, obs_dev, reward_dev, done_dev,
-                                      goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, stream);
-  if (!obs_dev || !reward_dev || !done_dev) return set_err(h, MZ_ERR_ARG, "mz_rollout_actor_critic: null array", hipSuccess);
-  if (n_steps < 1 || n_steps > 65536) return set_err(h, MZ_ERR_ARG, "mz_rollout_actor_critic: n_steps must be 1 .. 65536", hipSuccess);
-  int rc = policy_args(h, "mz_rollout_actor_critic", params_dev, param_env_stride, hidden, squash, sample != 0);
-  if (rc != MZ_OK) return rc;
-  if (critic->reserved != 0) return set_err(h, MZ_ERR_ARG, "mz_rollout_actor_critic: critic->reserved must be 0", hipSuccess);
-  rc = critic_args(h, "mz_rollout_actor_critic", critic->params_dev, critic->env_stride, critic->hidden);
-  if (rc != MZ_OK) return rc;
-  if (critic->next_value_seq_dev && h->auto_reset && !h->final_obs)
-    return set_err(h, MZ_ERR_ARG, "mz_rollout_actor_critic: critic->next_value_seq_dev under auto-reset needs a bound final_obs buffer "
-                                  "(mz_bind_final_obs): the terminal rows are valued there", hipSuccess);
-  const size_t n = (size_t)h->n, od = (size_t)h->model.obs_dim, nu = (size_t)h->model.nu;
-  const float scale = (float)action_scale;
-  if (!sample) logp_seq_dev = NULL;
-  if (h->nrm_mean) {
-    const mz_net a = legacy_net(params_dev, param_env_stride, hidden, squash, action_scale);
-    const mz_net c = legacy_net(critic->params_dev, critic->env_stride, critic->hidden, 0, 1.0);
-    return mz_rollout_net(h, n_steps, &a, sample, noise_seed, noise_step, &c, critic->value_seq_dev, critic->next_value_seq_dev, obs_dev, reward_dev,
-                          done_dev, goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, logp_seq_dev, stream);
-  }
-  DeviceScope scope(h->device);
-  hipStream_t st = (hipStream_t)stream;
-  if (mzk_planar_rollout_fused(h)) {
-    HIPCHK(h, mzk_planar_rollout_actor_critic(h, st, n_steps, params_dev, (long)param_env_stride, hidden, squash, scale, sample, noise_seed, noise_step,
-                                              critic, obs_dev, reward_dev, done_dev, goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, logp_seq_dev));
-    if (h->record) {  // the last step's row
-      const size_t tot = n * (od + 2), last = (size_t)(n_steps - 1) * n;
-      hipLaunchKernelGGL(pack_record_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, h->n, h->model.obs_dim, obs_dev, reward_dev + last, done_dev + last, h->record);
-      HIPCHK(h, hipGetLastError());
-    }
-  } else {
-    if (!actions_seq_dev && !h->policy_act) HIPCHK(h, hipMalloc(&h->policy_act, n * nu * sizeof(float)));
-    for (size_t k = 0; k < (size_t)n_steps; k++) {
-      float* a = actions_seq_dev ? actions_seq_dev + k * n * nu : h->policy_act;
-      if (critic->value_seq_dev)
-        value_launch(h, st, critic->params_dev, critic->env_stride, critic->hidden, obs_dev, NULL, NULL, critic->value_seq_dev + k * n);
-      if (sample)
-        policy_sample_launch(h, st, params_dev, param_env_stride, hidden, squash, scale, noise_seed, noise_step + k, obs_dev, a,
-                             logp_seq_dev ? logp_seq_dev + k * n : NULL);
-      else
-        policy_act_launch(h, st, params_dev, param_env_stride, hidden, squash, scale, obs_dev, a);
-      HIPCHK(h, hipGetLastError());
-      rc = step_launches(h, st, a, obs_dev, reward_dev + k * n, done_dev + k * n, goal_idx_dev ? goal_idx_dev + k * n : NULL,
-                         info_dev ? info_dev + k * n * 4 : NULL);
-      if (rc != MZ_OK) return rc;
-      if (critic->next_value_seq_dev) {
-        value_launch(h, st, critic->params_dev, critic->env_stride, critic->hidden, obs_dev, h->auto_reset ? h->final_obs : NULL,
-                     h->auto_reset ? done_dev + k * n : NULL, critic->next_value_seq_dev + k * n);
-        HIPCHK(h, hipGetLastError());
-      }
-      if (obs_seq_dev) HIPCHK(h, hipMemcpyAsync(obs_seq_dev + k * n * od, obs_dev, n * od * sizeof(float), hipMemcpyDeviceToDevice, st));
-    }
-  }
-  h->nsteps += n_steps;
-  return MZ_OK;
-}
-
 // the checks the three mz_net entries share; `which`: the argument's name ("actor" / "critic"), nout: nu or 1, stochastic: the
 // vector carries log_std[nu] behind the network.  MZ_OK or MZ_ERR_ARG with the message set.
 static int net_args(mz_handle* h, const char* who, const char* which, const mz_net* net, int nout, bool stochastic, bool is_critic) {
@@ -949,8 +740,6 @@ static int net_args(mz_handle* h, const char* who, const char* which, const mz_n
 }
 
 static mzp_shape net_shape(const mz_net* net) { return mzp_shape{net->n_hidden, net->hidden[0], net->hidden[1], net->activation}; }
-// a network the one-layer kernels evaluate: at most one hidden layer, tanh
-static bool net_shallow(const mz_net* net) { return net->n_hidden <= 1 && net->activation == MZ_ACT_TANH; }
 
 static void net_act_launch(mz_handle* h, hipStream_t st, const mz_net* actor, int sample, uint64_t noise_seed, uint64_t noise_step,
                            const float* obs_dev, float* actions_dev, float* logp_dev, int noise_mode) {
@@ -999,92 +788,6 @@ int32_t mz_net_value(mz_handle* h, const mz_net* critic, const float* obs_dev, f
   return MZ_OK;
 }
 
-// mz_rollout_actor_critic for networks described by mz_net (include/mazestep.h).  Fused handles evaluate both networks inside the
-// rollout kernels — the one-layer instantiations where both are at most one tanh hidden layer, the DEEP ones otherwise, which
-// compute the same bits for such a network, and their NRM twins for every shape while a normaliser is bound —; every other handle runs the defining loop itself: net_value_kernel, net_act_kernel,
-// the step's own launches, net_value_kernel again with the final_obs row where the env finished under auto-reset.
-// noise_mode / next_obs_seq_dev: MZ_NOISE_PRE_SQUASH / NULL from mz_rollout_net, the caller's from mz_rollout_ex, which has checked them.
-static int32_t rollout_net(mz_handle* h, int32_t n_steps, const mz_net* actor, int32_t sample, uint64_t noise_seed, uint64_t noise_step,
-                           const mz_net* critic, float* value_seq_dev, float* next_value_seq_dev, float* obs_dev, float* reward_dev,
-                           uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev, float* obs_seq_dev, float* actions_seq_dev,
-                           float* logp_seq_dev, int noise_mode, float* next_obs_seq_dev, void* stream) {
-  if (!h) return MZ_ERR_ARG;
-  if (sample != 0 && sample != 1) return set_err(h, MZ_ERR_ARG, "mz_rollout_net: sample must be 0 or 1", hipSuccess);
-  if (!obs_dev || !reward_dev || !done_dev) return set_err(h, MZ_ERR_ARG, "mz_rollout_net: null array", hipSuccess);
-  if (n_steps < 1 || n_steps > 65536) return set_err(h, MZ_ERR_ARG, "mz_rollout_net: n_steps must be 1 .. 65536", hipSuccess);
-  int rc = net_args(h, "mz_rollout_net", "actor", actor, h->model.nu, sample != 0, false);
-  if (rc != MZ_OK) return rc;
-  if (critic) {
-    rc = net_args(h, "mz_rollout_net", "critic", critic, 1, false, true);
-    if (rc != MZ_OK) return rc;
-    if (next_value_seq_dev && h->auto_reset && !h->final_obs)
-      return set_err(h, MZ_ERR_ARG, "mz_rollout_net: next_value_seq_dev under auto-reset needs a bound final_obs buffer (mz_bind_final_obs): "
-                                    "the terminal rows are valued there", hipSuccess);
-  } else {
-    value_seq_dev = next_value_seq_dev = NULL;
-  }
-  if (!sample) logp_seq_dev = NULL;
-  const size_t n = (size_t)h->n, od = (size_t)h->model.obs_dim, nu = (size_t)h->model.nu;
-  DeviceScope scope(h->device);
-  hipStream_t st = (hipStream_t)stream;
-  if (mzk_planar_rollout_fused(h)) {
-    if (!h->nrm_mean && net_shallow(actor) && (!critic || net_shallow(critic))) {
-      const float* p = actor->params_dev;
-      const long ps = (long)actor->env_stride;
-      const int H = actor->hidden[0], sq = actor->squash;
-      const float scale = (float)actor->action_scale;
-      if (critic) {
-        const mz_critic c{critic->params_dev, critic->env_stride, critic->hidden[0], 0, value_seq_dev, next_value_seq_dev};
-        HIPCHK(h, mzk_planar_rollout_actor_critic(h, st, n_steps, p, ps, H, sq, scale, sample, noise_seed, noise_step, &c, obs_dev, reward_dev, done_dev,
-                                                  goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, logp_seq_dev, noise_mode, next_obs_seq_dev));
-      } else if (sample) {
-        HIPCHK(h, mzk_planar_rollout_policy_sample(h, st, n_steps, p, ps, H, sq, scale, noise_seed, noise_step, obs_dev, reward_dev, done_dev,
-                                                   goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, logp_seq_dev, noise_mode, next_obs_seq_dev));
-      } else {
-        HIPCHK(h, mzk_planar_rollout_policy(h, st, n_steps, p, ps, H, sq, scale, obs_dev, reward_dev, done_dev, goal_idx_dev, info_dev, obs_seq_dev,
-                                            actions_seq_dev, next_obs_seq_dev));
-      }
-    } else {
-      HIPCHK(h, mzk_planar_rollout_net(h, st, n_steps, actor, sample, noise_seed, noise_step, critic, value_seq_dev, next_value_seq_dev, obs_dev,
-                                       reward_dev, done_dev, goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, logp_seq_dev, noise_mode,
-                                       next_obs_seq_dev));
-    }
-    if (h->record) {  // the last step's row
-      const size_t tot = n * (od + 2), last = (size_t)(n_steps - 1) * n;
-      hipLaunchKernelGGL(pack_record_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, h->n, h->model.obs_dim, obs_dev, reward_dev + last, done_dev + last, h->record);
-      HIPCHK(h, hipGetLastError());
-    }
-  } else {
-    if (!actions_seq_dev && !h->policy_act) HIPCHK(h, hipMalloc(&h->policy_act, n * nu * sizeof(float)));
-    for (size_t k = 0; k < (size_t)n_steps; k++) {
-      float* a = actions_seq_dev ? actions_seq_dev + k * n * nu : h->policy_act;
-      if (value_seq_dev) net_value_launch(h, st, critic, obs_dev, NULL, NULL, value_seq_dev + k * n);
-      net_act_launch(h, st, actor, sample, noise_seed, noise_step + k, obs_dev, a, logp_seq_dev ? logp_seq_dev + k * n : NULL, noise_mode);
-      HIPCHK(h, hipGetLastError());
-      rc = step_launches(h, st, a, obs_dev, reward_dev + k * n, done_dev + k * n, goal_idx_dev ? goal_idx_dev + k * n : NULL,
-                         info_dev ? info_dev + k * n * 4 : NULL);
-      if (rc != MZ_OK) return rc;
-      if (next_value_seq_dev) {
-        net_value_launch(h, st, critic, obs_dev, h->auto_reset ? h->final_obs : NULL, h->auto_reset ? done_dev + k * n : NULL,
-                         next_value_seq_dev + k * n);
-        HIPCHK(h, hipGetLastError());
-      }
-      if (next_obs_seq_dev) HIPCHK(h, next_obs_row(h, st, obs_dev, done_dev + k * n, next_obs_seq_dev + k * n * od));
-      if (obs_seq_dev) HIPCHK(h, hipMemcpyAsync(obs_seq_dev + k * n * od, obs_dev, n * od * sizeof(float), hipMemcpyDeviceToDevice, st));
-    }
-  }
-  h->nsteps += n_steps;
-  return MZ_OK;
-}
-
-int32_t mz_rollout_net(mz_handle* h, int32_t n_steps, const mz_net* actor, int32_t sample, uint64_t noise_seed, uint64_t noise_step,
-                       const mz_net* critic, float* value_seq_dev, float* next_value_seq_dev, float* obs_dev, float* reward_dev,
-                       uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev, float* obs_seq_dev, float* actions_seq_dev,
-                       float* logp_seq_dev, void* stream) {
-  return rollout_net(h, n_steps, actor, sample, noise_seed, noise_step, critic, value_seq_dev, next_value_seq_dev, obs_dev, reward_dev, done_dev,
-                     goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, logp_seq_dev, MZ_NOISE_PRE_SQUASH, NULL, stream);
-}
-
 // the checks mz_net_sample and mz_rollout_ex share; MZ_OK or MZ_ERR_ARG with the message set
 static int noise_args(mz_handle* h, const char* who, const mz_noise* noise) {
   char msg[160];
@@ -1112,8 +815,215 @@ int32_t mz_net_sample(mz_handle* h, const mz_net* actor, const mz_noise* noise, 
   return MZ_OK;
 }
 
+// ------------------------------------------------------------------ rollouts: six entries, one plan (mz_internal.h), one driver
+// row k of next_obs_seq_dev on a handle that steps launch by launch: behind the step's launches, before anything overwrites obs_dev or
+// the final_obs row (the caller has checked that final_obs is bound under auto-reset)
+static hipError_t next_obs_row(mz_handle* h, hipStream_t st, const float* obs_dev, const uint8_t* done_dev, float* out) {
+  const size_t tot = (size_t)h->n * h->model.obs_dim;
+  if (!h->auto_reset) return hipMemcpyAsync(out, obs_dev, tot * sizeof(float), hipMemcpyDeviceToDevice, st);
+  hipLaunchKernelGGL(next_obs_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, h->n, h->model.obs_dim, obs_dev, h->final_obs, done_dev, out);
+  return hipGetLastError();
+}
+
+// the plan's actor on the rows of obs_dev into `actions`, with the noise of step k: the kernels of mzk_rollout_kernels' loop column
+static void rollout_act_launch(mz_handle* h, hipStream_t st, const RolloutPlan& p, bool one_layer, size_t k, float* actions) {
+  const mz_net* a = p.actor;
+  float* logp = p.logp_seq_dev ? p.logp_seq_dev + k * (size_t)h->n : NULL;
+  if (!one_layer) net_act_launch(h, st, a, p.sample, p.noise_seed, p.noise_step + k, p.obs_dev, actions, logp, p.noise_mode);
+  else if (p.sample)
+    policy_sample_launch(h, st, a->params_dev, a->env_stride, a->hidden[0], a->squash, (float)a->action_scale, p.noise_seed, p.noise_step + k, p.obs_dev,
+                         actions, logp);
+  else policy_act_launch(h, st, a->params_dev, a->env_stride, a->hidden[0], a->squash, (float)a->action_scale, p.obs_dev, actions);
+}
+
+// the plan's critic on the rows of obs_dev — the final_obs row where done (both NULL: every row from obs_dev) — likewise
+static void rollout_value_launch(mz_handle* h, hipStream_t st, const RolloutPlan& p, bool one_layer, const float* final_obs_dev,
+                                 const uint8_t* done_dev, float* values_dev) {
+  const mz_net* c = p.critic;
+  if (one_layer) value_launch(h, st, c->params_dev, c->env_stride, c->hidden[0], p.obs_dev, final_obs_dev, done_dev, values_dev);
+  else net_value_launch(h, st, c, p.obs_dev, final_obs_dev, done_dev, values_dev);
+}
+
+// The driver behind every rollout entry: n_steps times [a = the plan's actor on obs, or row k of its action tensor]; step(a) in one
+// call (include/mazestep.h).  Fused handles (mzk_planar_rollout_fused) advance up to MZ_ROLLOUT_CHUNK steps per launch on a state that
+// stays on chip and evaluate the networks inside the kernels; the record then gets the last step's row from one launch behind them.
+// Every other handle runs the defining loop itself with the output pointers advanced, which is sequential stepping by construction:
+//   [value of obs] -> actor -> the step's own launches (mzk_view_fill among them: the view entries of both rows are in place)
+//   -> [next value: of the final_obs row where the env finished under auto-reset] -> [next_obs_row] -> [obs_seq copy]
+// with the actions in row k of actions_seq_dev, or in the handle's scratch.  Which kernels evaluate the networks: mzk_rollout_kernels.
+// The entry has checked the plan.
+static int32_t rollout_run(mz_handle* h, const RolloutPlan& plan, void* stream) {
+  RolloutPlan p = plan;
+  if (!p.critic) p.value_seq_dev = p.next_value_seq_dev = NULL;
+  if (!p.sample) p.logp_seq_dev = NULL;
+  const size_t n = (size_t)h->n, od = (size_t)h->model.obs_dim, nu = (size_t)h->model.nu;
+  DeviceScope scope(h->device);
+  hipStream_t st = (hipStream_t)stream;
+  if (mzk_planar_rollout_fused(h)) {
+    HIPCHK(h, mzk_planar_rollout(h, st, p));
+    if (h->record) {  // the last step's row
+      const size_t tot = n * (od + 2), last = (size_t)(p.n_steps - 1) * n;
+      hipLaunchKernelGGL(pack_record_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, h->n, h->model.obs_dim, p.obs_dev, p.reward_dev + last, p.done_dev + last, h->record);
+      HIPCHK(h, hipGetLastError());
+    }
+  } else {
+    const bool one_layer = mzk_rollout_kernels(h, p).one_layer;
+    if (p.actor && !p.actions_seq_dev && !h->policy_act) HIPCHK(h, hipMalloc(&h->policy_act, n * nu * sizeof(float)));
+    for (size_t k = 0; k < (size_t)p.n_steps; k++) {
+      uint8_t* done_k = p.done_dev + k * n;
+      const float* a;
+      if (p.actor) {
+        float* out = p.actions_seq_dev ? p.actions_seq_dev + k * n * nu : h->policy_act;
+        if (p.value_seq_dev) rollout_value_launch(h, st, p, one_layer, NULL, NULL, p.value_seq_dev + k * n);
+        rollout_act_launch(h, st, p, one_layer, k, out);
+        HIPCHK(h, hipGetLastError());
+        a = out;
+      } else {
+        a = p.actions_dev + k * (size_t)p.action_step_stride;
+      }
+      const int rc = step_launches(h, st, a, p.obs_dev, p.reward_dev + k * n, done_k, p.goal_idx_dev ? p.goal_idx_dev + k * n : NULL,
+                                   p.info_dev ? p.info_dev + k * n * 4 : NULL);
+      if (rc != MZ_OK) return rc;
+      if (p.next_value_seq_dev) {
+        rollout_value_launch(h, st, p, one_layer, h->auto_reset ? h->final_obs : NULL, h->auto_reset ? done_k : NULL, p.next_value_seq_dev + k * n);
+        HIPCHK(h, hipGetLastError());
+      }
+      if (p.next_obs_seq_dev) HIPCHK(h, next_obs_row(h, st, p.obs_dev, done_k, p.next_obs_seq_dev + k * n * od));
+      if (p.obs_seq_dev) HIPCHK(h, hipMemcpyAsync(p.obs_seq_dev + k * n * od, p.obs_dev, n * od * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
+  }
+  h->nsteps += p.n_steps;
+  return MZ_OK;
+}
+
+// a plan with what every entry has: its name, the step count and the outputs of mz_rollout; everything else zero
+static RolloutPlan rollout_plan(const char* who, int32_t n_steps, float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t* goal_idx_dev,
+                                float* info_dev, float* obs_seq_dev) {
+  RolloutPlan p{};
+  p.who = who; p.n_steps = n_steps; p.noise_mode = MZ_NOISE_PRE_SQUASH;
+  p.obs_dev = obs_dev; p.reward_dev = reward_dev; p.done_dev = done_dev; p.goal_idx_dev = goal_idx_dev; p.info_dev = info_dev; p.obs_seq_dev = obs_seq_dev;
+  return p;
+}
+
+// the two checks every entry makes, each at its own place among the entry's other checks — the first message of a refused call is
+// part of the interface —, under the name of the entry the call stands for
+static int rollout_args(mz_handle* h, const RolloutPlan& p) {
+  char msg[96];
+  const char* why = nullptr;
+  if (!p.obs_dev || !p.reward_dev || !p.done_dev) why = "null array";
+  else if (p.n_steps < 1 || p.n_steps > 65536) why = "n_steps must be 1 .. 65536";
+  if (!why) return MZ_OK;
+  snprintf(msg, sizeof(msg), "%s: %s", p.who, why);
+  return set_err(h, MZ_ERR_ARG, msg, hipSuccess);
+}
+
+// what mz_rollout refuses, on its plan (mz_rollout_ex with a tensor of actions stands for it)
+static int open_loop_args(mz_handle* h, const RolloutPlan& p) {
+  if (!p.actions_dev) return set_err(h, MZ_ERR_ARG, "mz_rollout: null array", hipSuccess);
+  const int rc = rollout_args(h, p);
+  if (rc != MZ_OK) return rc;
+  if (p.action_step_stride != 0 && p.action_step_stride != (long)h->n * h->model.nu)
+    return set_err(h, MZ_ERR_ARG, "mz_rollout: action_step_stride must be num_envs * nu ([K, N, nu] actions) or 0 (one [N, nu] block repeated)", hipSuccess);
+  return MZ_OK;
+}
+
+// what mz_rollout_net refuses, on its plan (mz_rollout_ex with an actor stands for it)
+static int net_rollout_args(mz_handle* h, const RolloutPlan& p) {
+  if (p.sample != 0 && p.sample != 1) return set_err(h, MZ_ERR_ARG, "mz_rollout_net: sample must be 0 or 1", hipSuccess);
+  int rc = rollout_args(h, p);
+  if (rc != MZ_OK) return rc;
+  rc = net_args(h, "mz_rollout_net", "actor", p.actor, h->model.nu, p.sample != 0, false);
+  if (rc != MZ_OK || !p.critic) return rc;
+  rc = net_args(h, "mz_rollout_net", "critic", p.critic, 1, false, true);
+  if (rc != MZ_OK) return rc;
+  if (p.next_value_seq_dev && h->auto_reset && !h->final_obs)
+    return set_err(h, MZ_ERR_ARG, "mz_rollout_net: next_value_seq_dev under auto-reset needs a bound final_obs buffer (mz_bind_final_obs): "
+                                  "the terminal rows are valued there", hipSuccess);
+  return MZ_OK;
+}
+
+// The three entries that take an int `hidden`: their checks under the name `who`, then the plan with both networks as legacy_net's.
+// mz_rollout_policy is sample = 0 without a critic, mz_rollout_policy_sample sample = 1 without one.
+static int32_t rollout_legacy(mz_handle* h, const char* who, int32_t n_steps, const float* params_dev, int64_t param_env_stride, int32_t hidden,
+                              int32_t squash, double action_scale, int32_t sample, uint64_t noise_seed, uint64_t noise_step, const mz_critic* critic,
+                              float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev, float* obs_seq_dev,
+                              float* actions_seq_dev, float* logp_seq_dev, void* stream) {
+  RolloutPlan p = rollout_plan(who, n_steps, obs_dev, reward_dev, done_dev, goal_idx_dev, info_dev, obs_seq_dev);
+  int rc = rollout_args(h, p);
+  if (rc != MZ_OK) return rc;
+  rc = policy_args(h, who, params_dev, param_env_stride, hidden, squash, sample != 0);
+  if (rc != MZ_OK) return rc;
+  const mz_net a = legacy_net(params_dev, param_env_stride, hidden, squash, action_scale);
+  mz_net c{};
+  if (critic) {
+    if (critic->reserved != 0) return set_err(h, MZ_ERR_ARG, "mz_rollout_actor_critic: critic->reserved must be 0", hipSuccess);
+    rc = critic_args(h, who, critic->params_dev, critic->env_stride, critic->hidden);
+    if (rc != MZ_OK) return rc;
+    if (critic->next_value_seq_dev && h->auto_reset && !h->final_obs)
+      return set_err(h, MZ_ERR_ARG, "mz_rollout_actor_critic: critic->next_value_seq_dev under auto-reset needs a bound final_obs buffer "
+                                    "(mz_bind_final_obs): the terminal rows are valued there", hipSuccess);
+    c = legacy_net(critic->params_dev, critic->env_stride, critic->hidden, 0, 1.0);
+    p.critic = &c; p.value_seq_dev = critic->value_seq_dev; p.next_value_seq_dev = critic->next_value_seq_dev;
+  }
+  p.legacy = 1;
+  p.actor = &a; p.sample = sample; p.noise_seed = noise_seed; p.noise_step = noise_step;
+  p.actions_seq_dev = actions_seq_dev; p.logp_seq_dev = logp_seq_dev;
+  return rollout_run(h, p, stream);
+}
+
+int32_t mz_rollout(mz_handle* h, int32_t n_steps, const float* actions_dev, int64_t action_step_stride, float* obs_dev, float* reward_dev,
+                   uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev, float* obs_seq_dev, void* stream) {
+  if (!h) return MZ_ERR_ARG;
+  RolloutPlan p = rollout_plan("mz_rollout", n_steps, obs_dev, reward_dev, done_dev, goal_idx_dev, info_dev, obs_seq_dev);
+  p.actions_dev = actions_dev; p.action_step_stride = (long)action_step_stride;
+  const int rc = open_loop_args(h, p);
+  return rc != MZ_OK ? rc : rollout_run(h, p, stream);
+}
+
+int32_t mz_rollout_policy(mz_handle* h, int32_t n_steps, const float* params_dev, int64_t param_env_stride, int32_t hidden, int32_t squash,
+                          double action_scale, float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev,
+                          float* obs_seq_dev, float* actions_seq_dev, void* stream) {
+  if (!h) return MZ_ERR_ARG;
+  return rollout_legacy(h, "mz_rollout_policy", n_steps, params_dev, param_env_stride, hidden, squash, action_scale, 0, 0, 0, NULL, obs_dev, reward_dev,
+                        done_dev, goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, NULL, stream);
+}
+
+int32_t mz_rollout_policy_sample(mz_handle* h, int32_t n_steps, const float* params_dev, int64_t param_env_stride, int32_t hidden, int32_t squash,
+                                 double action_scale, uint64_t noise_seed, uint64_t noise_step, float* obs_dev, float* reward_dev,
+                                 uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev, float* obs_seq_dev, float* actions_seq_dev,
+                                 float* logp_seq_dev, void* stream) {
+  if (!h) return MZ_ERR_ARG;
+  return rollout_legacy(h, "mz_rollout_policy_sample", n_steps, params_dev, param_env_stride, hidden, squash, action_scale, 1, noise_seed, noise_step,
+                        NULL, obs_dev, reward_dev, done_dev, goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, logp_seq_dev, stream);
+}
+
+// without a critic the call IS mz_rollout_policy_sample / mz_rollout_policy (include/mazestep.h), down to the name in a refusal
+int32_t mz_rollout_actor_critic(mz_handle* h, int32_t n_steps, const float* params_dev, int64_t param_env_stride, int32_t hidden, int32_t squash,
+                                double action_scale, int32_t sample, uint64_t noise_seed, uint64_t noise_step, const mz_critic* critic,
+                                float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev, float* obs_seq_dev,
+                                float* actions_seq_dev, float* logp_seq_dev, void* stream) {
+  if (!h) return MZ_ERR_ARG;
+  if (sample != 0 && sample != 1) return set_err(h, MZ_ERR_ARG, "mz_rollout_actor_critic: sample must be 0 or 1", hipSuccess);
+  const char* who = critic ? "mz_rollout_actor_critic" : (sample ? "mz_rollout_policy_sample" : "mz_rollout_policy");
+  return rollout_legacy(h, who, n_steps, params_dev, param_env_stride, hidden, squash, action_scale, sample, noise_seed, noise_step, critic, obs_dev,
+                        reward_dev, done_dev, goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, logp_seq_dev, stream);
+}
+
+int32_t mz_rollout_net(mz_handle* h, int32_t n_steps, const mz_net* actor, int32_t sample, uint64_t noise_seed, uint64_t noise_step,
+                       const mz_net* critic, float* value_seq_dev, float* next_value_seq_dev, float* obs_dev, float* reward_dev,
+                       uint8_t* done_dev, int32_t* goal_idx_dev, float* info_dev, float* obs_seq_dev, float* actions_seq_dev,
+                       float* logp_seq_dev, void* stream) {
+  if (!h) return MZ_ERR_ARG;
+  RolloutPlan p = rollout_plan("mz_rollout_net", n_steps, obs_dev, reward_dev, done_dev, goal_idx_dev, info_dev, obs_seq_dev);
+  p.actor = actor; p.sample = sample; p.noise_seed = noise_seed; p.noise_step = noise_step;
+  p.critic = critic; p.value_seq_dev = value_seq_dev; p.next_value_seq_dev = next_value_seq_dev;
+  p.actions_seq_dev = actions_seq_dev; p.logp_seq_dev = logp_seq_dev;
+  const int rc = net_rollout_args(h, p);
+  return rc != MZ_OK ? rc : rollout_run(h, p, stream);
+}
+
 // mz_rollout / mz_rollout_net behind one struct, with the per-step pre-reset rows and the noise mode (include/mazestep.h).  The
-// checks here are those the struct adds; everything else is refused by the entry the call stands for, whose launches it runs.
+// checks here are those the struct adds; everything else is refused as by the entry the call stands for, whose plan it fills.
 int32_t mz_rollout_ex(mz_handle* h, const mz_rollout_io* io, void* stream) {
   if (!h) return MZ_ERR_ARG;
   if (!io) return set_err(h, MZ_ERR_ARG, "mz_rollout_ex: io is NULL", hipSuccess);
@@ -1131,13 +1041,18 @@ int32_t mz_rollout_ex(mz_handle* h, const mz_rollout_io* io, void* stream) {
   if (io->next_obs_seq_dev && h->auto_reset && !h->final_obs)
     return set_err(h, MZ_ERR_ARG, "mz_rollout_ex: next_obs_seq_dev under auto-reset needs a bound final_obs buffer (mz_bind_final_obs): "
                                   "the contract is the same on every handle", hipSuccess);
-  if (!io->actor)
-    return rollout_open(h, io->n_steps, io->actions_dev, io->action_step_stride, io->obs_dev, io->reward_dev, io->done_dev, io->goal_idx_dev,
-                        io->info_dev, io->obs_seq_dev, io->next_obs_seq_dev, stream);
-  return rollout_net(h, io->n_steps, io->actor, io->noise ? 1 : 0, io->noise ? io->noise->seed : 0, io->noise ? io->noise->step : 0, io->critic,
-                     io->value_seq_dev, io->next_value_seq_dev, io->obs_dev, io->reward_dev, io->done_dev, io->goal_idx_dev, io->info_dev,
-                     io->obs_seq_dev, io->actions_seq_dev, io->logp_seq_dev, io->noise ? io->noise->mode : MZ_NOISE_PRE_SQUASH, io->next_obs_seq_dev,
-                     stream);
+  RolloutPlan p = rollout_plan(io->actor ? "mz_rollout_net" : "mz_rollout", io->n_steps, io->obs_dev, io->reward_dev, io->done_dev, io->goal_idx_dev,
+                               io->info_dev, io->obs_seq_dev);
+  p.next_obs_seq_dev = io->next_obs_seq_dev;
+  if (!io->actor) {
+    p.actions_dev = io->actions_dev; p.action_step_stride = (long)io->action_step_stride;
+  } else {
+    p.actor = io->actor; p.critic = io->critic; p.value_seq_dev = io->value_seq_dev; p.next_value_seq_dev = io->next_value_seq_dev;
+    p.actions_seq_dev = io->actions_seq_dev; p.logp_seq_dev = io->logp_seq_dev;
+    if (io->noise) { p.sample = 1; p.noise_seed = io->noise->seed; p.noise_step = io->noise->step; p.noise_mode = io->noise->mode; }
+  }
+  const int rc = io->actor ? net_rollout_args(h, p) : open_loop_args(h, p);
+  return rc != MZ_OK ? rc : rollout_run(h, p, stream);
 }
 
 int32_t mz_gae(mz_handle* h, int32_t n_steps, const float* reward_dev, const uint8_t* done_dev, const float* value_dev,

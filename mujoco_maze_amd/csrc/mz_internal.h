@@ -93,34 +93,56 @@ hipError_t mzk_view_fill(mz_handle* h, hipStream_t st, float* obs, float* final_
 // MZ_ROLLOUT_CHUNK steps, which bounds a kernel's duration
 constexpr int MZ_ROLLOUT_CHUNK = 256;
 int mzk_planar_rollout_fused(const mz_handle* h);
-// the trailing arguments of the five launchers below serve mz_rollout_ex alone: next_obs_seq [nsteps][n][obs_dim] (nullable) gets the
-// raw row every step produced, before any auto-reset, from inside the kernels; noise_mode: MZ_NOISE_* of the sampled actions
-hipError_t mzk_planar_rollout(mz_handle* h, hipStream_t st, int nsteps, const float* actions, long astride, float* obs, float* reward,
-                              uint8_t* done, int* goal_idx, float* info, float* obs_seq, float* next_obs_seq = nullptr);
-// mz_rollout_policy on the same handles, with the same launch geometry and split: the policy of csrc/mz_policy.h (params: [npar], or
-// [n][npar] with pstride = npar) is evaluated between two steps on the observation row on chip; every launch writes obs at its last step
-hipError_t mzk_planar_rollout_policy(mz_handle* h, hipStream_t st, int nsteps, const float* params, long pstride, int hidden, int squash,
-                                     float action_scale, float* obs, float* reward, uint8_t* done, int* goal_idx, float* info, float* obs_seq,
-                                     float* actions_seq, float* next_obs_seq = nullptr);
-// mz_rollout_policy_sample on the same handles: the same launches, every step's actions drawn from the policy's Gaussian with the
-// noise of (noise_seed, noise_step + k); logp_seq [nsteps][n] nullable
-hipError_t mzk_planar_rollout_policy_sample(mz_handle* h, hipStream_t st, int nsteps, const float* params, long pstride, int hidden, int squash,
-                                            float action_scale, uint64_t noise_seed, uint64_t noise_step, float* obs, float* reward, uint8_t* done,
-                                            int* goal_idx, float* info, float* obs_seq, float* actions_seq, float* logp_seq,
-                                            int noise_mode = MZ_NOISE_PRE_SQUASH, float* next_obs_seq = nullptr);
-// mz_rollout_actor_critic with a critic on the same handles: the same launches (sample: the Gaussian policy), the critic of `critic`
-// (checked by the caller) evaluated on the on-chip row at every step and on the terminal row before an auto-reset overwrites it
-hipError_t mzk_planar_rollout_actor_critic(mz_handle* h, hipStream_t st, int nsteps, const float* params, long pstride, int hidden, int squash,
-                                           float action_scale, int sample, uint64_t noise_seed, uint64_t noise_step, const mz_critic* critic,
-                                           float* obs, float* reward, uint8_t* done, int* goal_idx, float* info, float* obs_seq, float* actions_seq,
-                                           float* logp_seq, int noise_mode = MZ_NOISE_PRE_SQUASH, float* next_obs_seq = nullptr);
-// mz_rollout_net on the same handles where a network has two hidden layers or ReLU units: the same launches of the kernels' DEEP
-// instantiations, which evaluate networks of every shape mz_net describes (`actor`, `critic` — nullable — checked by the caller);
-// with a normaliser bound (h->nrm_mean) their NRM twins, for every shape
-hipError_t mzk_planar_rollout_net(mz_handle* h, hipStream_t st, int nsteps, const mz_net* actor, int sample, uint64_t noise_seed,
-                                  uint64_t noise_step, const mz_net* critic, float* value_seq, float* next_value_seq, float* obs, float* reward,
-                                  uint8_t* done, int* goal_idx, float* info, float* obs_seq, float* actions_seq, float* logp_seq,
-                                  int noise_mode = MZ_NOISE_PRE_SQUASH, float* next_obs_seq = nullptr);
+
+// One rollout call, whichever entry of include/mazestep.h it came through (mz_rollout, mz_rollout_policy, mz_rollout_policy_sample,
+// mz_rollout_actor_critic, mz_rollout_net, mz_rollout_ex).  The entry checks its arguments and fills a plan; rollout_run (mazestep.hip)
+// is the one driver that executes it, and mzk_planar_rollout below the one launcher of the fused kernels.  Arrays as in mz_rollout_io.
+struct RolloutPlan {
+  const char* who;  // the entry the call stands for: the name in the messages of a refusal
+  int n_steps;
+  // the action source: a tensor ..
+  const float* actions_dev;
+  long action_step_stride;
+  // .. or an actor (sample: drawn from its Gaussian with the noise of (noise_seed, noise_step + k), formed in noise_mode = MZ_NOISE_*)
+  const mz_net* actor;
+  int sample;
+  uint64_t noise_seed, noise_step;
+  int noise_mode;
+  // an optional critic beside the actor; the two sequences are not read without one
+  const mz_net* critic;
+  float *value_seq_dev, *next_value_seq_dev;
+  // the call came through an entry that takes an int `hidden` (the networks are then legacy_net's, mazestep.hip)
+  int legacy;
+  // outputs: obs, reward, done required; logp_seq is not read unless sample
+  float *obs_dev, *reward_dev;
+  uint8_t* done_dev;
+  int32_t* goal_idx_dev;
+  float *info_dev, *obs_seq_dev, *actions_seq_dev, *logp_seq_dev, *next_obs_seq_dev;
+};
+
+// The kernels a closed-loop plan runs: what every entry launched before there was a plan, and what it must go on launching.
+//
+//   call                                               | launch-by-launch loop                     | fused (Point / Swimmer without view)
+//   ---------------------------------------------------+-------------------------------------------+-------------------------------------
+//   legacy entry, no normaliser bound                  | policy_act_kernel / policy_sample_kernel  | non-DEEP instantiations
+//                                                      |   / value_kernel              (one_layer) |
+//   mz_rollout_net / mz_rollout_ex, both nets at most  | net_act_kernel<false>                     | non-DEEP instantiations
+//     one tanh hidden layer, no normaliser             |   / net_value_kernel<false>               |
+//   any other shape, no normaliser                     | the same net kernels                      | DEEP
+//   normaliser bound (any entry)                       | net_*_kernel<true>                        | DEEP + NRM
+//
+// EXT exactly when next_obs_seq is given or a sampled call uses MZ_NOISE_ACTION; an open-loop plan reads `ext` alone.
+struct RolloutKernels { bool one_layer, deep, nrm, ext; };
+inline RolloutKernels mzk_rollout_kernels(const mz_handle* h, const RolloutPlan& p) {
+  auto shallow = [](const mz_net* net) { return !net || (net->n_hidden <= 1 && net->activation == MZ_ACT_TANH); };
+  const bool nrm = h->nrm_mean != nullptr;
+  return RolloutKernels{p.legacy && !nrm, nrm || !shallow(p.actor) || !shallow(p.critic), nrm,
+                        p.next_obs_seq_dev || (p.sample && p.noise_mode != MZ_NOISE_PRE_SQUASH)};
+}
+// the plan on the fused kernels: launches of at most MZ_ROLLOUT_CHUNK steps with the launch geometry and the instantiation of the step
+// kernel they stand for — the open-loop kernels for a tensor of actions, else the policy kernels' SMP / CRT / DEEP / NRM / EXT
+// instantiation of mzk_rollout_kernels; every launch writes obs at its last step.  The caller has checked the plan.
+hipError_t mzk_planar_rollout(mz_handle* h, hipStream_t st, const RolloutPlan& p);
 int mzk_planar_state_width(const mz_handle* h);  // coordinates per env of the state (NV)
 int mzk_planar_record_width(const mz_handle* h); // Point: floats per env-major record; 0 for the chains (SoA)
 

@@ -21,6 +21,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "mz_task.h"
 #include "point_dyn.h"
 #include "planar_dyn.h"
@@ -900,50 +902,67 @@ int mzk_planar_lanes(const mz_handle* h) {
   return (lanes == 8 || lanes == 16) ? lanes : 32;
 }
 
+// ---- the handle-to-instantiation ladder, once: the step, both rollout kernels and the reset launch what it picks, so a rollout
+// cannot run another instantiation than the step it claims to equal.  f gets the template arguments as std::integral_constant's.
+template <int V> using ic = std::integral_constant<int, V>;
+
+// Swimmer / Reacher: f(NL, NB, G) — NL links, NB the movable block's degrees of freedom (0: none), G = 4 lanes per env up to four
+// links, else 8 (mzk_planar_lanes)
+template <class F>
+static void swimmer_ladder(const mz_handle* h, F&& f) {
+  const int bd = h->swimmer.nblock ? h->swimmer.nbdof : 0;
+  if (h->swimmer.nlink == 3) { if (bd == 3) f(ic<3>{}, ic<3>{}, ic<4>{}); else if (bd == 2) f(ic<3>{}, ic<2>{}, ic<4>{}); else f(ic<3>{}, ic<0>{}, ic<4>{}); }
+  else if (h->swimmer.nlink == 2) { if (bd == 3) f(ic<2>{}, ic<3>{}, ic<4>{}); else if (bd == 2) f(ic<2>{}, ic<2>{}, ic<4>{}); else f(ic<2>{}, ic<0>{}, ic<4>{}); }
+  else if (h->swimmer.nlink == 4) f(ic<4>{}, ic<0>{}, ic<4>{});  // longer chains (user MJCF): no movable blocks
+  else if (h->swimmer.nlink == 5) f(ic<5>{}, ic<0>{}, ic<8>{});
+  else f(ic<6>{}, ic<0>{}, ic<8>{});
+}
+// the Swimmer kernels' launch geometry: workgroups of `waves_per_block` waves (option; default 4), G lanes per env
+static unsigned swimmer_block(const mz_handle* h) { return 64u * (unsigned)(h->wpb_set ? h->waves_per_block : 4); }
+static dim3 swimmer_grid(const mz_handle* h, int G) { return dim3((unsigned)(((size_t)h->n * G + swimmer_block(h) - 1) / swimmer_block(h))); }
+
+// Point: f(NB, NS, G) — NB movable blocks or NS object balls, G lanes per env.
+// Lanes per env: 32 for the bare robot — its 18 collision enumerators then share one round, and 4096 envs make two waves per
+// SIMD: a wave runs as long as the slowest of its envs (only envs at a wall enumerate, fill and iterate), so two envs per wave
+// and a second wave to fill the gaps beat four envs per wave (measured, round 3: 34.8 vs 31.6 M env-steps/s on PointUMaze) —
+// 32 / 64 with blocks (bigger contact sets in LDS).
+// Round 5: 16 lanes per env by default while that still gives every wave a SIMD of its own (up to 4096 envs on a 256-CU device).
+// Round 3 measured the opposite (34.8 against 31.6 M at 32 lanes: two envs per wave and a second wave to fill the gaps); with
+// the step in registers (point_bare.h) and the unit-step solver the waves are short and even enough that four envs per wave on
+// a SIMD of their own win: PointUMaze 4096 envs 74.3 -> 79.6 M env-steps/s, Point4Rooms 79.6 -> 82.6 M; beyond (8192 envs:
+// 108.0 at 32 lanes against 106.3) it stays at 32 (profiles/r05/point_knobs.txt).
+template <class F>
+static void point_ladder(const mz_handle* h, F&& f) {
+  if (h->point.nball) f(ic<0>{}, ic<1>{}, ic<32>{});
+  else switch (h->point.nblock) {
+    case 0: {
+      const int lanes = mzk_planar_lanes(h);
+      if (lanes == 8) f(ic<0>{}, ic<0>{}, ic<8>{});
+      else if (lanes == 16) f(ic<0>{}, ic<0>{}, ic<16>{});
+      else f(ic<0>{}, ic<0>{}, ic<32>{});
+      break;
+    }
+    case 1: f(ic<1>{}, ic<0>{}, ic<32>{}); break;
+    case 2: f(ic<2>{}, ic<0>{}, ic<64>{}); break;
+    default: f(ic<3>{}, ic<0>{}, ic<64>{}); break;
+  }
+}
+// the Point kernels' launch geometry: one wave per workgroup, 64 / G envs in it
+static dim3 point_grid(const mz_handle* h, int G) { return dim3((h->n + 64 / G - 1) / (64 / G)); }
+
 hipError_t mzk_planar_step(mz_handle* h, hipStream_t st, const float* actions_dev, float* obs_dev, float* reward_dev, uint8_t* done_dev,
                            int* goal_idx_dev, float* info_dev) {
   PointState S{h->state, h->pt_t, h->pt_ep, h->pt_rec};
-  if (h->robot == MZ_ROBOT_SWIMMER) {
-#define MZ_SW_STEP(NL, NB)                                                                                                          \
-  hipLaunchKernelGGL((swimmer_step_kernel<NL, NB, (NL <= 4 ? 4 : 8)>), dim3((unsigned)(((size_t)h->n * (NL <= 4 ? 4 : 8) + sw_bd - 1) / sw_bd)), dim3(sw_bd), 0, st, \
-                     h->swimmer_dev, h->n, S, actions_dev, obs_dev, reward_dev, done_dev, goal_idx_dev, info_dev, h->status, h->auto_reset, h->seed,    \
-                     h->env0, h->final_obs, h->model.obs_dim)
-    const int bd = h->swimmer.nblock ? h->swimmer.nbdof : 0;
-    const unsigned sw_bd = 64u * (unsigned)(h->wpb_set ? h->waves_per_block : 4);  // workgroup size (option "waves_per_block")
-    if (h->swimmer.nlink == 3) { if (bd == 3) MZ_SW_STEP(3, 3); else if (bd == 2) MZ_SW_STEP(3, 2); else MZ_SW_STEP(3, 0); }
-    else if (h->swimmer.nlink == 2) { if (bd == 3) MZ_SW_STEP(2, 3); else if (bd == 2) MZ_SW_STEP(2, 2); else MZ_SW_STEP(2, 0); }
-    else if (h->swimmer.nlink == 4) MZ_SW_STEP(4, 0);  // longer chains (user MJCF): no movable blocks
-    else if (h->swimmer.nlink == 5) MZ_SW_STEP(5, 0);
-    else MZ_SW_STEP(6, 0);
-#undef MZ_SW_STEP
-    return hipGetLastError();
-  }
-  // lanes per env: 32 for the bare robot — its 18 collision enumerators then share one round, and 4096 envs make two waves per
-  // SIMD: a wave runs as long as the slowest of its envs (only envs at a wall enumerate, fill and iterate), so two envs per wave
-  // and a second wave to fill the gaps beat four envs per wave (measured, round 3: 34.8 vs 31.6 M env-steps/s on PointUMaze) —
-  // 32 / 64 with blocks (bigger contact sets in LDS)
-#define MZ_PLANAR_LAUNCH(NB, NS, G)                                                                                                    \
-  hipLaunchKernelGGL((planar_step_kernel<NB, NS, G>), dim3((h->n + 64 / G - 1) / (64 / G)), dim3(64), 0, st, h->point_dev, h->n, S, actions_dev, \
-                     obs_dev, reward_dev, done_dev, goal_idx_dev, info_dev, h->status, h->auto_reset, h->seed, h->env0, h->final_obs, h->model.obs_dim)
-  if (h->point.nball) MZ_PLANAR_LAUNCH(0, 1, 32);
-  else switch (h->point.nblock) {
-    case 0: {
-      // Round 5: 16 lanes per env by default while that still gives every wave a SIMD of its own (up to 4096 envs on a 256-CU device).
-      // Round 3 measured the opposite (34.8 against 31.6 M at 32 lanes: two envs per wave and a second wave to fill the gaps); with
-      // the step in registers (point_bare.h) and the unit-step solver the waves are short and even enough that four envs per wave on
-      // a SIMD of their own win: PointUMaze 4096 envs 74.3 -> 79.6 M env-steps/s, Point4Rooms 79.6 -> 82.6 M; beyond (8192 envs:
-      // 108.0 at 32 lanes against 106.3) it stays at 32 (profiles/r05/point_knobs.txt).
-      const int lanes = mzk_planar_lanes(h);
-      if (lanes == 8) MZ_PLANAR_LAUNCH(0, 0, 8);
-      else if (lanes == 16) MZ_PLANAR_LAUNCH(0, 0, 16);
-      else MZ_PLANAR_LAUNCH(0, 0, 32);
-      break;
-    }
-    case 1: MZ_PLANAR_LAUNCH(1, 0, 32); break;
-    case 2: MZ_PLANAR_LAUNCH(2, 0, 64); break;
-    default: MZ_PLANAR_LAUNCH(3, 0, 64); break;
-  }
-#undef MZ_PLANAR_LAUNCH
+  if (h->robot == MZ_ROBOT_SWIMMER)
+    swimmer_ladder(h, [&](auto NL, auto NB, auto G) {
+      hipLaunchKernelGGL((swimmer_step_kernel<NL, NB, G>), swimmer_grid(h, G), dim3(swimmer_block(h)), 0, st, h->swimmer_dev, h->n, S, actions_dev, obs_dev,
+                         reward_dev, done_dev, goal_idx_dev, info_dev, h->status, h->auto_reset, h->seed, h->env0, h->final_obs, h->model.obs_dim);
+    });
+  else
+    point_ladder(h, [&](auto NB, auto NS, auto G) {
+      hipLaunchKernelGGL((planar_step_kernel<NB, NS, G>), point_grid(h, G), dim3(64), 0, st, h->point_dev, h->n, S, actions_dev, obs_dev, reward_dev,
+                         done_dev, goal_idx_dev, info_dev, h->status, h->auto_reset, h->seed, h->env0, h->final_obs, h->model.obs_dim);
+    });
   return hipGetLastError();
 }
 
@@ -953,128 +972,78 @@ int mzk_planar_rollout_fused(const mz_handle* h) {
   return (h->robot == MZ_ROBOT_POINT || h->robot == MZ_ROBOT_SWIMMER) && !h->view.on;
 }
 
-// steps k = 0 .. nsteps - 1 of a rollout in launches of at most MZ_ROLLOUT_CHUNK steps, each with the launch geometry of the step
-// kernel it stands for; arrays as in mz_rollout (include/mazestep.h)
-hipError_t mzk_planar_rollout(mz_handle* h, hipStream_t st, int nsteps, const float* actions_dev, long astride, float* obs_dev, float* reward_dev,
-                              uint8_t* done_dev, int* goal_idx_dev, float* info_dev, float* obs_seq_dev, float* next_obs_seq_dev) {
-  PointState S{h->state, h->pt_t, h->pt_ep, h->pt_rec};
-  const size_t n = (size_t)h->n, od = (size_t)h->model.obs_dim;
-  for (int k0 = 0; k0 < nsteps; k0 += MZ_ROLLOUT_CHUNK) {
-    const int ks = nsteps - k0 < MZ_ROLLOUT_CHUNK ? nsteps - k0 : MZ_ROLLOUT_CHUNK;
-    const int last = k0 + ks == nsteps ? ks - 1 : -1;  // the launch that holds the rollout's last step writes obs_dev
-    const float* act = actions_dev + (size_t)k0 * astride;
-    float* rew = reward_dev + k0 * n;
-    uint8_t* dn = done_dev + k0 * n;
-    int* gi = goal_idx_dev ? goal_idx_dev + k0 * n : nullptr;
-    float* inf = info_dev ? info_dev + k0 * n * 4 : nullptr;
-    float* oseq = obs_seq_dev ? obs_seq_dev + k0 * n * od : nullptr;
-    float* nseq = next_obs_seq_dev ? next_obs_seq_dev + k0 * n * od : nullptr;  // this launch writes rows k0 .. k0 + ks - 1
-    if (h->robot == MZ_ROBOT_SWIMMER) {
-#define MZ_SW_ROLL(NL, NB) do { if (nseq) MZ_SW_ROLL_(NL, NB, true); else MZ_SW_ROLL_(NL, NB, false); } while (0)
-#define MZ_SW_ROLL_(NL, NB, EXT)                                                                                                    \
-  hipLaunchKernelGGL((swimmer_rollout_kernel<NL, NB, (NL <= 4 ? 4 : 8), EXT>), dim3((unsigned)((n * (NL <= 4 ? 4 : 8) + sw_bd - 1) / sw_bd)), dim3(sw_bd), 0, st, \
-                     h->swimmer_dev, h->n, S, ks, act, astride, obs_dev, last, rew, dn, gi, inf, oseq, h->status, h->auto_reset, h->seed, h->env0, h->final_obs, nseq)
-      const int bd = h->swimmer.nblock ? h->swimmer.nbdof : 0;
-      const unsigned sw_bd = 64u * (unsigned)(h->wpb_set ? h->waves_per_block : 4);
-      if (h->swimmer.nlink == 3) { if (bd == 3) MZ_SW_ROLL(3, 3); else if (bd == 2) MZ_SW_ROLL(3, 2); else MZ_SW_ROLL(3, 0); }
-      else if (h->swimmer.nlink == 2) { if (bd == 3) MZ_SW_ROLL(2, 3); else if (bd == 2) MZ_SW_ROLL(2, 2); else MZ_SW_ROLL(2, 0); }
-      else if (h->swimmer.nlink == 4) MZ_SW_ROLL(4, 0);
-      else if (h->swimmer.nlink == 5) MZ_SW_ROLL(5, 0);
-      else MZ_SW_ROLL(6, 0);
-#undef MZ_SW_ROLL
-#undef MZ_SW_ROLL_
-    } else {
-#define MZ_PLANAR_ROLL(NB, NS, G) do { if (nseq) MZ_PLANAR_ROLL_(NB, NS, G, true); else MZ_PLANAR_ROLL_(NB, NS, G, false); } while (0)
-#define MZ_PLANAR_ROLL_(NB, NS, G, EXT)                                                                                                \
-  hipLaunchKernelGGL((planar_rollout_kernel<NB, NS, G, EXT>), dim3((h->n + 64 / G - 1) / (64 / G)), dim3(64), 0, st, h->point_dev, h->n, S, ks, act, astride, \
-                     obs_dev, last, rew, dn, gi, inf, oseq, h->status, h->auto_reset, h->seed, h->env0, h->final_obs, nseq)
-      if (h->point.nball) MZ_PLANAR_ROLL(0, 1, 32);
-      else switch (h->point.nblock) {
-        case 0: {
-          const int lanes = mzk_planar_lanes(h);  // the step's rule
-          if (lanes == 8) MZ_PLANAR_ROLL(0, 0, 8);
-          else if (lanes == 16) MZ_PLANAR_ROLL(0, 0, 16);
-          else MZ_PLANAR_ROLL(0, 0, 32);
-          break;
-        }
-        case 1: MZ_PLANAR_ROLL(1, 0, 32); break;
-        case 2: MZ_PLANAR_ROLL(2, 0, 64); break;
-        default: MZ_PLANAR_ROLL(3, 0, 64); break;
-      }
-#undef MZ_PLANAR_ROLL
-#undef MZ_PLANAR_ROLL_
-    }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+// f(std::bool_constant's) for run-time flags: the run-time to template switch of the rollout kernels' flags, once
+template <class F>
+static hipError_t flag_switch(F&& f) { return f(); }
+template <class F, class... Rest>
+static hipError_t flag_switch(F&& f, bool flag, Rest... rest) {
+  auto with = [&](auto B) { return flag_switch([&](auto... r) { return f(B, r...); }, rest...); };
+  return flag ? with(std::true_type{}) : with(std::false_type{});
 }
 
-// mz_rollout_policy (SMP false) / mz_rollout_policy_sample (SMP true: `noise` holds the call's seed, first step and logp_seq) on
-// the fused handles: mzk_planar_rollout's launches with the policy in place of the action tensor.  Every launch writes obs_dev at
-// its last step, and the next one reads its first observation there — and continues at noise_step + the steps done so far.
-// CRT (mz_rollout_actor_critic with a critic): `critic` holds the critic's parameters and the call's value_seq / next_value_seq.
-// DEEP (mz_rollout_net with a network of two hidden layers or ReLU units): `shapes` holds both networks' shapes.
-// NRM (DEEP with a normaliser bound): the kernels' NRM instantiations, with the handle's normaliser.
-// next_obs_seq_dev / noise.mode (mz_rollout_ex): see `ext` below.
-template <bool SMP, bool CRT = false, bool DEEP = false, bool NRM = false>
-static hipError_t planar_rollout_policy_launches(mz_handle* h, hipStream_t st, int nsteps, const float* params_dev, long pstride, int hidden,
-                                                 int squash, float action_scale, float* obs_dev, float* reward_dev, uint8_t* done_dev,
-                                                 int* goal_idx_dev, float* info_dev, float* obs_seq_dev, float* actions_seq_dev, PolicyNoise noise,
-                                                 PolicyCritic critic = PolicyCritic{nullptr, 0, 0, nullptr, nullptr},
-                                                 PolicyShapes shapes = PolicyShapes{{0, 0, 0, 0}, {0, 0, 0, 0}}, float* next_obs_seq_dev = nullptr) {
+// Steps k = 0 .. n_steps - 1 of a plan in launches of at most MZ_ROLLOUT_CHUNK steps, each with the launch geometry and the
+// instantiation of the step kernel it stands for, every array advanced to the launch's first step; arrays as in mz_rollout_io.
+// POL false: the open-loop kernels on the plan's action tensor (EXT alone is read); the launch that holds the rollout's last step writes
+// obs_dev.  POL true: the policy kernels.  Every launch writes obs_dev at its last step, and the next one reads its first observation
+// there — and continues at noise_step + the steps done so far.  What the kernels get of the plan's networks:
+//   SMP   ns: the call's seed, the launch's first noise step, its logp rows and the noise mode (else zeros);
+//   CRT   cr: the critic's parameters and the launch's value_seq / next_value_seq rows (else zeros);
+//   DEEP  sh: both networks' shapes; `hidden` and cr.hidden are 0 — else sh is zeros and the two carry the one hidden width each;
+//   NRM   (DEEP with a normaliser bound) nm: the handle's normaliser;
+//   EXT   nseq: the launch's next_obs_seq rows (nullable), and ns.mode is honoured.
+template <bool POL, bool SMP, bool CRT, bool DEEP, bool NRM, bool EXT>
+static hipError_t rollout_launches(mz_handle* h, hipStream_t st, const RolloutPlan& p) {
   PointState S{h->state, h->pt_t, h->pt_ep, h->pt_rec};
   const size_t n = (size_t)h->n, od = (size_t)h->model.obs_dim, nu = (size_t)h->model.nu;
   const mzp_norm nm{h->nrm_mean, h->nrm_inv_std, h->nrm_clip};
-  // what mz_rollout_ex adds runs the kernels' EXT instantiations; every other call launches what it always launched
-  const bool ext = next_obs_seq_dev || (SMP && noise.mode != MZ_NOISE_PRE_SQUASH);
-  for (int k0 = 0; k0 < nsteps; k0 += MZ_ROLLOUT_CHUNK) {
-    const int ks = nsteps - k0 < MZ_ROLLOUT_CHUNK ? nsteps - k0 : MZ_ROLLOUT_CHUNK;
-    float* rew = reward_dev + k0 * n;
-    uint8_t* dn = done_dev + k0 * n;
-    int* gi = goal_idx_dev ? goal_idx_dev + k0 * n : nullptr;
-    float* inf = info_dev ? info_dev + k0 * n * 4 : nullptr;
-    float* oseq = obs_seq_dev ? obs_seq_dev + k0 * n * od : nullptr;
-    float* aseq = actions_seq_dev ? actions_seq_dev + k0 * n * nu : nullptr;
-    float* nseq = next_obs_seq_dev ? next_obs_seq_dev + k0 * n * od : nullptr;
-    const PolicyNoise ns{noise.seed, noise.step + (uint64_t)k0, noise.logp_seq ? noise.logp_seq + k0 * n : nullptr, noise.mode};
-    const PolicyCritic cr{critic.params, critic.stride, critic.hidden, critic.value_seq ? critic.value_seq + k0 * n : nullptr,
-                          critic.next_value_seq ? critic.next_value_seq + k0 * n : nullptr};
-    if (h->robot == MZ_ROBOT_SWIMMER) {
-#define MZ_SW_ROLL(NL, NB) do { if (ext) MZ_SW_ROLL_(NL, NB, true); else MZ_SW_ROLL_(NL, NB, false); } while (0)
-#define MZ_SW_ROLL_(NL, NB, EXT)                                                                                                    \
-  hipLaunchKernelGGL((swimmer_policy_rollout_kernel<NL, NB, (NL <= 4 ? 4 : 8), SMP, CRT, DEEP, NRM, EXT>), dim3((unsigned)((n * (NL <= 4 ? 4 : 8) + sw_bd - 1) / sw_bd)), dim3(sw_bd), 0, st, \
-                     h->swimmer_dev, h->n, S, ks, params_dev, pstride, hidden, squash, action_scale, obs_dev, rew, dn, gi, inf, oseq, aseq, h->status,         \
-                     h->auto_reset, h->seed, h->env0, h->final_obs, ns, cr, shapes, nm, nseq)
-      const int bd = h->swimmer.nblock ? h->swimmer.nbdof : 0;
-      const unsigned sw_bd = 64u * (unsigned)(h->wpb_set ? h->waves_per_block : 4);
-      if (h->swimmer.nlink == 3) { if (bd == 3) MZ_SW_ROLL(3, 3); else if (bd == 2) MZ_SW_ROLL(3, 2); else MZ_SW_ROLL(3, 0); }
-      else if (h->swimmer.nlink == 2) { if (bd == 3) MZ_SW_ROLL(2, 3); else if (bd == 2) MZ_SW_ROLL(2, 2); else MZ_SW_ROLL(2, 0); }
-      else if (h->swimmer.nlink == 4) MZ_SW_ROLL(4, 0);
-      else if (h->swimmer.nlink == 5) MZ_SW_ROLL(5, 0);
-      else MZ_SW_ROLL(6, 0);
-#undef MZ_SW_ROLL
-#undef MZ_SW_ROLL_
+  const mz_net *A = p.actor, *C = p.critic;
+  auto shape = [](const mz_net* net) { return mzp_shape{net->n_hidden, net->hidden[0], net->hidden[1], net->activation}; };
+  const PolicyShapes sh{DEEP ? shape(A) : mzp_shape{0, 0, 0, 0}, DEEP && CRT ? shape(C) : mzp_shape{0, 0, 0, 0}};
+  const int hidden = POL && !DEEP ? A->hidden[0] : 0, squash = POL ? A->squash : 0;
+  const float action_scale = POL ? (float)A->action_scale : 0.0f;
+  const float* params = POL ? A->params_dev : nullptr;
+  const long pstride = POL ? (long)A->env_stride : 0, astride = p.action_step_stride;
+  for (int k0 = 0; k0 < p.n_steps; k0 += MZ_ROLLOUT_CHUNK) {
+    const int ks = p.n_steps - k0 < MZ_ROLLOUT_CHUNK ? p.n_steps - k0 : MZ_ROLLOUT_CHUNK;
+    float* rew = p.reward_dev + k0 * n;
+    uint8_t* dn = p.done_dev + k0 * n;
+    int* gi = p.goal_idx_dev ? p.goal_idx_dev + k0 * n : nullptr;
+    float* inf = p.info_dev ? p.info_dev + k0 * n * 4 : nullptr;
+    float* oseq = p.obs_seq_dev ? p.obs_seq_dev + k0 * n * od : nullptr;
+    float* nseq = p.next_obs_seq_dev ? p.next_obs_seq_dev + k0 * n * od : nullptr;  // this launch writes rows k0 .. k0 + ks - 1
+    if constexpr (!POL) {
+      const int last = k0 + ks == p.n_steps ? ks - 1 : -1;
+      const float* act = p.actions_dev + (size_t)k0 * astride;
+      if (h->robot == MZ_ROBOT_SWIMMER)
+        swimmer_ladder(h, [&](auto NL, auto NB, auto G) {
+          hipLaunchKernelGGL((swimmer_rollout_kernel<NL, NB, G, EXT>), swimmer_grid(h, G), dim3(swimmer_block(h)), 0, st, h->swimmer_dev, h->n, S, ks, act,
+                             astride, p.obs_dev, last, rew, dn, gi, inf, oseq, h->status, h->auto_reset, h->seed, h->env0, h->final_obs, nseq);
+        });
+      else
+        point_ladder(h, [&](auto NB, auto NS, auto G) {
+          hipLaunchKernelGGL((planar_rollout_kernel<NB, NS, G, EXT>), point_grid(h, G), dim3(64), 0, st, h->point_dev, h->n, S, ks, act, astride, p.obs_dev,
+                             last, rew, dn, gi, inf, oseq, h->status, h->auto_reset, h->seed, h->env0, h->final_obs, nseq);
+        });
     } else {
-#define MZ_PLANAR_ROLL(NB, NS, G) do { if (ext) MZ_PLANAR_ROLL_(NB, NS, G, true); else MZ_PLANAR_ROLL_(NB, NS, G, false); } while (0)
-#define MZ_PLANAR_ROLL_(NB, NS, G, EXT)                                                                                                \
-  hipLaunchKernelGGL((planar_policy_rollout_kernel<NB, NS, G, SMP, CRT, DEEP, NRM, EXT>), dim3((h->n + 64 / G - 1) / (64 / G)), dim3(64), 0, st, h->point_dev, h->n, S, ks, params_dev, \
-                     pstride, hidden, squash, action_scale, obs_dev, rew, dn, gi, inf, oseq, aseq, h->status, h->auto_reset, h->seed, h->env0, h->final_obs, ns, cr, shapes, nm, nseq)
-      if (h->point.nball) MZ_PLANAR_ROLL(0, 1, 32);
-      else switch (h->point.nblock) {
-        case 0: {
-          const int lanes = mzk_planar_lanes(h);  // the step's rule
-          if (lanes == 8) MZ_PLANAR_ROLL(0, 0, 8);
-          else if (lanes == 16) MZ_PLANAR_ROLL(0, 0, 16);
-          else MZ_PLANAR_ROLL(0, 0, 32);
-          break;
-        }
-        case 1: MZ_PLANAR_ROLL(1, 0, 32); break;
-        case 2: MZ_PLANAR_ROLL(2, 0, 64); break;
-        default: MZ_PLANAR_ROLL(3, 0, 64); break;
-      }
-#undef MZ_PLANAR_ROLL
-#undef MZ_PLANAR_ROLL_
+      float* aseq = p.actions_seq_dev ? p.actions_seq_dev + k0 * n * nu : nullptr;
+      const PolicyNoise ns = SMP ? PolicyNoise{p.noise_seed, p.noise_step + (uint64_t)k0, p.logp_seq_dev ? p.logp_seq_dev + k0 * n : nullptr, p.noise_mode}
+                                 : PolicyNoise{0, 0, nullptr, 0};
+      const PolicyCritic cr = CRT ? PolicyCritic{C->params_dev, (long)C->env_stride, DEEP ? 0 : C->hidden[0],
+                                                 p.value_seq_dev ? p.value_seq_dev + k0 * n : nullptr,
+                                                 p.next_value_seq_dev ? p.next_value_seq_dev + k0 * n : nullptr}
+                                  : PolicyCritic{nullptr, 0, 0, nullptr, nullptr};
+      if (h->robot == MZ_ROBOT_SWIMMER)
+        swimmer_ladder(h, [&](auto NL, auto NB, auto G) {
+          hipLaunchKernelGGL((swimmer_policy_rollout_kernel<NL, NB, G, SMP, CRT, DEEP, NRM, EXT>), swimmer_grid(h, G), dim3(swimmer_block(h)), 0, st,
+                             h->swimmer_dev, h->n, S, ks, params, pstride, hidden, squash, action_scale, p.obs_dev, rew, dn, gi, inf, oseq, aseq, h->status,
+                             h->auto_reset, h->seed, h->env0, h->final_obs, ns, cr, sh, nm, nseq);
+        });
+      else
+        point_ladder(h, [&](auto NB, auto NS, auto G) {
+          hipLaunchKernelGGL((planar_policy_rollout_kernel<NB, NS, G, SMP, CRT, DEEP, NRM, EXT>), point_grid(h, G), dim3(64), 0, st, h->point_dev, h->n, S, ks,
+                             params, pstride, hidden, squash, action_scale, p.obs_dev, rew, dn, gi, inf, oseq, aseq, h->status, h->auto_reset, h->seed,
+                             h->env0, h->final_obs, ns, cr, sh, nm, nseq);
+        });
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -1082,84 +1051,28 @@ static hipError_t planar_rollout_policy_launches(mz_handle* h, hipStream_t st, i
   return hipSuccess;
 }
 
-hipError_t mzk_planar_rollout_policy(mz_handle* h, hipStream_t st, int nsteps, const float* params_dev, long pstride, int hidden, int squash,
-                                     float action_scale, float* obs_dev, float* reward_dev, uint8_t* done_dev, int* goal_idx_dev, float* info_dev,
-                                     float* obs_seq_dev, float* actions_seq_dev, float* next_obs_seq_dev) {
-  return planar_rollout_policy_launches<false>(h, st, nsteps, params_dev, pstride, hidden, squash, action_scale, obs_dev, reward_dev, done_dev,
-                                               goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, PolicyNoise{0, 0, nullptr, 0},
-                                               PolicyCritic{nullptr, 0, 0, nullptr, nullptr}, PolicyShapes{{0, 0, 0, 0}, {0, 0, 0, 0}}, next_obs_seq_dev);
-}
-
-hipError_t mzk_planar_rollout_policy_sample(mz_handle* h, hipStream_t st, int nsteps, const float* params_dev, long pstride, int hidden, int squash,
-                                            float action_scale, uint64_t noise_seed, uint64_t noise_step, float* obs_dev, float* reward_dev,
-                                            uint8_t* done_dev, int* goal_idx_dev, float* info_dev, float* obs_seq_dev, float* actions_seq_dev,
-                                            float* logp_seq_dev, int noise_mode, float* next_obs_seq_dev) {
-  return planar_rollout_policy_launches<true>(h, st, nsteps, params_dev, pstride, hidden, squash, action_scale, obs_dev, reward_dev, done_dev,
-                                              goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev,
-                                              PolicyNoise{noise_seed, noise_step, logp_seq_dev, noise_mode},
-                                              PolicyCritic{nullptr, 0, 0, nullptr, nullptr}, PolicyShapes{{0, 0, 0, 0}, {0, 0, 0, 0}}, next_obs_seq_dev);
-}
-
-hipError_t mzk_planar_rollout_actor_critic(mz_handle* h, hipStream_t st, int nsteps, const float* params_dev, long pstride, int hidden, int squash,
-                                           float action_scale, int sample, uint64_t noise_seed, uint64_t noise_step, const mz_critic* critic,
-                                           float* obs_dev, float* reward_dev, uint8_t* done_dev, int* goal_idx_dev, float* info_dev, float* obs_seq_dev,
-                                           float* actions_seq_dev, float* logp_seq_dev, int noise_mode, float* next_obs_seq_dev) {
-  const PolicyCritic cr{critic->params_dev, (long)critic->env_stride, critic->hidden, critic->value_seq_dev, critic->next_value_seq_dev};
-  const PolicyShapes none{{0, 0, 0, 0}, {0, 0, 0, 0}};
-  if (sample)
-    return planar_rollout_policy_launches<true, true>(h, st, nsteps, params_dev, pstride, hidden, squash, action_scale, obs_dev, reward_dev, done_dev,
-                                                      goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev,
-                                                      PolicyNoise{noise_seed, noise_step, logp_seq_dev, noise_mode}, cr, none, next_obs_seq_dev);
-  return planar_rollout_policy_launches<false, true>(h, st, nsteps, params_dev, pstride, hidden, squash, action_scale, obs_dev, reward_dev, done_dev,
-                                                     goal_idx_dev, info_dev, obs_seq_dev, actions_seq_dev, PolicyNoise{0, 0, nullptr, 0}, cr, none,
-                                                     next_obs_seq_dev);
-}
-
-hipError_t mzk_planar_rollout_net(mz_handle* h, hipStream_t st, int nsteps, const mz_net* actor, int sample, uint64_t noise_seed,
-                                  uint64_t noise_step, const mz_net* critic, float* value_seq_dev, float* next_value_seq_dev, float* obs_dev,
-                                  float* reward_dev, uint8_t* done_dev, int* goal_idx_dev, float* info_dev, float* obs_seq_dev,
-                                  float* actions_seq_dev, float* logp_seq_dev, int noise_mode, float* next_obs_seq_dev) {
-  const PolicyNoise ns = sample ? PolicyNoise{noise_seed, noise_step, logp_seq_dev, noise_mode} : PolicyNoise{0, 0, nullptr, 0};
-  PolicyShapes sh{{actor->n_hidden, actor->hidden[0], actor->hidden[1], actor->activation}, {0, 0, 0, 0}};
-  PolicyCritic cr{nullptr, 0, 0, nullptr, nullptr};
-  if (critic) {
-    sh.critic = mzp_shape{critic->n_hidden, critic->hidden[0], critic->hidden[1], critic->activation};
-    cr = PolicyCritic{critic->params_dev, (long)critic->env_stride, 0, value_seq_dev, next_value_seq_dev};
-  }
-#define MZ_NET_ROLL(SMP, CRT, NRM)                                                                                                          \
-  planar_rollout_policy_launches<SMP, CRT, true, NRM>(h, st, nsteps, actor->params_dev, (long)actor->env_stride, 0, actor->squash,          \
-                                                      (float)actor->action_scale, obs_dev, reward_dev, done_dev, goal_idx_dev, info_dev,    \
-                                                      obs_seq_dev, actions_seq_dev, ns, cr, sh, next_obs_seq_dev)
-  if (h->nrm_mean) {
-    if (critic) return sample ? MZ_NET_ROLL(true, true, true) : MZ_NET_ROLL(false, true, true);
-    return sample ? MZ_NET_ROLL(true, false, true) : MZ_NET_ROLL(false, false, true);
-  }
-  if (critic) return sample ? MZ_NET_ROLL(true, true, false) : MZ_NET_ROLL(false, true, false);
-  return sample ? MZ_NET_ROLL(true, false, false) : MZ_NET_ROLL(false, false, false);
-#undef MZ_NET_ROLL
+hipError_t mzk_planar_rollout(mz_handle* h, hipStream_t st, const RolloutPlan& p) {
+  const RolloutKernels kn = mzk_rollout_kernels(h, p);
+  if (!p.actor) return flag_switch([&](auto EXT) { return rollout_launches<false, false, false, false, false, EXT>(h, st, p); }, kn.ext);
+  return flag_switch(
+      [&](auto SMP, auto CRT, auto DEEP, auto NRM, auto EXT) {
+        if constexpr (NRM && !DEEP) return hipErrorInvalidValue;  // not instantiated: a bound normaliser makes every call DEEP
+        else return rollout_launches<true, SMP, CRT, DEEP, NRM, EXT>(h, st, p);
+      },
+      p.sample != 0, p.critic != nullptr, kn.deep, kn.nrm, kn.ext);
 }
 
 hipError_t mzk_planar_reset(mz_handle* h, hipStream_t st, const uint8_t* mask_dev, uint64_t seed, float* obs_dev) {
   PointState S{h->state, h->pt_t, h->pt_ep, h->pt_rec};
-  const int nb = (h->n + 255) / 256;
-  if (h->robot == MZ_ROBOT_SWIMMER) {
-#define MZ_SW_RESET(NL, NB) hipLaunchKernelGGL((swimmer_reset_kernel<NL, NB>), dim3(nb), dim3(256), 0, st, h->swimmer_dev, h->n, S, mask_dev, seed, h->env0, obs_dev, h->model.obs_dim)
-    const int bd = h->swimmer.nblock ? h->swimmer.nbdof : 0;
-    if (h->swimmer.nlink == 3) { if (bd == 3) MZ_SW_RESET(3, 3); else if (bd == 2) MZ_SW_RESET(3, 2); else MZ_SW_RESET(3, 0); }
-    else if (h->swimmer.nlink == 2) { if (bd == 3) MZ_SW_RESET(2, 3); else if (bd == 2) MZ_SW_RESET(2, 2); else MZ_SW_RESET(2, 0); }
-    else if (h->swimmer.nlink == 4) MZ_SW_RESET(4, 0);
-    else if (h->swimmer.nlink == 5) MZ_SW_RESET(5, 0);
-    else MZ_SW_RESET(6, 0);
-#undef MZ_SW_RESET
-    return hipGetLastError();
-  }
-  if (h->point.nball) hipLaunchKernelGGL((point_reset_kernel<0, 1>), dim3(nb), dim3(256), 0, st, h->point_dev, h->n, S, mask_dev, seed, h->env0, obs_dev, h->model.obs_dim);
-  else switch (h->point.nblock) {
-    case 0: hipLaunchKernelGGL((point_reset_kernel<0, 0>), dim3(nb), dim3(256), 0, st, h->point_dev, h->n, S, mask_dev, seed, h->env0, obs_dev, h->model.obs_dim); break;
-    case 1: hipLaunchKernelGGL((point_reset_kernel<1, 0>), dim3(nb), dim3(256), 0, st, h->point_dev, h->n, S, mask_dev, seed, h->env0, obs_dev, h->model.obs_dim); break;
-    case 2: hipLaunchKernelGGL((point_reset_kernel<2, 0>), dim3(nb), dim3(256), 0, st, h->point_dev, h->n, S, mask_dev, seed, h->env0, obs_dev, h->model.obs_dim); break;
-    default: hipLaunchKernelGGL((point_reset_kernel<3, 0>), dim3(nb), dim3(256), 0, st, h->point_dev, h->n, S, mask_dev, seed, h->env0, obs_dev, h->model.obs_dim); break;
-  }
+  const int nb = (h->n + 255) / 256;  // one lane per env: the ladder's lane count is not read
+  if (h->robot == MZ_ROBOT_SWIMMER)
+    swimmer_ladder(h, [&](auto NL, auto NB, auto) {
+      hipLaunchKernelGGL((swimmer_reset_kernel<NL, NB>), dim3(nb), dim3(256), 0, st, h->swimmer_dev, h->n, S, mask_dev, seed, h->env0, obs_dev, h->model.obs_dim);
+    });
+  else
+    point_ladder(h, [&](auto NB, auto NS, auto) {
+      hipLaunchKernelGGL((point_reset_kernel<NB, NS>), dim3(nb), dim3(256), 0, st, h->point_dev, h->n, S, mask_dev, seed, h->env0, obs_dev, h->model.obs_dim);
+    });
   return hipGetLastError();
 }
 

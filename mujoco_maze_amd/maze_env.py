@@ -497,15 +497,21 @@ class VecMazeEnv:
                                       _ptr(buf["done"]), _ptr(buf["goal"]), _ptr(buf["info"]), _ptr(buf["obs_seq"]) if return_obs else None,
                                       self._stream())
             _capi.check(self._lib, self._h, rc, "mz_rollout")
+        return self._obs, buf["reward"], buf["done"], self._rollout_info(buf, return_obs, return_next_obs)
+
+    def _rollout_info(self, buf, return_obs: bool, return_next_obs: bool, return_actions: bool = False, **per_step) -> dict:
+        """The info dict of a rollout from its buffers; per_step: what a closed-loop call adds ([K, N] each)."""
         info = {"position": buf["info"][:, :, :2], "reward_forward": buf["info"][:, :, 2], "reward_ctrl": buf["info"][:, :, 3],
-                "goal_index": buf["goal"]}
+                "goal_index": buf["goal"], **per_step}
         if return_obs:
             info["observations"] = buf["obs_seq"]
         if return_next_obs:
             info["next_observations"] = buf["next_obs_seq"]
+        if return_actions:
+            info["actions"] = buf["actions"]
         if self._auto_reset:
             info["final_observation"] = self._final_obs
-        return self._obs, buf["reward"], buf["done"], info
+        return info
 
     @staticmethod
     def _net_kind(hidden, activation: str, what: str = "hidden"):
@@ -584,45 +590,8 @@ class VecMazeEnv:
 
         return_next_obs: info["next_observations"] [K, N, obs_dim] as in `rollout` (raw rows, whether or not a normaliser is bound);
         the call is then one mz_rollout_ex."""
-        if value_params is not None or gae is not None or return_next_obs or not self._net_kind(hidden, activation)[2]:
-            return self._rollout_actor_critic(False, params, steps, hidden, squash, action_scale, obs, None, None, return_obs, return_actions,
-                                              value_params, value_hidden, gae, activation, value_activation, return_next_obs)
-        torch, n = self._torch, self.num_envs
-        p, stride = self._policy_params(params, hidden)
-        K = int(steps)
-        if not 1 <= K <= 65536:
-            raise ValueError(f"a rollout takes 1 .. 65536 steps, got {K}")
-        if obs is not None:
-            o = self._policy_obs(obs)
-            if o.data_ptr() != self._obs.data_ptr():
-                self._obs.copy_(o)
-        buf = self._rollout_buffers(K, return_obs)
-        if return_actions and "actions" not in buf:
-            buf["actions"] = torch.empty((K, n, self.nu), dtype=torch.float32, device=self.device)
-        if self._host_rewards or (self._env_goals is not None and self._auto_reset):
-            for k in range(K):
-                a = self.policy_act(p, None, hidden, squash, action_scale)
-                o, rew, done, inf = self.step(a)
-                buf["reward"][k], buf["done"][k], buf["goal"][k], buf["info"][k] = rew, done, inf["goal_index"], self._info
-                if return_obs:
-                    buf["obs_seq"][k] = o
-                if return_actions:
-                    buf["actions"][k] = a
-        else:
-            rc = self._lib.mz_rollout_policy(self._h, K, _ptr(p), stride, int(hidden), 1 if squash else 0, float(action_scale), _ptr(self._obs),
-                                             _ptr(buf["reward"]), _ptr(buf["done"]), _ptr(buf["goal"]), _ptr(buf["info"]),
-                                             _ptr(buf["obs_seq"]) if return_obs else None, _ptr(buf["actions"]) if return_actions else None,
-                                             self._stream())
-            _capi.check(self._lib, self._h, rc, "mz_rollout_policy")
-        info = {"position": buf["info"][:, :, :2], "reward_forward": buf["info"][:, :, 2], "reward_ctrl": buf["info"][:, :, 3],
-                "goal_index": buf["goal"]}
-        if return_obs:
-            info["observations"] = buf["obs_seq"]
-        if return_actions:
-            info["actions"] = buf["actions"]
-        if self._auto_reset:
-            info["final_observation"] = self._final_obs
-        return self._obs, buf["reward"], buf["done"], info
+        return self._rollout_closed_loop(False, params, steps, hidden, squash, action_scale, obs, None, None, return_obs, return_actions,
+                                         value_params, value_hidden, gae, activation, value_activation, return_next_obs)
 
     def _noise_args(self, noise_seed, noise_step, advance: int):
         """(noise_seed, noise_step) of a draw as uint64: the env's own seed and counter where the caller gives none; the counter
@@ -703,50 +672,8 @@ class VecMazeEnv:
         noise as in `policy_sample` ("action": TD3 / DDPG exploration), return_next_obs as in `rollout`: either makes the call one
         mz_rollout_ex, which runs the same kernels.  Together they collect an off-policy batch in one call: s = the entry observation
         followed by "observations"[:-1], a = "actions", r, s' = "next_observations", terminated = dones & 1."""
-        mode = _capi.noise_mode(noise)
-        if value_params is not None or gae is not None or return_next_obs or mode != _capi.NOISE_PRE_SQUASH or not self._net_kind(hidden, activation)[2]:
-            return self._rollout_actor_critic(True, params, steps, hidden, squash, action_scale, obs, noise_seed, noise_step, return_obs,
-                                              return_actions, value_params, value_hidden, gae, activation, value_activation, return_next_obs,
-                                              noise)
-        torch, n = self._torch, self.num_envs
-        p, stride = self._policy_params(params, hidden, stochastic=True)
-        K = int(steps)
-        if not 1 <= K <= 65536:
-            raise ValueError(f"a rollout takes 1 .. 65536 steps, got {K}")
-        if obs is not None:
-            o = self._policy_obs(obs)
-            if o.data_ptr() != self._obs.data_ptr():
-                self._obs.copy_(o)
-        buf = self._rollout_buffers(K, return_obs)
-        if return_actions and "actions" not in buf:
-            buf["actions"] = torch.empty((K, n, self.nu), dtype=torch.float32, device=self.device)
-        if "logp" not in buf:
-            buf["logp"] = torch.empty((K, n), dtype=torch.float32, device=self.device)
-        seed, step = self._noise_args(noise_seed, noise_step, K)
-        if self._host_rewards or (self._env_goals is not None and self._auto_reset):
-            for k in range(K):
-                a, lp = self.policy_sample(p, None, hidden, squash, action_scale, seed.value, step.value + k)
-                o, rew, done, inf = self.step(a)
-                buf["reward"][k], buf["done"][k], buf["goal"][k], buf["info"][k], buf["logp"][k] = rew, done, inf["goal_index"], self._info, lp
-                if return_obs:
-                    buf["obs_seq"][k] = o
-                if return_actions:
-                    buf["actions"][k] = a
-        else:
-            rc = self._lib.mz_rollout_policy_sample(self._h, K, _ptr(p), stride, int(hidden), 1 if squash else 0, float(action_scale), seed, step,
-                                                    _ptr(self._obs), _ptr(buf["reward"]), _ptr(buf["done"]), _ptr(buf["goal"]), _ptr(buf["info"]),
-                                                    _ptr(buf["obs_seq"]) if return_obs else None,
-                                                    _ptr(buf["actions"]) if return_actions else None, _ptr(buf["logp"]), self._stream())
-            _capi.check(self._lib, self._h, rc, "mz_rollout_policy_sample")
-        info = {"position": buf["info"][:, :, :2], "reward_forward": buf["info"][:, :, 2], "reward_ctrl": buf["info"][:, :, 3],
-                "goal_index": buf["goal"], "logp": buf["logp"]}
-        if return_obs:
-            info["observations"] = buf["obs_seq"]
-        if return_actions:
-            info["actions"] = buf["actions"]
-        if self._auto_reset:
-            info["final_observation"] = self._final_obs
-        return self._obs, buf["reward"], buf["done"], info
+        return self._rollout_closed_loop(True, params, steps, hidden, squash, action_scale, obs, noise_seed, noise_step, return_obs,
+                                         return_actions, value_params, value_hidden, gae, activation, value_activation, return_next_obs, noise)
 
     def _value_params(self, value_params, hidden):
         """A critic's parameters as a contiguous float32 device tensor [nvpar] or [N, nvpar]; returns (tensor, env_stride)."""
@@ -845,12 +772,12 @@ class VecMazeEnv:
         _capi.check(self._lib, self._h, rc, "mz_return_scan")
         return ret, ln
 
-    def _rollout_actor_critic(self, sample: bool, params, steps, hidden, squash, action_scale, obs, noise_seed, noise_step, return_obs,
-                              return_actions, value_params, value_hidden, gae, activation="tanh", value_activation="tanh",
-                              return_next_obs=False, noise="pre_squash"):
-        """rollout_policy (sample False) / rollout_policy_sample (sample True) with a critic, or with a network that needs mz_net
-        (then the critic is optional): one mz_rollout_actor_critic or mz_rollout_net call — one mz_rollout_ex with return_next_obs or
-        noise="action" —, or the defining loop where the host has work between steps."""
+    def _rollout_closed_loop(self, sample: bool, params, steps, hidden, squash, action_scale, obs, noise_seed, noise_step, return_obs,
+                             return_actions, value_params, value_hidden, gae, activation="tanh", value_activation="tanh",
+                             return_next_obs=False, noise="pre_squash"):
+        """rollout_policy (sample False) / rollout_policy_sample (sample True): the defining loop where the host has work between
+        steps, else one C call — mz_rollout_ex with return_next_obs or noise="action"; mz_rollout_net where a network, actor or
+        critic, needs mz_net; mz_rollout_actor_critic with a critic; mz_rollout_policy_sample / mz_rollout_policy without one."""
         torch, n = self._torch, self.num_envs
         mode = _capi.noise_mode(noise)
         extended = return_next_obs or mode != _capi.NOISE_PRE_SQUASH
@@ -924,31 +851,29 @@ class VecMazeEnv:
                                           _ptr(buf["logp"]) if sample else None, self._stream())
             _capi.check(self._lib, self._h, rc, "mz_rollout_net")
         else:
-            critic = _capi.MzCritic(_ptr(vp), vstride, int(value_hidden), 0, _ptr(buf["values"]), _ptr(buf["next_values"]))
-            rc = self._lib.mz_rollout_actor_critic(self._h, K, _ptr(p), stride, int(hidden), 1 if squash else 0, float(action_scale), 1 if sample else 0,
-                                                   seed, step, C.byref(critic), _ptr(self._obs), _ptr(buf["reward"]), _ptr(buf["done"]),
-                                                   _ptr(buf["goal"]), _ptr(buf["info"]), _ptr(buf["obs_seq"]) if return_obs else None,
-                                                   _ptr(buf["actions"]) if return_actions else None, _ptr(buf["logp"]) if sample else None,
-                                                   self._stream())
-            _capi.check(self._lib, self._h, rc, "mz_rollout_actor_critic")
-        info = {"position": buf["info"][:, :, :2], "reward_forward": buf["info"][:, :, 2], "reward_ctrl": buf["info"][:, :, 3],
-                "goal_index": buf["goal"]}
+            legacy_args = (self._h, K, _ptr(p), stride, int(hidden), 1 if squash else 0, float(action_scale))
+            outputs = (_ptr(self._obs), _ptr(buf["reward"]), _ptr(buf["done"]), _ptr(buf["goal"]), _ptr(buf["info"]),
+                       _ptr(buf["obs_seq"]) if return_obs else None, _ptr(buf["actions"]) if return_actions else None)
+            if with_critic:
+                critic = _capi.MzCritic(_ptr(vp), vstride, int(value_hidden), 0, _ptr(buf["values"]), _ptr(buf["next_values"]))
+                rc = self._lib.mz_rollout_actor_critic(*legacy_args, 1 if sample else 0, seed, step, C.byref(critic), *outputs,
+                                                       _ptr(buf["logp"]) if sample else None, self._stream())
+                _capi.check(self._lib, self._h, rc, "mz_rollout_actor_critic")
+            elif sample:
+                rc = self._lib.mz_rollout_policy_sample(*legacy_args, seed, step, *outputs, _ptr(buf["logp"]), self._stream())
+                _capi.check(self._lib, self._h, rc, "mz_rollout_policy_sample")
+            else:
+                rc = self._lib.mz_rollout_policy(*legacy_args, *outputs, self._stream())
+                _capi.check(self._lib, self._h, rc, "mz_rollout_policy")
+        per_step = {}
         if with_critic:
-            info["values"], info["next_values"] = buf["values"], buf["next_values"]
+            per_step["values"], per_step["next_values"] = buf["values"], buf["next_values"]
         if sample:
-            info["logp"] = buf["logp"]
+            per_step["logp"] = buf["logp"]
         if gae is not None:
-            info["advantages"], info["returns"] = self.gae(buf["reward"], buf["done"], buf["values"], buf["next_values"], gamma, lam,
-                                                           out=(buf["advantages"], buf["returns"]))
-        if return_obs:
-            info["observations"] = buf["obs_seq"]
-        if return_next_obs:
-            info["next_observations"] = buf["next_obs_seq"]
-        if return_actions:
-            info["actions"] = buf["actions"]
-        if self._auto_reset:
-            info["final_observation"] = self._final_obs
-        return self._obs, buf["reward"], buf["done"], info
+            per_step["advantages"], per_step["returns"] = self.gae(buf["reward"], buf["done"], buf["values"], buf["next_values"], gamma, lam,
+                                                                   out=(buf["advantages"], buf["returns"]))
+        return self._obs, buf["reward"], buf["done"], self._rollout_info(buf, return_obs, return_next_obs, return_actions, **per_step)
 
     def _rollout_buffers(self, K: int, with_obs: bool, with_next_obs: bool = False) -> dict:
         """Output tensors of rollout(), allocated per K and kept."""
