@@ -892,8 +892,8 @@ int mzk_planar_state_width(const mz_handle* h) {
   return h->robot == MZ_ROBOT_SWIMMER ? h->swimmer.nlink + 2 + (h->swimmer.nblock ? h->swimmer.nbdof : 0) : 3 + 2 * h->point.nblock + 3 * h->point.nball;
 }
 
-// lanes per env of the next step launch (one rule for the launch and for mz_get_info)
-int mzk_planar_lanes(const mz_handle* h) {
+// lanes per env by the handle's robot, blocks, batch size and options: the rule the ladders below read
+static int planar_lane_rule(const mz_handle* h) {
   if (h->robot == MZ_ROBOT_SWIMMER) return h->swimmer.nlink <= 4 ? 4 : 8;
   if (h->point.nball || h->point.nblock == 1) return 32;
   if (h->point.nblock >= 2) return 64;
@@ -907,7 +907,8 @@ int mzk_planar_lanes(const mz_handle* h) {
 template <int V> using ic = std::integral_constant<int, V>;
 
 // Swimmer / Reacher: f(NL, NB, G) — NL links, NB the movable block's degrees of freedom (0: none), G = 4 lanes per env up to four
-// links, else 8 (mzk_planar_lanes)
+// links, else 8.  The two rungs with NB = 3 (a block on three slides: a custom MultiFall task) have no handle: mz_create sends such a
+// model to the general engine (gen_model_needs_general_engine)
 template <class F>
 static void swimmer_ladder(const mz_handle* h, F&& f) {
   const int bd = h->swimmer.nblock ? h->swimmer.nbdof : 0;
@@ -936,7 +937,7 @@ static void point_ladder(const mz_handle* h, F&& f) {
   if (h->point.nball) f(ic<0>{}, ic<1>{}, ic<32>{});
   else switch (h->point.nblock) {
     case 0: {
-      const int lanes = mzk_planar_lanes(h);
+      const int lanes = planar_lane_rule(h);
       if (lanes == 8) f(ic<0>{}, ic<0>{}, ic<8>{});
       else if (lanes == 16) f(ic<0>{}, ic<0>{}, ic<16>{});
       else f(ic<0>{}, ic<0>{}, ic<32>{});
@@ -949,6 +950,15 @@ static void point_ladder(const mz_handle* h, F&& f) {
 }
 // the Point kernels' launch geometry: one wave per workgroup, 64 / G envs in it
 static dim3 point_grid(const mz_handle* h, int G) { return dim3((h->n + 64 / G - 1) / (64 / G)); }
+
+// lanes per env of the next step launch, for mz_get_info: the G of the instantiation the ladder picks — not the rule's value, so a
+// ladder that sent a lane count to another rung shows in launch_info() (tests/test_gpu_planar_ladder.py reads the rung from it)
+int mzk_planar_lanes(const mz_handle* h) {
+  int g = 0;
+  if (h->robot == MZ_ROBOT_SWIMMER) swimmer_ladder(h, [&](auto, auto, auto G) { g = G; });
+  else point_ladder(h, [&](auto, auto, auto G) { g = G; });
+  return g;
+}
 
 hipError_t mzk_planar_step(mz_handle* h, hipStream_t st, const float* actions_dev, float* obs_dev, float* reward_dev, uint8_t* done_dev,
                            int* goal_idx_dev, float* info_dev) {

@@ -42,8 +42,10 @@ struct SwimmerDev {
   // force-free slide-x / slide-y body — it only drifts with whatever velocity it is given and shows up in the observation
   int nblock, observe_blocks;
   double block_pos0[1][3], block_mass, block_box[3];  // inertia-box sizes: the medium drags a moving block too
-  // slide dofs of the block: 2 (x, y: Push mazes) or 2 / 3 with a z slide (y, z: Fall; x, y, z: MultiFall), the latter LIMITED
-  // (maze_env.py:607-648) and pulled by gravity
+  // slide dofs of the block: 2 (x, y: Push mazes) or 2 / 3 with a z slide (y, z: Fall and the registered MultiFall-v2 ids, which are
+  // built on the Fall maze; x, y, z: the MultiFall maze proper, which no registered Swimmer / Reacher id has — a custom task only, and
+  // mz_create steps that model on the general engine, so nbdof == 3 reaches no kernel today), the z slide LIMITED (maze_env.py:607-648)
+  // and pulled by gravity
   int nbdof, bd_axis[3], bd_limited[3];
   double bd_lo[3], bd_hi[3], bd_margin, bd_K, bd_B, bd_solimp[5], gz;
   TaskDev task;

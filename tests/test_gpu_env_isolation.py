@@ -1,6 +1,6 @@
 """Env isolation: what an env computes depends on its own state, action, seed and global slot — never on its batch-mates.
 
-Every kernel packs several envs into one wavefront (4 or 2 for the Point and the Ant, 16 for the Swimmer and Reacher; the chains
+Every kernel packs several envs into one wavefront (8, 4 or 2 for the bare Point, 4 or 2 for the Ant, 16 for the Swimmer and Reacher; the chains
 also 64 into one workgroup, the Ant 2 or 4 waves) and takes wave-uniform shortcuts: `cx.any(ncon > SW)` in point_bare.h, the
 contact-slot guards and the wave-uniform Newton count of ant_newton_rows.h, `gballot` in planar_dyn.h, the in-kernel auto-reset of
 only some lanes.  tests/test_gpu_ant_slot_guards.py holds the contract for the Ant row solver at 16 lanes; this module holds it for
@@ -46,6 +46,9 @@ BAD_STATE = 1
 
 # (a): id, options, N, lanes per env
 ROWS = {
+    # eight envs per wave, SW = 8 register slots per lane (point_bare.h); 128 envs: the oracle counts 24 envs without a contact there (arrangement
+    # A needs 15), W = 16 waves >= e = 8
+    "point8": ("PointUMaze-v0", {"lanes_per_env": 8}, 128, 8),
     "point16": ("PointUMaze-v0", {"lanes_per_env": 16}, 64, 16),
     "point32": ("PointUMaze-v0", {"lanes_per_env": 32}, 64, 32),
     "pointpush": ("PointPush-v0", {}, 32, 32),
@@ -146,7 +149,7 @@ def build_case(oracle, cm, key):
     act, nc = act[order], nc[order]
     waves = nc.reshape(-1, e)
     assert (waves[0] == least).all() and waves[1].max() == nc.max() and (waves[1] == least).any()
-    if key in ("point16", "point32"):
+    if key in ("point8", "point16", "point32"):
         assert (nc > 16).sum() >= 3, np.bincount(nc)  # more contacts than the 16 register slots of a row of lanes
     return st, act, nc, least
 
@@ -336,7 +339,7 @@ def test_slot_independence_general_engine(torch):
 
 # ------------------------------------------------------------------ (c) a NaN wave-mate
 POISON_ROWS = {
-    "point16": ("point16", {}), "point32": ("point32", {}), "pointpush": ("pointpush", {}), "antpush": ("antpush", {}), "swimmer": ("swimmer", {}),
+    "point8": ("point8", {}), "point16": ("point16", {}), "point32": ("point32", {}), "pointpush": ("pointpush", {}), "antpush": ("antpush", {}), "swimmer": ("swimmer", {}),
     "ant16wps1": ("ant16wpb2", {"waves_per_simd": 1}), "ant16wps2": ("ant16wpb2", {"waves_per_simd": 2}),
 }
 

@@ -616,10 +616,18 @@ def test_ant_multi_block_mazes(torch, oracle, env_id, nblock):
     env.close()
 
 
-def test_point_step_parity_and_bounce(torch, oracle):
+def _point_step_parity_and_bounce(torch, oracle, lanes):
+    """`lanes`: None (the handle's default: 16 lanes per env at this batch size on a 256-CU device) or the option "lanes_per_env" (8 / 16 / 32: the three
+    instantiations of the bare Point, csrc/point_bare.h — at 8 lanes a lane holds SW = 8 contact slots per round and the 24
+    clipping candidates take three passes).  Returns the step's observations."""
     n = 4096
     env = mm.make("PointUMaze-v0", num_envs=n)
+    if lanes:
+        env.set_option("lanes_per_env", lanes)
+    li = env.launch_info()
+    assert li["lanes_per_env"] == (lanes or (16 if (n + 3) // 4 <= li["device_simds"] else 32)) and li["engine"] == 0, li
     cm = env.model
+    assert cm.c.nblock == 0 and cm.c.nball == 0
     rng = np.random.default_rng(9)
     xmin, xmax, ymin, ymax = cm.world.xy_limits()
     st = dict(qpos=np.stack([rng.uniform(xmin, xmax, n), rng.uniform(ymin, ymax, n), rng.uniform(-3.2, 3.2, n)], 1),
@@ -648,6 +656,12 @@ def test_point_step_parity_and_bounce(torch, oracle):
     assert np.array_equal(rew.cpu().numpy()[free], ref["reward"][free].astype(np.float32))
     assert np.all(done.cpu().numpy()[:8] & 2)
     env.close()
+    return o
+
+
+@pytest.mark.parametrize("lanes", [None, 8, 16, 32], ids=["default", "8", "16", "32"])
+def test_point_step_parity_and_bounce(torch, oracle, lanes):
+    _point_step_parity_and_bounce(torch, oracle, lanes)
 
 
 def test_point_arrow_deep_inside_a_wall(torch, oracle):
@@ -694,7 +708,7 @@ def test_point_arrow_deep_inside_a_wall(torch, oracle):
     env.close()
 
 
-@pytest.mark.parametrize("env_id,nblock", [("PointPush-v0", 1), ("PointPushMaze-v0", 3), ("PointBilliard-v0", 0), ("PointSmallBilliard-v1", 0)])
+@pytest.mark.parametrize("env_id,nblock", [("PointPush-v0", 1), ("PointMultiPush-v0", 2), ("PointPushMaze-v0", 3), ("PointBilliard-v0", 0), ("PointSmallBilliard-v1", 0)])
 def test_point_with_movable_blocks(torch, oracle, env_id, nblock):
     """Point + movable XY blocks (or the Billiard's object ball) on the lane-group planar kernel (32 / 64 lanes per env)."""
     n = 1024

@@ -56,7 +56,8 @@ def _near_goal(env, obs0):
     env.set_state(qpos=qpos)
 
 
-def _twin_check(make, K, seed=11, point=False, expect_done=False, status=True):
+def _twin_check(make, K, seed=11, point=False, expect_done=False, status=True, after_reset=None):
+    """`after_reset(env)`: called on both envs behind the reset (state injection of other robots than the Point)"""
     import torch
 
     ea, eb = make(), make()
@@ -65,6 +66,8 @@ def _twin_check(make, K, seed=11, point=False, expect_done=False, status=True):
         assert _same(oa, ob)
         if point:
             _near_goal(ea, oa); _near_goal(eb, ob)
+        if after_reset:
+            after_reset(ea); after_reset(eb)
         acts = _actions(ea, K, seed + 1, drive=point)
         rows = {k: [] for k in ("obs", "reward", "done", "goal", "pos", "fwd", "ctrl")}
         for k in range(K):

@@ -105,9 +105,10 @@ def _same_state(ea, eb, status_a=None):
 
 
 def _transitions_check(make, K, mode, seed=11, point=False, net="tanh5", critic=None, prepare=None, noise="pre_squash", third=True,
-                       expect_done=True):
+                       expect_done=True, after_reset=None):
     """env A: the defining loop; env B: one call with return_next_obs; env C: the same call without.  Returns (rows of the loop, the
-    call's output, B's launch info, the critic)."""
+    call's output, B's launch info, the critic).  `prepare(env)` runs in front of the reset, `after_reset(env)` behind it (state
+    injection of other robots than the Point; the observation buffer is refreshed afterwards)."""
     import torch
 
     envs = [make() for _ in range(3 if third else 2)]
@@ -118,6 +119,9 @@ def _transitions_check(make, K, mode, seed=11, point=False, net="tanh5", critic=
             o = e.reset(seed=seed)
             if point:
                 _near_goal(e, o)
+                _current_obs(e)
+            if after_reset:
+                after_reset(e)
                 _current_obs(e)
         ea, eb = envs[:2]
         assert _same(ea._obs, eb._obs)

@@ -180,22 +180,36 @@ def test_user_chain_of_another_length(nlink, oracle):
 
 
 @pytest.mark.gpu
-def test_user_chain_on_the_device(oracle):
-    """A five-link chain from user MJCF on the HIP path (swimmer_step_kernel<5, 0>): single-step parity from rollout states."""
+@pytest.mark.parametrize("nlink", [4, 5, 6])
+def test_user_chain_on_the_device(oracle, nlink):
+    """Chains of four, five and six links from user MJCF on the HIP path (swimmer_step_kernel<4, 0, 4>, <5, 0, 8>, <6, 0, 8>):
+    single-step parity from rollout states — random actions up to step 40, then the sustained torques of
+    test_chain_lane_group_form_matches_one_lane_and_oracle, which hold the hinges in their limits: at step 70 the oracle's own state
+    has envs beyond a limit (asserted from it alone), so the limit rows — the structured Cholesky start and the hinge-column
+    refactorisation of the longer chains — are active in the step that is compared."""
     import torch
 
     import mujoco_maze_amd as mm
 
     n = 512
-    env = mm.make("SwimmerUMaze-v0", num_envs=n, robot_xml=chain_swimmer_xml(5))
+    env = mm.make("SwimmerUMaze-v0", num_envs=n, robot_xml=chain_swimmer_xml(nlink))
     cm = env.model
-    assert (env.nq, env.nu, env.obs_dim) == (7, 4, 15)
+    m = cm.c
+    assert (env.nq, env.nu, env.obs_dim) == (nlink + 2, nlink - 1, 2 * (nlink + 2) + 1)
+    li = env.launch_info()
+    assert m.nblock == 0 and m.nbody - 1 - m.nblock == nlink and li["lanes_per_env"] == (4 if nlink <= 4 else 8) and li["engine"] == 0, li
     st, _ = oracle.reset(cm, n, 7)
     rng = np.random.default_rng(2)
-    for k in range(41):
-        act = rng.uniform(-1, 1, (n, 4)).astype(np.float32)
-        if k in (0, 10, 40):
+    lim = np.array([m.jnt_range[3 + k][1] for k in range(nlink - 1)])
+    hold, beyond = None, {}
+    for k in range(71):
+        act = rng.uniform(-1, 1, (n, nlink - 1)).astype(np.float32)
+        if k > 40:  # sustained torques drive the hinges into their limits (drawn behind step 40: the states up to there are unchanged)
+            hold = np.sign(rng.uniform(-1, 1, (n, m.nu))) if hold is None else hold
+            act = (hold * rng.uniform(0.5, 1.5, (n, m.nu))).astype(np.float32)
+        if k in (0, 10, 40, 70):
             s64 = {kk: (v.astype(np.float32).astype(np.float64) if v.dtype == np.float64 else v.copy()) for kk, v in st.items()}
+            beyond[k] = int((np.abs(s64["qpos"][:, 3:]) > lim).any(1).sum())
             env.set_state(s64["qpos"], s64["qvel"], None, s64["t"])
             obs, rew, done, info = env.step(torch.as_tensor(act, device=env.device))
             ref = oracle.step(cm, s64, act.astype(np.float64), nthreads=8)
@@ -204,12 +218,13 @@ def test_user_chain_on_the_device(oracle):
             assert np.abs(obs.cpu().numpy() - ref["obs"]).max() < 2e-5 and np.array_equal(done.cpu().numpy(), ref["done"])
             assert np.abs(rew.cpu().numpy() - ref["reward"]).max() < 1e-5
         oracle.step(cm, st, act.astype(np.float64), nthreads=8)
+    assert beyond[70] > 0, beyond  # hinges beyond their limits at the last checkpoint, by the oracle's state alone
     assert np.all(env.status().cpu().numpy() == 0)
     env.close()
 
 
 # ------------------------------------------------------------------------------------------------ the chain kernel's lane-group branch on CPU
-@pytest.mark.parametrize("robot,nlink", [("swimmer", 3), ("reacher", 2), ("swimmer", 4), ("swimmer", 5)])
+@pytest.mark.parametrize("robot,nlink", [("swimmer", 3), ("reacher", 2), ("swimmer", 4), ("swimmer", 5), ("swimmer", 6)])
 def test_chain_lane_group_form_matches_one_lane_and_oracle(oracle, robot, nlink):
     """swimmer_step_kernel runs the `C::nlanes > 1` branches of csrc/swimmer_dyn.h (lane b = link b: per-lane link constants in ONE
     instruction stream, group sums, the slides' constant corner of M, closed-form limit rows for 2 / 3 links, the structured
