@@ -264,7 +264,9 @@ int32_t mz_nu(const mz_handle* h);
  * "ls_iterations" (Ant solver: evaluations of the exact line search), "ls_fast_iterations" / "ls_fast" (the first n Newton
  * iterations of a solve search the line with at most that many evaluations; defaults 5 / 0: unit steps; "ls_fast_iterations" also
  * sets the Point's float64 solvers; 0 = MuJoCo's search in every iteration, monotone on any maze at ~7 % of the Ant kernel's time:
- * what the host mirror sets for custom tasks, whose stiffness nobody has soaked — the registered mazes are), "lanes_per_env" (8/16/32/64 lanes of a wavefront per environment; defaults: plain Ant 16,
+ * what the host mirror sets for custom tasks, whose stiffness nobody has soaked — the registered mazes are), "lanes_per_env" (8/16/32/64 lanes of a wavefront per environment; 8 on an Ant
+ * with movable blocks or a ball is refused with MZ_ERR_UNSUPPORTED and leaves the handle's width as it was: those kernels exist at 16, 32 and 64 lanes, and
+ * mz_get_info("lanes_per_env") always names the instantiation that steps; defaults: plain Ant 16,
  * Ant with one movable block 32 — 16 for batches beyond 2048 envs, where 32 would mean more waves than the device has SIMDs —, with more blocks / a three-slide block / the ball 64; Point 16 while that leaves every wave a SIMD of its own (up to 4096 envs), else 32; with one block or the ball 32, with two or three blocks 64;
  * Swimmer / Reacher 4, fixed), "waves_per_block" (1/2/4, Ant), "waves_per_simd" (plain Ant at 16 lanes: 1 = the one-wave
  * kernel, 2 = the kernel held to 256 registers so that two waves share a SIMD, 0 = default: by the wave count of the

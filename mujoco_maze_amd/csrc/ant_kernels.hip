@@ -371,22 +371,27 @@ static hipError_t launch_ant_forward(mz_handle* h, hipStream_t st, const float* 
 // per env that it costs at 32 (measured: 8.9 vs 8.1 M env-steps/s; round 1, wait-bound, had it the other way round);
 // 64 with blocks (their contact sets keep 64 lanes busy, and the 2048-env batches of those configs then fill the chip with
 // two waves per SIMD instead of one).
-template <int NB>
-static int ant_lanes(const mz_handle* h);
+static int ant_rung_lanes(const mz_handle* h);
+// From the rung's G to the instantiation: a lane count that has no instantiation for NB is an error here, never another rung's
+// kernel (mz_set_option refuses such a count before it reaches a launch: mzk_ant_lanes_ok)
 template <int NB>
 static hipError_t dispatch_ant_step(mz_handle* h, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, int* gi, float* inf) {
+  const int lanes = ant_rung_lanes(h);
   if constexpr (NB == 0) {
-    if (h->lanes_set && h->lanes == 8) return launch_ant_step<NB, 8>(h, st, a, o, r, d, gi, inf);
+    if (lanes == 8) return launch_ant_step<NB, 8>(h, st, a, o, r, d, gi, inf);
   }
-  const int lanes = ant_lanes<NB>(h);
   if (lanes == 64) return launch_ant_step<NB, 64>(h, st, a, o, r, d, gi, inf);
   if (lanes == 16) return launch_ant_step<NB, 16>(h, st, a, o, r, d, gi, inf);
-  return launch_ant_step<NB, 32>(h, st, a, o, r, d, gi, inf);
+  if (lanes == 32) return launch_ant_step<NB, 32>(h, st, a, o, r, d, gi, inf);
+  return hipErrorNotSupported;
 }
-// lanes per env of the handle: ONE rule for the step and for mz_debug_forward, so that the diagnostic evaluates the very
-// instantiation that steps (8 lanes exist for the plain ant's step only; the forward diagnostic then uses 16)
-template <int NB>
-static int ant_lanes(const mz_handle* h) {
+// The rung of the handle: NB is ant_config(h), G is what this function returns — ONE rule for the step (dispatch_ant_step), for
+// mz_debug_forward (dispatch_ant_forward: the diagnostic evaluates the very instantiation that steps; 8 lanes exist for the plain
+// ant's step only, the forward diagnostic then uses 16) and for mz_get_info (mzk_ant_shape), which therefore reports the G of the
+// instantiation the step launches.  Nineteen rungs: G in {16, 32, 64} for every configuration, and (0, 8).
+static int ant_config(const mz_handle* h);
+static int ant_rung_lanes(const mz_handle* h) {
+  const int NB = ant_config(h);
   // one movable block: the row solver (16 dofs in one DPP row, the block's own contacts spread over the group) at 32 lanes per env
   // — 2048 envs then put exactly one wave on every SIMD; more blocks / the ball: the lane-group solver at 64
   // (the plain ant: 16 at every batch size since the solver's DPP operands were fused, round 3 — 8192 / 16384 / 32768 envs run
@@ -403,10 +408,11 @@ static int ant_lanes(const mz_handle* h) {
 }
 template <int NB>
 static hipError_t dispatch_ant_forward(mz_handle* h, hipStream_t st, const float* a, float* qacc, int* counts) {
-  const int lanes = ant_lanes<NB>(h);
+  const int lanes = ant_rung_lanes(h);
   if (lanes == 64) return launch_ant_forward<NB, 64>(h, st, a, qacc, counts);
   if (lanes == 32) return launch_ant_forward<NB, 32>(h, st, a, qacc, counts);
-  return launch_ant_forward<NB, 16>(h, st, a, qacc, counts);
+  if (lanes == 16 || (NB == 0 && lanes == 8)) return launch_ant_forward<NB, 16>(h, st, a, qacc, counts);  // (the plain ant at 8 lanes: the diagnostic runs at 16)
+  return hipErrorNotSupported;
 }
 
 // MazeTask.reward / termination on rows of observations (parity tests: the instance of task_eval_dev that is inlined into
@@ -474,13 +480,13 @@ hipError_t mzk_ant_forward(mz_handle* h, hipStream_t st, const float* a, float* 
 #endif
 }
 
+// the lane counts that have a step instantiation for the handle's configuration: 16 / 32 / 64, and 8 for the plain ant alone
+int mzk_ant_lanes_ok(const mz_handle* h, int lanes) {
+  return lanes == 16 || lanes == 32 || lanes == 64 || (lanes == 8 && ant_config(h) == 0);
+}
+
 void mzk_ant_shape(const mz_handle* h, int* lanes, int* waves_per_simd) {
-  int l = 16;
-  switch (ant_config(h)) {
-    case 0: l = (h->lanes_set && h->lanes == 8) ? 8 : ant_lanes<0>(h); break;
-    case 1: l = ant_lanes<1>(h); break;
-    default: l = ant_lanes<2>(h); break;  // (one rule for every configuration with more movable bodies)
-  }
+  const int l = ant_rung_lanes(h);
   *lanes = l;
   const int wpb = h->waves_per_block, epb = wpb * 64 / 16;  // launch_ant_step's grid: workgroups of wpb waves, four 16-lane envs per wave
   *waves_per_simd = (ant_config(h) == 0 && l == 16 && ant_two_waves<0, 16>(h, (h->n + epb - 1) / epb * wpb)) ? 2 : 1;

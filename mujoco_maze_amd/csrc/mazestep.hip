@@ -386,6 +386,8 @@ int32_t mz_set_option(mz_handle* h, const char* key, double value) {
   if (!strcmp(key, "lanes_per_env")) {
     int g = (int)value;
     if (g != 8 && g != 16 && g != 32 && g != 64) return set_err(h, MZ_ERR_ARG, "lanes_per_env must be 8, 16, 32 or 64", hipSuccess);
+    if (h->robot == MZ_ROBOT_ANT && !mzk_ant_lanes_ok(h, g))  // no fall-back to another width: launch_info() names the kernel that steps
+      return set_err(h, MZ_ERR_UNSUPPORTED, "mz_set_option: lanes_per_env = 8 exists for the plain Ant only; an Ant with movable blocks or a ball steps at 16, 32 or 64 lanes", hipSuccess);
     h->lanes = g; h->lanes_set = 1;
     return MZ_OK;
   }

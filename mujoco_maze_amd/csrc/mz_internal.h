@@ -76,6 +76,7 @@ hipError_t mzk_ant_task_eval(mz_handle* h, hipStream_t st, int n, const float* o
 
 // launch shape the next mz_step takes (mz_get_info): lanes per env, and for the plain ant at 16 lanes which instantiation (1 / 2 waves per SIMD)
 void mzk_ant_shape(const mz_handle* h, int* lanes, int* waves_per_simd);
+int mzk_ant_lanes_ok(const mz_handle* h, int lanes);  // 1: the Ant ladder has a step instantiation of that lane count for the handle's movable bodies
 int mzk_planar_lanes(const mz_handle* h);
 
 // ---- planar_kernels.hip (Point, Swimmer, Reacher)

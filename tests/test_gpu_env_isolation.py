@@ -1,6 +1,6 @@
 """Env isolation: what an env computes depends on its own state, action, seed and global slot — never on its batch-mates.
 
-Every kernel packs several envs into one wavefront (8, 4 or 2 for the bare Point, 4 or 2 for the Ant, 16 for the Swimmer and Reacher; the chains
+Every kernel packs several envs into one wavefront (8, 4 or 2 for the bare Point, 8, 4 or 2 for the Ant, 16 for the Swimmer and Reacher; the chains
 also 64 into one workgroup, the Ant 2 or 4 waves) and takes wave-uniform shortcuts: `cx.any(ncon > SW)` in point_bare.h, the
 contact-slot guards and the wave-uniform Newton count of ant_newton_rows.h, `gballot` in planar_dyn.h, the in-kernel auto-reset of
 only some lanes.  tests/test_gpu_ant_slot_guards.py holds the contract for the Ant row solver at 16 lanes; this module holds it for
@@ -29,7 +29,19 @@ every engine.  Every assertion is a bit-equality or a precondition derived from 
     never converges costs its wave the cap, not more; contact loops run to staged counts clamped to the buffers (CAP, NC, <= 4 deep
     jobs); cell indices go through mz_cell, or — ant_forward_rows.h, the plain ant's geom_contacts — through the device's
     saturating conversion into loops bounded by themselves and reads that check their index (comments there); the kernels' own
-    indices come from threadIdx / blockIdx and the env count.  NaN converts to cell 0, a cell of the grid: no loop bound there."""
+    indices come from threadIdx / blockIdx and the env count.  NaN converts to cell 0, a cell of the grid: no loop bound there.
+    The lane-group path of csrc/ant_dyn.h (rows ant8 and antmultipush16: ant_forward's last block and ant_solve; 8-lane groups and
+    ants with two or more movable bodies), read the same way: the Newton loop is `while (cx.any(!done) && it < K.max_iter)`, the
+    line search `for (ls < ls_max)` with ls_max one of two options; every loop over contacts runs to s.ncon or between s.cbeg[]
+    entries, and every writer of those clamps to NC (con_map_item, con_fill_item: `tot > NC`, `off < NC ? off : NC`); con_map_item's
+    loop over a geom's count writes only `slot < NC`, con_enum_item's staging only `n < MZ_STAGE`, con_fill_item only
+    `slot < NC && slot < end` — and a geom's count is its number of emits, which the enumerators bound by themselves: constant
+    trip counts (four corners, two capsule ends, two layers, bb.nu / bb.nv of 1 or 2, the blocks below e) around cell ranges that
+    come from mz_cell (a block's own cell part, the ball's and a robot geom's bounding square for NB > 0: NaN gives -2, a range is
+    at most MZ_MAX_GRID + 4 long, cells off the grid are skipped before a row is read) — the plain ant's robot geoms take the
+    saturating conversion described above at every width.  The torso's broad phase (kin_item) is a fixed 3 x 3 ring around an
+    mz_cell.  The kind / block / partner codes a contact row decodes are integers the enumerator wrote, never state.  No site
+    needed a fix."""
 import numpy as np
 import pytest
 
@@ -44,21 +56,35 @@ pytestmark = pytest.mark.gpu
 ALL_NAMES = NAMES + ("goal_index", "info")
 BAD_STATE = 1
 
-# (a): id, options, N, lanes per env
+# (a): id, options, N, lanes per env, keywords of mm.make
 ROWS = {
     # eight envs per wave, SW = 8 register slots per lane (point_bare.h); 128 envs: the oracle counts 24 envs without a contact there (arrangement
     # A needs 15), W = 16 waves >= e = 8
-    "point8": ("PointUMaze-v0", {"lanes_per_env": 8}, 128, 8),
-    "point16": ("PointUMaze-v0", {"lanes_per_env": 16}, 64, 16),
-    "point32": ("PointUMaze-v0", {"lanes_per_env": 32}, 64, 32),
-    "pointpush": ("PointPush-v0", {}, 32, 32),
-    "pointbilliard": ("PointBilliard-v0", {}, 32, 32),
-    "antpush": ("AntPush-v0", {}, 32, 32),
-    "ant16wpb2": ("AntUMaze-v0", {"lanes_per_env": 16, "waves_per_block": 2}, 64, 16),
-    "ant16wpb4": ("AntUMaze-v0", {"lanes_per_env": 16, "waves_per_block": 4}, 64, 16),
-    "swimmer": ("SwimmerUMaze-v0", {}, 256, 4),
-    "reacher": ("ReacherUMaze-v0", {}, 256, 4),
-    "swimmerpush": ("SwimmerPush-v0", {}, 256, 4),
+    "point8": ("PointUMaze-v0", {"lanes_per_env": 8}, 128, 8, {}),
+    "point16": ("PointUMaze-v0", {"lanes_per_env": 16}, 64, 16, {}),
+    "point32": ("PointUMaze-v0", {"lanes_per_env": 32}, 64, 32, {}),
+    "pointpush": ("PointPush-v0", {}, 32, 32, {}),
+    "pointbilliard": ("PointBilliard-v0", {}, 32, 32, {}),
+    "antpush": ("AntPush-v0", {}, 32, 32, {}),
+    "ant16wpb2": ("AntUMaze-v0", {"lanes_per_env": 16, "waves_per_block": 2}, 64, 16, {}),
+    "ant16wpb4": ("AntUMaze-v0", {"lanes_per_env": 16, "waves_per_block": 4}, 64, 16, {}),
+    "swimmer": ("SwimmerUMaze-v0", {}, 256, 4, {}),
+    "reacher": ("ReacherUMaze-v0", {}, 256, 4, {}),
+    "swimmerpush": ("SwimmerPush-v0", {}, 256, 4, {}),
+    # the plain ant with eight envs per wave (the lane-group solver of csrc/ant_dyn.h: 8-lane groups run no row solver), and with two
+    "ant8": ("AntUMaze-v0", {"lanes_per_env": 8}, 128, 8, {}),
+    "ant32": ("AntUMaze-v0", {"lanes_per_env": 32}, 64, 32, {}),
+    # ants with movable bodies that SHARE a wave: four / two envs of the lane-group solver (ant_solve: `while (cx.any(!done) ...)`
+    # keeps a converged env beside its mates' iterations; the re-enumeration on s.con_over runs for some lanes of a wave only).  At
+    # their default of 64 lanes these kernels have a wave per env.  Oracle counts of the recipe below (N = 64, by maze and scale):
+    # MultiPush at 2: least 8 (two blocks at rest) on 36 envs, maximum 21; MultiFall: 4 on 34, 17; SmallBilliard: 1 on 35, 4.
+    # (PushMaze at scale 2 has 3 least-loaded envs, 7 needed: it would be a row at scale 8 only — 48 on 38 envs, maximum 52.)
+    "antmultipush16": ("AntMultiPush-v0", {"lanes_per_env": 16}, 64, 16, {"maze_size_scaling": 2.0}),
+    "antmultipush32": ("AntMultiPush-v0", {"lanes_per_env": 32}, 64, 32, {"maze_size_scaling": 2.0}),
+    "antbilliard16": ("AntSmallBilliard-v0", {"lanes_per_env": 16}, 64, 16, {}),
+    "antmultifall16": ("AntMultiFall-v0", {"lanes_per_env": 16}, 64, 16, {}),
+    # four waves per workgroup: launch_ant_step halves the workgroup until its LDS fits (test_waves_per_block_changes_no_bit)
+    "antmultipush16wpb4": ("AntMultiPush-v0", {"lanes_per_env": 16, "waves_per_block": 4}, 64, 16, {"maze_size_scaling": 2.0}),
 }
 # Points deep inside an inner corner of the U (x = -2 / 10, y = -2 / 10 are wall faces), arrow across the walls: the oracle counts
 # 17 contacts for each (fp32-exact values, found by a random search around the corners on the CPU)
@@ -98,7 +124,7 @@ def _chain_states(oracle, cm, n, seed, steps):
 
 def build_case(oracle, cm, key):
     """CPU only: (start state of arrangement A, actions, oracle counts, least load) of row `key` — preconditions asserted here"""
-    env_id, _, n, lanes = ROWS[key]
+    env_id, _, n, lanes, _ = ROWS[key]
     e = 64 // lanes
     m = cm.c
     rng = np.random.default_rng(17)
@@ -170,8 +196,8 @@ def _step_all(torch, env, start, act):
 
 
 def _make_row(key):
-    env_id, opts, n, lanes = ROWS[key]
-    env = mm.make(env_id, num_envs=n)
+    env_id, opts, n, lanes, kw = ROWS[key]
+    env = mm.make(env_id, num_envs=n, **kw)
     for k, v in opts.items():
         env.set_option(k, v)
     assert env.launch_info()["lanes_per_env"] == lanes, env.launch_info()
@@ -184,7 +210,7 @@ def cases(oracle):
     cache = {}
 
     def get(key, cm):
-        same = ROWS[key][0], ROWS[key][2], ROWS[key][3]  # (the two plain-ant rows differ in a launch option only)
+        same = ROWS[key][0], ROWS[key][2], ROWS[key][3], tuple(sorted(ROWS[key][4].items()))  # (rows that differ in a launch option only share a case)
         if same not in cache:
             cache[same] = build_case(oracle, cm, key)
         return cache[same]
@@ -198,7 +224,7 @@ def _shares(group_a, group_b):
 
 @pytest.mark.parametrize("key", list(ROWS))
 def test_wave_mate_independence(torch, cases, key):
-    env_id, opts, n, lanes = ROWS[key]
+    env_id, opts, n, lanes, _ = ROWS[key]
     e, w = 64 // lanes, n // (64 // lanes)
     env = _make_row(key)
     try:
@@ -225,6 +251,24 @@ def test_wave_mate_independence(torch, cases, key):
         assert np.array_equal(status, status3[to_b])
     finally:
         env.close()
+
+
+def test_waves_per_block_changes_no_bit(torch, cases):
+    """Two-block ants at 16 lanes, one wave and four waves per workgroup (sixteen envs in one workgroup, or as many as its LDS holds:
+    launch_ant_step halves the workgroup until it fits): every output, the state and the status words of one step, bit for bit."""
+    outs = {}
+    for key in ("antmultipush16", "antmultipush16wpb4"):
+        env = _make_row(key)
+        try:
+            start, act, nc, least = cases(key, env.model)
+            outs[key] = _step_all(torch, env, start, act)
+        finally:
+            env.close()
+    (one, status1), (four, status4) = outs["antmultipush16"], outs["antmultipush16wpb4"]
+    for name, a, b in zip(ALL_NAMES, one, four):
+        diff = _bits(a) != _bits(b)
+        assert not diff.any(), f"{name}: {int(diff.reshape(len(a), -1).any(1).sum())} envs step differently in a workgroup of four waves"
+    assert np.array_equal(status1, status4)
 
 
 # ------------------------------------------------------------------ (b) slot independence across auto-reset
@@ -341,13 +385,14 @@ def test_slot_independence_general_engine(torch):
 POISON_ROWS = {
     "point8": ("point8", {}), "point16": ("point16", {}), "point32": ("point32", {}), "pointpush": ("pointpush", {}), "antpush": ("antpush", {}), "swimmer": ("swimmer", {}),
     "ant16wps1": ("ant16wpb2", {"waves_per_simd": 1}), "ant16wps2": ("ant16wpb2", {"waves_per_simd": 2}),
+    "ant8": ("ant8", {}), "antmultipush16": ("antmultipush16", {}),  # the lane-group path (module docstring: its loop bounds)
 }
 
 
 @pytest.mark.parametrize("name", list(POISON_ROWS))
 def test_nan_wave_mate_one_step(torch, cases, name):
     key, extra = POISON_ROWS[name]
-    env_id, opts, n, lanes = ROWS[key]
+    env_id, opts, n, lanes, _ = ROWS[key]
     e = 64 // lanes
     env = _make_row(key)
     try:

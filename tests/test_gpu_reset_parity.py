@@ -65,6 +65,14 @@ for lanes in (16, 32):
 _case("AntMultiPush-v0", "ant", dict(ANT, frac=0.006), n=38)
 _case("AntSmallBilliard-v0", "ant", dict(ANT, frac=0.01, rew=(1e-5, 1e-5)), n=38)
 _case("AntFall-v0", "ant", dict(ANT, frac=0.01), n=38)
+# the in-step reset of step instantiations that no default reaches (every step kernel carries its own copy: DESIGN.md section 3.8; the
+# table of rungs is DESIGN.md section 3.1): n and the family tolerances of the default-width cases above
+_case("AntPush-v0/lanes64", "ant", dict(ANT, frac=0.005), "AntPush-v0", n=38, options={"lanes_per_env": 64})
+for lanes in (16, 32):
+    _case(f"AntMultiPush-v0/lanes{lanes}", "ant", dict(ANT, frac=0.006), "AntMultiPush-v0", n=38, options={"lanes_per_env": lanes})
+_case("AntSmallBilliard-v0/lanes16", "ant", dict(ANT, frac=0.01, rew=(1e-5, 1e-5)), "AntSmallBilliard-v0", n=38, options={"lanes_per_env": 16})
+_case("AntMultiFall-v0", "ant", dict(ANT, frac=0.01), n=38)  # the block on three slides (x, y, z): the 64-lane default
+_case("AntMultiFall-v0/lanes16", "ant", dict(ANT, frac=0.01), "AntMultiFall-v0", n=38, options={"lanes_per_env": 16})
 _case("PointUMaze-v0", "point", POINT_BARE)
 _case("PointUMaze-v0/lanes32", "point", POINT_BARE, "PointUMaze-v0", options={"lanes_per_env": 32})
 for _id in ("PointPush-v0", "PointPushMaze-v0", "PointBilliard-v0", "PointFall-v0"):
