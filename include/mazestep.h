@@ -615,6 +615,53 @@ int32_t mz_net_sample(mz_handle* h, const mz_net* actor, const mz_noise* noise, 
                       void* stream);
 int32_t mz_rollout_ex(mz_handle* h, const mz_rollout_io* io, void* stream);
 
+/* Stochastic actors with a state-dependent log-std head (SAC; PPO code with a second head): the standard deviation is an output of
+ * the network, and the log-probability may be that of the squashed action.  Additive entries: MZ_ABI_VERSION does not change for
+ * them; mz_head carries its own size.
+ *
+ * A head actor is an mz_net whose output layer has 2 nu units — units 0 .. nu - 1 the means m_u, units nu .. 2 nu - 1 the raw
+ * log-stds r_u; packed input-major as above, ... W_out_t [nin][2 nu], b_out [2 nu] — and NO trailing log_std vector:
+ * count = the floats of the network with nout = 2 nu; params_dev [count] (env_stride == 0) or [N, count] (env_stride == count).
+ * Every unit is one lane through one dot product, as above.  In fp32, every operation rounded separately (csrc/mz_policy.h):
+ *     ls_u = r_u < lo ? lo : (r_u > hi ? hi : r_u)         two selects: a NaN passes; lo = -inf / hi = +inf switch a side off
+ *     s = expf(ls_u);  p = s * eps_u;  z_u = m_u + p;  a_u = squash ? A * tanhf(z_u) : z_u                  (MZ_NOISE_PRE_SQUASH)
+ * with eps_u and the key schedule of mz_policy_sample (step k of a rollout draws with noise->step + k; slot: the global env slot).
+ * logp, one lane, u = 0 .. nu - 1 in order:
+ *     q = eps_u * eps_u;  h = -0.5f * q;  t = h - ls_u;  t = t - 0.9189385f;                     (mz_policy_sample's, clamped ls_u)
+ *     logp_squashed:  x = -2.0f * z_u;  ax = fabsf(x);  e = expf(-ax);  l = log1pf(e);  sp = (x > 0.0f ? x : 0.0f) + l;
+ *                     c = 0.6931472f - z_u;  c = c - sp;  c = 2.0f * c;  c = c + logA;  t = t - c;
+ *     acc = acc + t
+ * The correction is log |d(A tanh z) / dz| = log A + 2 (log 2 - z - softplus(-2 z)), finite wherever z is — never log(1 - tanh^2),
+ * which is -inf in fp32 from |z| ~ 9.  logA = logf((float)action_scale) is computed once per call on the host and is exactly 0 for
+ * action_scale == 1.  A NaN log-std unit reaches that unit's action and the row's logp only.  With zero weights into the log-std
+ * units and a bias b inside the bounds the actions and the un-squashed logp are the bits of mz_net_sample with log_std = b; with
+ * lo = -inf and a bias of -inf the actions are the bits of mz_net_act on the means' columns (wherever the mean is not -0).
+ *
+ * mz_net_sample_head: the head actor on the rows of obs_dev; actions_dev [N, nu], logp_dev [N] (nullable).
+ * mz_rollout_head: mz_rollout_ex with a head actor.  The call leaves the handle, every output, the status words and the bound
+ * buffers as this loop would, bit for bit:
+ *     for k:  [mz_net_value]; mz_net_sample_head(noise step + k); mz_step; [mz_net_value of the terminal / new row, as in
+ *             mz_rollout_actor_critic]
+ * Critic, next_obs_seq_dev, a bound normaliser and a bound final_obs buffer compose as in mz_rollout_ex.  Handles with
+ * "rollout_fused" = 1 sample inside the fused rollout kernels — chains of five or six links excepted —; every other handle runs the
+ * loop inside the call.
+ * head == NULL: the two calls ARE mz_net_sample and mz_rollout_ex — the same launches, the same bits.
+ * MZ_ERR_ARG, with a message that names the argument: a wrong head->struct_size, kind or reserved; logp_squashed outside {0, 1}, or
+ * 1 with actor->squash == 0; a NaN bound or log_std_min > log_std_max; a head without an actor or without noise (a head samples);
+ * noise->mode != MZ_NOISE_PRE_SQUASH; an actor->env_stride that is neither 0 nor the head count; and everything mz_net_sample /
+ * mz_rollout_ex refuse.  MZ_ERR_UNSUPPORTED: nu > MZ_POLICY_MAX_HIDDEN.  A refused call leaves the handle as it was. */
+#define MZ_HEAD_STATE_STD 1
+typedef struct mz_head {
+  uint32_t struct_size;      /* sizeof(mz_head); anything else: MZ_ERR_ARG */
+  int32_t kind;              /* MZ_HEAD_STATE_STD */
+  float log_std_min, log_std_max; /* lo, hi of the clamp; -inf / +inf allowed; NaN or lo > hi: MZ_ERR_ARG */
+  int32_t logp_squashed;     /* 0: density of z (as mz_policy_sample); 1: density of the action A * tanh(z); needs squash == 1 */
+  int32_t reserved;          /* 0 */
+} mz_head;
+int32_t mz_net_sample_head(mz_handle* h, const mz_net* actor, const mz_head* head, const mz_noise* noise, const float* obs_dev,
+                           float* actions_dev, float* logp_dev, void* stream);
+int32_t mz_rollout_head(mz_handle* h, const mz_rollout_io* io, const mz_head* head, void* stream);
+
 /* Normalised observations for the device-side networks (the observation half of VecNormalize; ARS-V2's state normalisation), and the
  * forward return scan that reward scaling and episode logging need.  Additive entries: MZ_ABI_VERSION does not change for them.
  *

@@ -27,6 +27,7 @@ SYMBOLS = [
     "mz_net_act", "mz_net_value", "mz_rollout_net",
     "mz_bind_obs_norm", "mz_return_scan",
     "mz_net_sample", "mz_rollout_ex",
+    "mz_net_sample_head", "mz_rollout_head",
 ]
 
 
@@ -76,6 +77,20 @@ class MzRolloutIo(C.Structure):
                 ("obs_dev", C.c_void_p), ("reward_dev", C.c_void_p), ("done_dev", C.c_void_p), ("goal_idx_dev", C.c_void_p),
                 ("info_dev", C.c_void_p), ("obs_seq_dev", C.c_void_p), ("actions_seq_dev", C.c_void_p), ("logp_seq_dev", C.c_void_p),
                 ("value_seq_dev", C.c_void_p), ("next_value_seq_dev", C.c_void_p), ("next_obs_seq_dev", C.c_void_p)]
+
+
+HEAD_STATE_STD = 1  # MZ_HEAD_STATE_STD (include/mazestep.h)
+
+
+class MzHead(C.Structure):
+    """`mz_head` of include/mazestep.h: the state-dependent log-std head of one mz_net_sample_head / mz_rollout_head call."""
+    _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_int32), ("log_std_min", C.c_float), ("log_std_max", C.c_float),
+                ("logp_squashed", C.c_int32), ("reserved", C.c_int32)]
+
+
+def make_head(log_std_min: float, log_std_max: float, logp_squashed: bool = False) -> MzHead:
+    """An MzHead with struct_size and kind set."""
+    return MzHead(C.sizeof(MzHead), HEAD_STATE_STD, float(log_std_min), float(log_std_max), 1 if logp_squashed else 0, 0)
 
 
 def make_noise(mode: int, seed: int, step: int) -> MzNoise:
@@ -175,6 +190,10 @@ def load():
     lib.mz_net_sample.argtypes = [vp, C.POINTER(MzNet), C.POINTER(MzNoise), vp, vp, vp, vp]
     lib.mz_rollout_ex.restype = i32
     lib.mz_rollout_ex.argtypes = [vp, C.POINTER(MzRolloutIo), vp]
+    lib.mz_net_sample_head.restype = i32
+    lib.mz_net_sample_head.argtypes = [vp, C.POINTER(MzNet), C.POINTER(MzHead), C.POINTER(MzNoise), vp, vp, vp, vp]
+    lib.mz_rollout_head.restype = i32
+    lib.mz_rollout_head.argtypes = [vp, C.POINTER(MzRolloutIo), C.POINTER(MzHead), vp]
     lib.mz_bind_obs_norm.restype = i32
     lib.mz_bind_obs_norm.argtypes = [vp, vp, vp, C.c_double, vp]
     lib.mz_return_scan.restype = i32

@@ -120,6 +120,31 @@ __global__ __launch_bounds__(256) void net_act_kernel(int n, int obs_dim, int nu
   }
 }
 
+// net_act_kernel for an actor with a state-dependent log-std head (mz_net_sample_head; mz_rollout_head where it steps launch by launch):
+// the same groups and LDS rows, the output layer 2 nu units wide, mzp_group_net_sample_head of mz_policy.h.  A kernel of its own: the
+// two instantiations of net_act_kernel compile as they did.
+template <bool NRM = false>
+__global__ __launch_bounds__(256) void net_sample_head_kernel(int n, int obs_dim, int nu, mzp_shape s, int squash, float action_scale, mzp_head hd,
+                                                              const float* __restrict__ params, long pstride, uint64_t key, uint64_t env0,
+                                                              const float* __restrict__ obs, float* __restrict__ actions, float* __restrict__ logp,
+                                                              mzp_norm nm) {
+  __shared__ float hid[256 / MZ_POLICY_LANES][MZ_NET_MAX_HIDDEN_LAYERS][MZ_POLICY_MAX_HIDDEN];
+  const int l = (int)threadIdx.x % MZ_POLICY_LANES, grp = (int)threadIdx.x / MZ_POLICY_LANES;
+  size_t row = (size_t)blockIdx.x * (256 / MZ_POLICY_LANES) + grp;
+  const bool live = row < (size_t)n;
+  if (!live) row = (size_t)n - 1;
+  if constexpr (NRM) {
+    __shared__ float xn[256 / MZ_POLICY_LANES][MZ_MAX_OBS + MZ_VIEW_DIM];
+    mzp_group_norm(l, MZ_POLICY_LANES, nm, obs_dim, obs + row * obs_dim, xn[grp]);
+    mzp_wave_sync();
+    mzp_group_net_sample_head(l, MZ_POLICY_LANES, params + row * pstride, obs_dim, nu, s, squash, action_scale, hd, key, env0 + row, xn[grp],
+                              hid[grp][0], hid[grp][1], actions + row * nu, live, live && logp ? logp + row : nullptr);
+  } else {
+    mzp_group_net_sample_head(l, MZ_POLICY_LANES, params + row * pstride, obs_dim, nu, s, squash, action_scale, hd, key, env0 + row,
+                              obs + row * obs_dim, hid[grp][0], hid[grp][1], actions + row * nu, live, live && logp ? logp + row : nullptr);
+  }
+}
+
 // value_kernel for a critic of shape s (mz_net_value; mz_rollout_net where it steps launch by launch); NRM as in net_act_kernel: the
 // row that is staged is the one the critic values, the final_obs row where the env finished
 template <bool NRM = false>
@@ -714,8 +739,10 @@ int32_t mz_value(mz_handle* h, const float* vparams_dev, int64_t env_stride, int
 }
 
 // the checks the three mz_net entries share; `which`: the argument's name ("actor" / "critic"), nout: nu or 1, stochastic: the
-// vector carries log_std[nu] behind the network.  MZ_OK or MZ_ERR_ARG with the message set.
-static int net_args(mz_handle* h, const char* who, const char* which, const mz_net* net, int nout, bool stochastic, bool is_critic) {
+// vector carries log_std[nu] behind the network — unless `head`: the output layer is 2 nu units wide and nothing follows it.
+// MZ_OK or MZ_ERR_ARG with the message set.
+static int net_args(mz_handle* h, const char* who, const char* which, const mz_net* net, int nout, bool stochastic, bool is_critic,
+                    bool head = false) {
   char msg[200];
   auto fail = [&](const char* field, const char* why) {
     snprintf(msg, sizeof(msg), "%s: %s%s %s", who, which, field, why);
@@ -733,10 +760,12 @@ static int net_args(mz_handle* h, const char* who, const char* which, const mz_n
   if (net->squash != 0 && net->squash != 1) return fail("->squash", "must be 0 or 1");
   if (is_critic && net->squash != 0) return fail("->squash", "must be 0: a critic is never squashed");
   if (!net->params_dev) return fail("->params_dev", "is NULL");
-  const int64_t count = (int64_t)mzp_net_param_count(h->model.obs_dim, nout, mzp_shape{net->n_hidden, net->hidden[0], net->hidden[1], net->activation}) +
-                        (stochastic ? h->model.nu : 0);
+  const int64_t count = (int64_t)mzp_net_param_count(h->model.obs_dim, head ? 2 * nout : nout,
+                                                     mzp_shape{net->n_hidden, net->hidden[0], net->hidden[1], net->activation}) +
+                        (stochastic && !head ? h->model.nu : 0);
   if (net->env_stride != 0 && net->env_stride != count)
-    return fail("->env_stride", stochastic ? "must be 0 (one shared network) or count (one per env; log_std[nu] behind the network counts)"
+    return fail("->env_stride", head ? "must be 0 (one shared network) or the head count (one per env; an output layer of 2 nu units, no log_std behind it)"
+                                : stochastic ? "must be 0 (one shared network) or count (one per env; log_std[nu] behind the network counts)"
                                            : "must be 0 (one shared network) or count (one per env)");
   return MZ_OK;
 }
@@ -817,6 +846,59 @@ int32_t mz_net_sample(mz_handle* h, const mz_net* actor, const mz_noise* noise, 
   return MZ_OK;
 }
 
+// the checks mz_net_sample_head and mz_rollout_head share, on a head that is not NULL: the struct, then what it asks of the actor and
+// the noise (both may be NULL here: a head samples).  MZ_OK, MZ_ERR_ARG or MZ_ERR_UNSUPPORTED with the message set.
+static int head_args(mz_handle* h, const char* who, const mz_head* head, const mz_net* actor, const mz_noise* noise, bool in_io) {
+  char msg[200];
+  const char* why = nullptr;
+  int code = MZ_ERR_ARG;
+  if (head->struct_size != sizeof(mz_head)) why = "head->struct_size must be sizeof(mz_head)";
+  else if (head->kind != MZ_HEAD_STATE_STD) why = "head->kind must be MZ_HEAD_STATE_STD (1)";
+  else if (head->reserved != 0) why = "head->reserved must be 0";
+  else if (head->logp_squashed != 0 && head->logp_squashed != 1) why = "head->logp_squashed must be 0 or 1";
+  else if (head->log_std_min != head->log_std_min || head->log_std_max != head->log_std_max) why = "head->log_std_min / log_std_max must not be NaN";
+  else if (head->log_std_min > head->log_std_max) why = "head->log_std_min must not exceed head->log_std_max";
+  else if (!actor) why = in_io ? "a head needs an actor: io->actor is NULL" : "a head needs an actor: actor is NULL";
+  else if (!noise) why = in_io ? "a head samples: io->noise is NULL" : "a head samples: noise is NULL";
+  else if (noise->struct_size == sizeof(mz_noise) && noise->mode != MZ_NOISE_PRE_SQUASH) why = "noise->mode must be MZ_NOISE_PRE_SQUASH (0) with a head";
+  else if (head->logp_squashed && actor->struct_size == sizeof(mz_net) && actor->squash == 0) why = "head->logp_squashed needs actor->squash == 1";
+  else if (h->model.nu > MZ_POLICY_MAX_HIDDEN) { why = "a head needs nu <= MZ_POLICY_MAX_HIDDEN (64)"; code = MZ_ERR_UNSUPPORTED; }
+  if (!why) return MZ_OK;
+  snprintf(msg, sizeof(msg), "%s: %s", who, why);
+  return set_err(h, code, msg, hipSuccess);
+}
+
+static void net_sample_head_launch(mz_handle* h, hipStream_t st, const mz_net* actor, const mz_head* head, float logA, uint64_t noise_seed,
+                                   uint64_t noise_step, const float* obs_dev, float* actions_dev, float* logp_dev) {
+  const int rows = 256 / MZ_POLICY_LANES;
+  const mzp_norm nm{h->nrm_mean, h->nrm_inv_std, h->nrm_clip};
+  const mzp_head hd{head->log_std_min, head->log_std_max, head->logp_squashed, logA};
+#define MZ_NET_HEAD(NRM)                                                                                                                          \
+  hipLaunchKernelGGL(net_sample_head_kernel<NRM>, dim3((unsigned)((h->n + rows - 1) / rows)), dim3(256), 0, st, h->n, h->model.obs_dim, h->model.nu, \
+                     net_shape(actor), actor->squash, (float)actor->action_scale, hd, actor->params_dev, (long)actor->env_stride,                  \
+                     mzp_noise_key(noise_seed, noise_step), h->env0, obs_dev, actions_dev, logp_dev, nm)
+  if (h->nrm_mean) MZ_NET_HEAD(true); else MZ_NET_HEAD(false);
+#undef MZ_NET_HEAD
+}
+
+// mz_net_sample for an actor with a state-dependent log-std head (include/mazestep.h); head == NULL: mz_net_sample itself
+int32_t mz_net_sample_head(mz_handle* h, const mz_net* actor, const mz_head* head, const mz_noise* noise, const float* obs_dev,
+                           float* actions_dev, float* logp_dev, void* stream) {
+  if (!h) return MZ_ERR_ARG;
+  if (!head) return mz_net_sample(h, actor, noise, obs_dev, actions_dev, logp_dev, stream);
+  if (!obs_dev || !actions_dev) return set_err(h, MZ_ERR_ARG, "mz_net_sample_head: null array", hipSuccess);
+  int rc = head_args(h, "mz_net_sample_head", head, actor, noise, false);
+  if (rc != MZ_OK) return rc;
+  rc = noise_args(h, "mz_net_sample_head", noise);
+  if (rc != MZ_OK) return rc;
+  rc = net_args(h, "mz_net_sample_head", "actor", actor, h->model.nu, true, false, true);
+  if (rc != MZ_OK) return rc;
+  DeviceScope scope(h->device);
+  net_sample_head_launch(h, (hipStream_t)stream, actor, head, logf((float)actor->action_scale), noise->seed, noise->step, obs_dev, actions_dev, logp_dev);
+  HIPCHK(h, hipGetLastError());
+  return MZ_OK;
+}
+
 // ------------------------------------------------------------------ rollouts: six entries, one plan (mz_internal.h), one driver
 // row k of next_obs_seq_dev on a handle that steps launch by launch: behind the step's launches, before anything overwrites obs_dev or
 // the final_obs row (the caller has checked that final_obs is bound under auto-reset)
@@ -831,7 +913,8 @@ static hipError_t next_obs_row(mz_handle* h, hipStream_t st, const float* obs_de
 static void rollout_act_launch(mz_handle* h, hipStream_t st, const RolloutPlan& p, bool one_layer, size_t k, float* actions) {
   const mz_net* a = p.actor;
   float* logp = p.logp_seq_dev ? p.logp_seq_dev + k * (size_t)h->n : NULL;
-  if (!one_layer) net_act_launch(h, st, a, p.sample, p.noise_seed, p.noise_step + k, p.obs_dev, actions, logp, p.noise_mode);
+  if (p.head) net_sample_head_launch(h, st, a, p.head, p.head_logA, p.noise_seed, p.noise_step + k, p.obs_dev, actions, logp);
+  else if (!one_layer) net_act_launch(h, st, a, p.sample, p.noise_seed, p.noise_step + k, p.obs_dev, actions, logp, p.noise_mode);
   else if (p.sample)
     policy_sample_launch(h, st, a->params_dev, a->env_stride, a->hidden[0], a->squash, (float)a->action_scale, p.noise_seed, p.noise_step + k, p.obs_dev,
                          actions, logp);
@@ -866,7 +949,9 @@ static int32_t rollout_run(mz_handle* h, const RolloutPlan& plan, void* stream) 
   // the first step (tests/test_gpu_planar_ladder.py found it; the cause is not known, the source is the five-link kernel's, which agrees
   // by bits).  Its open-loop kernel and every kernel of the shorter chains agree with stepping by bits and stay fused.
   const bool six_link_policy = p.actor && h->robot == MZ_ROBOT_SWIMMER && h->swimmer.nlink == 6;
-  if (mzk_planar_rollout_fused(h) && !six_link_policy) {
+  // A head plan on a five- or six-link chain runs the loop too: their fused kernels compile without the head's branch (planar_kernels.hip).
+  const bool long_chain_head = p.head && h->robot == MZ_ROBOT_SWIMMER && h->swimmer.nlink >= 5;
+  if (mzk_planar_rollout_fused(h) && !six_link_policy && !long_chain_head) {
     HIPCHK(h, mzk_planar_rollout(h, st, p));
     if (h->record) {  // the last step's row
       const size_t tot = n * (od + 2), last = (size_t)(p.n_steps - 1) * n;
@@ -939,9 +1024,9 @@ static int net_rollout_args(mz_handle* h, const RolloutPlan& p) {
   if (p.sample != 0 && p.sample != 1) return set_err(h, MZ_ERR_ARG, "mz_rollout_net: sample must be 0 or 1", hipSuccess);
   int rc = rollout_args(h, p);
   if (rc != MZ_OK) return rc;
-  rc = net_args(h, "mz_rollout_net", "actor", p.actor, h->model.nu, p.sample != 0, false);
+  rc = net_args(h, p.who, "actor", p.actor, h->model.nu, p.sample != 0, false, p.head != nullptr);
   if (rc != MZ_OK || !p.critic) return rc;
-  rc = net_args(h, "mz_rollout_net", "critic", p.critic, 1, false, true);
+  rc = net_args(h, p.who, "critic", p.critic, 1, false, true);
   if (rc != MZ_OK) return rc;
   if (p.next_value_seq_dev && h->auto_reset && !h->final_obs)
     return set_err(h, MZ_ERR_ARG, "mz_rollout_net: next_value_seq_dev under auto-reset needs a bound final_obs buffer (mz_bind_final_obs): "
@@ -1031,25 +1116,38 @@ int32_t mz_rollout_net(mz_handle* h, int32_t n_steps, const mz_net* actor, int32
 
 // mz_rollout / mz_rollout_net behind one struct, with the per-step pre-reset rows and the noise mode (include/mazestep.h).  The
 // checks here are those the struct adds; everything else is refused as by the entry the call stands for, whose plan it fills.
-int32_t mz_rollout_ex(mz_handle* h, const mz_rollout_io* io, void* stream) {
+static int32_t rollout_ex(mz_handle* h, const mz_rollout_io* io, const mz_head* head, void* stream);
+int32_t mz_rollout_ex(mz_handle* h, const mz_rollout_io* io, void* stream) { return rollout_ex(h, io, NULL, stream); }
+// mz_rollout_ex with a state-dependent log-std head on the actor (include/mazestep.h); head == NULL: mz_rollout_ex itself
+int32_t mz_rollout_head(mz_handle* h, const mz_rollout_io* io, const mz_head* head, void* stream) { return rollout_ex(h, io, head, stream); }
+
+static int32_t rollout_ex(mz_handle* h, const mz_rollout_io* io, const mz_head* head, void* stream) {
   if (!h) return MZ_ERR_ARG;
-  if (!io) return set_err(h, MZ_ERR_ARG, "mz_rollout_ex: io is NULL", hipSuccess);
-  if (io->struct_size != sizeof(mz_rollout_io)) return set_err(h, MZ_ERR_ARG, "mz_rollout_ex: io->struct_size must be sizeof(mz_rollout_io)", hipSuccess);
-  if (io->actions_dev && io->actor)
-    return set_err(h, MZ_ERR_ARG, "mz_rollout_ex: both io->actions_dev and io->actor are given: exactly one is the action source", hipSuccess);
-  if (!io->actions_dev && !io->actor)
-    return set_err(h, MZ_ERR_ARG, "mz_rollout_ex: neither io->actions_dev nor io->actor is given: exactly one is the action source", hipSuccess);
-  if (!io->actor && io->noise) return set_err(h, MZ_ERR_ARG, "mz_rollout_ex: io->noise without io->actor", hipSuccess);
-  if (!io->actor && io->critic) return set_err(h, MZ_ERR_ARG, "mz_rollout_ex: io->critic without io->actor", hipSuccess);
+  // a refusal names the entry the caller used: with a head that is mz_rollout_head, for the io-level checks and for the plan's
+  const char* who = head ? "mz_rollout_head" : "mz_rollout_ex";
+  auto fail = [&](const char* why) {
+    char msg[224];
+    snprintf(msg, sizeof(msg), "%s: %s", who, why);
+    return set_err(h, MZ_ERR_ARG, msg, hipSuccess);
+  };
+  if (!io) return fail("io is NULL");
+  if (io->struct_size != sizeof(mz_rollout_io)) return fail("io->struct_size must be sizeof(mz_rollout_io)");
+  if (io->actions_dev && io->actor) return fail("both io->actions_dev and io->actor are given: exactly one is the action source");
+  if (!io->actions_dev && !io->actor) return fail("neither io->actions_dev nor io->actor is given: exactly one is the action source");
+  if (!io->actor && io->noise) return fail("io->noise without io->actor");
+  if (!io->actor && io->critic) return fail("io->critic without io->actor");
+  if (head) {
+    const int rc = head_args(h, who, head, io->actor, io->noise, true);
+    if (rc != MZ_OK) return rc;
+  }
   if (io->noise) {
-    const int rc = noise_args(h, "mz_rollout_ex", io->noise);
+    const int rc = noise_args(h, who, io->noise);
     if (rc != MZ_OK) return rc;
   }
   if (io->next_obs_seq_dev && h->auto_reset && !h->final_obs)
-    return set_err(h, MZ_ERR_ARG, "mz_rollout_ex: next_obs_seq_dev under auto-reset needs a bound final_obs buffer (mz_bind_final_obs): "
-                                  "the contract is the same on every handle", hipSuccess);
-  RolloutPlan p = rollout_plan(io->actor ? "mz_rollout_net" : "mz_rollout", io->n_steps, io->obs_dev, io->reward_dev, io->done_dev, io->goal_idx_dev,
-                               io->info_dev, io->obs_seq_dev);
+    return fail("next_obs_seq_dev under auto-reset needs a bound final_obs buffer (mz_bind_final_obs): the contract is the same on every handle");
+  RolloutPlan p = rollout_plan(head ? who : (io->actor ? "mz_rollout_net" : "mz_rollout"), io->n_steps, io->obs_dev, io->reward_dev, io->done_dev,
+                               io->goal_idx_dev, io->info_dev, io->obs_seq_dev);
   p.next_obs_seq_dev = io->next_obs_seq_dev;
   if (!io->actor) {
     p.actions_dev = io->actions_dev; p.action_step_stride = (long)io->action_step_stride;
@@ -1057,6 +1155,7 @@ int32_t mz_rollout_ex(mz_handle* h, const mz_rollout_io* io, void* stream) {
     p.actor = io->actor; p.critic = io->critic; p.value_seq_dev = io->value_seq_dev; p.next_value_seq_dev = io->next_value_seq_dev;
     p.actions_seq_dev = io->actions_seq_dev; p.logp_seq_dev = io->logp_seq_dev;
     if (io->noise) { p.sample = 1; p.noise_seed = io->noise->seed; p.noise_step = io->noise->step; p.noise_mode = io->noise->mode; }
+    if (head) { p.head = head; p.head_logA = logf((float)io->actor->action_scale); }
   }
   const int rc = io->actor ? net_rollout_args(h, p) : open_loop_args(h, p);
   return rc != MZ_OK ? rc : rollout_run(h, p, stream);

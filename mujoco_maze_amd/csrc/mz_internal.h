@@ -119,6 +119,10 @@ struct RolloutPlan {
   uint8_t* done_dev;
   int32_t* goal_idx_dev;
   float *info_dev, *obs_seq_dev, *actions_seq_dev, *logp_seq_dev, *next_obs_seq_dev;
+  // a state-dependent log-std head on the actor (mz_rollout_head; NULL: none) and logf((float)actor->action_scale), computed once by the
+  // entry
+  const mz_head* head;
+  float head_logA;
 };
 
 // The kernels a closed-loop plan runs: what every entry launched before there was a plan, and what it must go on launching.
@@ -131,14 +135,16 @@ struct RolloutPlan {
 //     one tanh hidden layer, no normaliser             |   / net_value_kernel<false>               |
 //   any other shape, no normaliser                     | the same net kernels                      | DEEP
 //   normaliser bound (any entry)                       | net_*_kernel<true>                        | DEEP + NRM
+//   a head on the actor (mz_rollout_head)              | net_sample_head_kernel<NRM>               | SMP + DEEP + EXT (+ NRM)
 //
-// EXT exactly when next_obs_seq is given or a sampled call uses MZ_NOISE_ACTION; an open-loop plan reads `ext` alone.
+// EXT exactly when next_obs_seq is given, a sampled call uses MZ_NOISE_ACTION or the actor has a head (whose fields travel beside the
+// noise mode and are read by the SMP + DEEP + EXT instantiations alone); an open-loop plan reads `ext` alone.
 struct RolloutKernels { bool one_layer, deep, nrm, ext; };
 inline RolloutKernels mzk_rollout_kernels(const mz_handle* h, const RolloutPlan& p) {
   auto shallow = [](const mz_net* net) { return !net || (net->n_hidden <= 1 && net->activation == MZ_ACT_TANH); };
   const bool nrm = h->nrm_mean != nullptr;
-  return RolloutKernels{p.legacy && !nrm, nrm || !shallow(p.actor) || !shallow(p.critic), nrm,
-                        p.next_obs_seq_dev || (p.sample && p.noise_mode != MZ_NOISE_PRE_SQUASH)};
+  return RolloutKernels{p.legacy && !nrm, nrm || p.head || !shallow(p.actor) || !shallow(p.critic), nrm,
+                        p.next_obs_seq_dev || p.head || (p.sample && p.noise_mode != MZ_NOISE_PRE_SQUASH)};
 }
 // the plan on the fused kernels: launches of at most MZ_ROLLOUT_CHUNK steps with the launch geometry and the instantiation of the step
 // kernel they stand for — the open-loop kernels for a tensor of actions, else the policy kernels' SMP / CRT / DEEP / NRM / EXT

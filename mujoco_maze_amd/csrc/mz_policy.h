@@ -263,6 +263,84 @@ MZP_HD float mzp_net_value_row(const float* vpar, int obs_dim, mzp_shape s, cons
   return mzp_net_output_pre(vpar, obs_dim, 1, s, mzp_net_hidden_row(vpar, obs_dim, s, x, hid1, hid2), 0);
 }
 
+// ------------------------------------------------------------------ a state-dependent log-std head (mz_net_sample_head / mz_rollout_head)
+// A head actor is a network of shape s whose output layer has 2 nu units: units 0 .. nu - 1 are the means m_u, units nu .. 2 nu - 1 the
+// raw log-stds r_u — W_out_t [nin][2 nu], b_out [2 nu]; mzp_net_param_count(obs_dim, 2 nu, s) floats, no trailing log_std.  Every unit
+// is one lane through mzp_dot, as everywhere above.  In fp32, every operation rounded separately:
+//   ls_u = r_u < lo ? lo : (r_u > hi ? hi : r_u)                two selects: a NaN passes, lo = -inf / hi = +inf switch a side off
+//   z_u  = m_u + expf(ls_u) * eps_u;  a_u = squash ? A * tanhf(z_u) : z_u        mzp_sample_unit's operations in MZ_NOISE_PRE_SQUASH, written
+//                                                               once more so that z_u is at hand (mzp_head_z, mzp_head_action); eps, key as above
+//   logp = sum over u, in order, of t_u:
+//          q = eps_u * eps_u;  h = -0.5f * q;  t = h - ls_u;  t = t - 0.9189385f                  (mzp_logp's, with the clamped ls_u)
+//          logp_squashed: the density of the action A tanh(z), log |d(A tanh z) / dz| = log A + 2 (log 2 - z - softplus(-2 z)):
+//            x = -2.0f * z_u;  ax = fabsf(x);  e = expf(-ax);  l = log1pf(e);  sp = (x > 0.0f ? x : 0.0f) + l
+//            c = 0.6931472f - z_u;  c = c - sp;  c = 2.0f * c;  c = c + logA;  t = t - c
+// logA = logf(A) is computed once per call on the host and handed to every kernel of the call.  Never log(1 - tanh^2), which is -inf
+// in fp32 from |z| ~ 9.  t_u is a pure function of the row, the parameters and four integers, so the lane that owns unit u computes
+// it and the group's first lane adds the nu terms in order: the bits of one lane computing everything (mzp_net_sample_head_row).
+typedef struct mzp_head {
+  float lo, hi;       // the clamp of the raw log-std
+  int logp_squashed;  // 0: density of z; 1: density of A * tanh(z)
+  float logA;         // logf((float)action_scale), from the host
+} mzp_head;
+
+MZP_HD float mzp_head_clamp(float r, float lo, float hi) { return r < lo ? lo : (r > hi ? hi : r); }
+
+// z_u and the action from it: together the operations of mzp_sample_unit in MZ_NOISE_PRE_SQUASH, so the same bits (pinned by the
+// constant-head tests: tests/test_sac_head_api.py, tests/test_gpu_sac_head.py)
+MZP_HD float mzp_head_z(float m, float ls, float eps) {
+#pragma clang fp contract(off) reassociate(off)
+  const float s = expf(ls);
+  const float p = s * eps;
+  return m + p;
+}
+MZP_HD float mzp_head_action(float z, int squash, float action_scale) { return squash ? action_scale * tanhf(z) : z; }
+
+// t_u (the head of this section)
+MZP_HD float mzp_head_logp_term(float eps, float ls, float z, int logp_squashed, float logA) {
+#pragma clang fp contract(off) reassociate(off)
+  const float q = eps * eps;
+  const float h = -0.5f * q;
+  float t = h - ls;
+  t = t - 0.9189385f;
+  if (logp_squashed) {
+    const float x = -2.0f * z;
+    const float ax = fabsf(x);
+    const float e = expf(-ax);
+    const float l = log1pf(e);
+    const float sp = (x > 0.0f ? x : 0.0f) + l;
+    float c = 0.6931472f - z;
+    c = c - sp;
+    c = 2.0f * c;
+    c = c + logA;
+    t = t - c;
+  }
+  return t;
+}
+
+MZP_HD float mzp_head_logp_add(float acc, float t) {
+#pragma clang fp contract(off) reassociate(off)
+  return acc + t;
+}
+
+// THE head actor: act[nu] and *logp (nullable) of one row
+MZP_HD void mzp_net_sample_head_row(const float* par, int obs_dim, int nu, mzp_shape s, int squash, float action_scale, mzp_head hd,
+                                    uint64_t noise_seed, uint64_t noise_step, uint64_t slot, const float* x, float* act, float* logp) {
+  float hid1[MZ_POLICY_MAX_HIDDEN], hid2[MZ_POLICY_MAX_HIDDEN];
+  const uint64_t key = mzp_noise_key(noise_seed, noise_step);
+  const float* in = mzp_net_hidden_row(par, obs_dim, s, x, hid1, hid2);
+  float acc = 0.0f;
+  for (int u = 0; u < nu; u++) {
+    const float m = mzp_net_output_pre(par, obs_dim, 2 * nu, s, in, u);
+    const float ls = mzp_head_clamp(mzp_net_output_pre(par, obs_dim, 2 * nu, s, in, nu + u), hd.lo, hd.hi);
+    const float eps = mzp_eps(key, slot, u);
+    const float z = mzp_head_z(m, ls, eps);
+    act[u] = mzp_head_action(z, squash, action_scale);
+    acc = mzp_head_logp_add(acc, mzp_head_logp_term(eps, ls, z, hd.logp_squashed, hd.logA));
+  }
+  if (logp) *logp = acc;
+}
+
 #if defined(__HIPCC__)
 // hand-off between the lanes of a group inside one wavefront (the DevCtx::sync of mz_device.h: LDS operations of a wavefront
 // execute in order, so a wavefront-scope fence that pins the compiler's ordering is a complete phase boundary)
@@ -372,6 +450,31 @@ __device__ __forceinline__ void mzp_group_net_act(int l, int G, const float* par
     if (store) act[u] = a;
   }
   if (sample && l == 0 && logp) *logp = mzp_logp(ls, nu, key, slot);
+}
+
+// mzp_net_sample_head_row on a group: lanes 0 .. nu - 1 own unit u's mean, raw log-std, eps, action and log-prob term t_u; the terms go
+// to the group's first lane through the hidden row the output layer does not read (`hid` behind two hidden layers, else `hid2`: the
+// phase boundary behind the last hidden layer has retired its readers; nu <= MZ_POLICY_MAX_HIDDEN), which adds them in order and
+// stores *logp unless that is NULL.  The caller hands `act` over, and both hidden rows stay untouched until then.
+__device__ __forceinline__ void mzp_group_net_sample_head(int l, int G, const float* par, int obs_dim, int nu, mzp_shape s, int squash,
+                                                          float action_scale, mzp_head hd, uint64_t key, uint64_t slot, const float* x, float* hid,
+                                                          float* hid2, float* act, bool store, float* logp) {
+  mzp_group_net_hidden(l, G, par, obs_dim, s, x, hid, hid2);
+  float* terms = s.n_hidden == 2 ? hid : hid2;
+  for (int u = l; u < nu; u += G) {
+    const float m = mzp_group_net_pre(par, obs_dim, 2 * nu, s, x, hid, hid2, u);
+    const float ls = mzp_head_clamp(mzp_group_net_pre(par, obs_dim, 2 * nu, s, x, hid, hid2, nu + u), hd.lo, hd.hi);
+    const float eps = mzp_eps(key, slot, u);
+    const float z = mzp_head_z(m, ls, eps);
+    if (store) act[u] = mzp_head_action(z, squash, action_scale);
+    terms[u] = mzp_head_logp_term(eps, ls, z, hd.logp_squashed, hd.logA);
+  }
+  mzp_wave_sync();
+  if (l == 0 && logp) {
+    float acc = 0.0f;
+    for (int u = 0; u < nu; u++) acc = mzp_head_logp_add(acc, terms[u]);
+    *logp = acc;
+  }
 }
 
 // mzp_group_value for a network of shape s: `hid` and `hid2` may be the rows the actor used, under the rule of mzp_group_value

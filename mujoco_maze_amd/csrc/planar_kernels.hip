@@ -243,6 +243,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && 
   }
 }
 
+// mzp_group_net_sample_head for the fused kernels, NOT inlined: inlined, the second sampling path cost every SMP + DEEP + EXT
+// instantiation about 25 AGPRs (the bare Point at 32 lanes: 100 bytes of scratch per lane) and the calls without a head 3 % on the
+// Point; behind a call the callers keep their registers to within a few AGPRs (profiles/rollout/sac_head.md).  The pointers arrive
+// as generic ones (hid, hid2 and act are LDS, x is LDS or global memory), which only the head path pays for; the arithmetic is the
+// header's, so the bits are those of net_sample_head_kernel (mazestep.hip).  Every lane of the wavefront makes the call (ns.head is
+// uniform), act is always stored.
+__device__ __attribute__((noinline)) void planar_head_act(int l, int G, const float* par, int obs_dim, int nu, mzp_shape s, int squash, float action_scale,
+                                                          mzp_head hd, uint64_t key, uint64_t slot, const float* x, float* hid, float* hid2, float* act,
+                                                          float* logp) {
+  mzp_group_net_sample_head(l, G, par, obs_dim, nu, s, squash, action_scale, hd, key, slot, x, hid, hid2, act, true, logp);
+}
+
 // planar_rollout_kernel with the actions computed on chip (mz_rollout_policy): before every step the group evaluates the policy of
 // mz_policy.h on the fp32 observation row in `o` — for the launch's first step the row of `obs` (what the previous launch, mz_step or
 // mz_reset wrote there), afterwards the row the step before computed, after an in-kernel auto-reset the new episode's t = 0 row — with
@@ -258,6 +270,8 @@ struct PolicyNoise {
   uint64_t seed, step;  // noise_seed; noise_step of the launch's first step
   float* logp_seq;      // [nsteps][n] rows of the launch (nullable)
   int mode;             // MZ_NOISE_* (mz_policy.h mzp_sample_unit), read by the EXT instantiations alone
+  int head;             // 1: the actor has the state-dependent log-std head `hd` (mz_rollout_head; mz_policy.h mzp_group_net_sample_head), its
+  mzp_head hd;          //    output layer 2 nu units wide; both read by the SMP + DEEP + EXT instantiations alone, where every head plan goes
 };
 // CRT (mz_rollout_actor_critic with a critic): the group also evaluates the critic of mz_policy.h (mzp_group_value: the unit functions
 // value_kernel, mazestep.hip, runs) on the rows in `o` — at the launch's start on its first row; after every step on the row the step
@@ -289,6 +303,10 @@ struct PolicyShapes {
 // predicate, every observation store and info read `o`.  NRM == false compiles the source as it was and never reads `nm`.
 // EXT (mz_rollout_ex with next_obs_seq_dev or MZ_NOISE_ACTION): as in planar_rollout_kernel, and the sampled actions are formed in
 // the mode ns.mode.  EXT == false compiles the source as it was: it never reads next_obs_seq, and samples in MZ_NOISE_PRE_SQUASH.
+// A head actor (mz_rollout_head: ns.head) is a run-time branch of the SMP + DEEP + EXT instantiations — planar_head_act above:
+// mzp_group_net_sample_head, the unit functions net_sample_head_kernel (mazestep.hip) runs, in place of mzp_group_net_act; the
+// log-prob terms go to the group's first lane through the hidden row the output layer does not read, which nothing rewrites before
+// the hand-over of pact.
 template <int NB, int NS, int G, bool SMP = false, bool CRT = false, bool DEEP = false, bool NRM = false, bool EXT = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && NS == 0 && G == 32) ? 2 : 1))) void planar_policy_rollout_kernel(
     const PointDev* __restrict__ Pp, int n, PointState S, int nsteps, const float* __restrict__ params, long pstride, int hidden, int squash,
@@ -340,7 +358,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 0 && 
     const size_t row = (size_t)step * n + env;
     cx.sync();  // the row in o is complete (CRT: and the critic is done with phid)
     if constexpr (CRT) { if (live && cx.l == 0 && cr.value_seq) cr.value_seq[row] = vcur; }
-    if constexpr (NRM)
+    bool head = false;  // (a run-time branch of the SMP + DEEP + EXT instantiations: no instantiation of its own)
+    if constexpr (SMP && DEEP && EXT) head = ns.head != 0;
+    if (head) {
+      if constexpr (SMP && DEEP && EXT) {
+        const float* xin;
+        if constexpr (NRM) xin = pnrm[grp]; else xin = o;
+        planar_head_act(cx.l, G, par, NOBS, 2, sh.actor, squash, action_scale, ns.hd, mzp_noise_key(ns.seed, ns.step + (uint64_t)step),
+                        env0 + (uint64_t)env, xin, phid[grp][0], phid[grp][1], pact[grp], live && ns.logp_seq ? ns.logp_seq + row : nullptr);
+      }
+    } else if constexpr (NRM)
       mzp_group_net_act(cx.l, G, par, NOBS, 2, sh.actor, squash, action_scale, SMP, SMP ? mzp_noise_key(ns.seed, ns.step + (uint64_t)step) : 0,
                         env0 + (uint64_t)env, pnrm[grp], phid[grp][0], phid[grp][DEEP ? 1 : 0], pact[grp], true,
                         SMP && live && ns.logp_seq ? ns.logp_seq + row : nullptr, EXT ? ns.mode : MZ_NOISE_PRE_SQUASH);
@@ -719,7 +746,16 @@ __global__ __launch_bounds__(256) void swimmer_policy_rollout_kernel(const Swimm
     const size_t row = (size_t)step * n + env;
     mzp_wave_sync();  // the row in x is complete (CRT: and the critic is done with phid)
     if constexpr (CRT) { if (live && cr.value_seq) cr.value_seq[row] = vcur; }
-    if constexpr (DEEP)
+    // (as in planar_policy_rollout_kernel; NL <= 4: the five- and six-link kernels need all 512 registers and spill on top of them, and
+    // with the branch compiled in <5, 0, 8, SMP, CRT, DEEP, , EXT> left its defining loop WITHOUT a head — tests/test_gpu_planar_ladder.py —
+    // so they compile their source as it was and rollout_run, mazestep.hip, runs the loop for a head plan on such a chain)
+    bool head = false;
+    if constexpr (SMP && DEEP && EXT && NL <= 4) head = ns.head != 0;
+    if (head) {
+      if constexpr (SMP && DEEP && EXT && NL <= 4)
+        planar_head_act(cx.l, G, par, NO, NH, sh.actor, squash, action_scale, ns.hd, mzp_noise_key(ns.seed, ns.step + (uint64_t)step),
+                        env0 + (uint64_t)env, x, phid[grp][0], phid[grp][1], pact[grp], live && ns.logp_seq ? ns.logp_seq + row : nullptr);
+    } else if constexpr (DEEP)
       mzp_group_net_act(cx.l, G, par, NO, NH, sh.actor, squash, action_scale, SMP, SMP ? mzp_noise_key(ns.seed, ns.step + (uint64_t)step) : 0,
                         env0 + (uint64_t)env, x, phid[grp][0], phid[grp][DEEP ? 1 : 0], pact[grp], true,
                         SMP && live && ns.logp_seq ? ns.logp_seq + row : nullptr, EXT ? ns.mode : MZ_NOISE_PRE_SQUASH);
@@ -1000,7 +1036,7 @@ static hipError_t flag_switch(F&& f, bool flag, Rest... rest) {
 //   CRT   cr: the critic's parameters and the launch's value_seq / next_value_seq rows (else zeros);
 //   DEEP  sh: both networks' shapes; `hidden` and cr.hidden are 0 — else sh is zeros and the two carry the one hidden width each;
 //   NRM   (DEEP with a normaliser bound) nm: the handle's normaliser;
-//   EXT   nseq: the launch's next_obs_seq rows (nullable), and ns.mode is honoured.
+//   EXT   nseq: the launch's next_obs_seq rows (nullable), and ns.mode is honoured — with SMP and DEEP also ns.head / ns.hd, the plan's head.
 template <bool POL, bool SMP, bool CRT, bool DEEP, bool NRM, bool EXT>
 static hipError_t rollout_launches(mz_handle* h, hipStream_t st, const RolloutPlan& p) {
   PointState S{h->state, h->pt_t, h->pt_ep, h->pt_rec};
@@ -1036,8 +1072,10 @@ static hipError_t rollout_launches(mz_handle* h, hipStream_t st, const RolloutPl
         });
     } else {
       float* aseq = p.actions_seq_dev ? p.actions_seq_dev + k0 * n * nu : nullptr;
-      const PolicyNoise ns = SMP ? PolicyNoise{p.noise_seed, p.noise_step + (uint64_t)k0, p.logp_seq_dev ? p.logp_seq_dev + k0 * n : nullptr, p.noise_mode}
-                                 : PolicyNoise{0, 0, nullptr, 0};
+      const mzp_head hd = p.head ? mzp_head{p.head->log_std_min, p.head->log_std_max, p.head->logp_squashed, p.head_logA} : mzp_head{0.0f, 0.0f, 0, 0.0f};
+      const PolicyNoise ns = SMP ? PolicyNoise{p.noise_seed, p.noise_step + (uint64_t)k0, p.logp_seq_dev ? p.logp_seq_dev + k0 * n : nullptr, p.noise_mode,
+                                               p.head ? 1 : 0, hd}
+                                 : PolicyNoise{0, 0, nullptr, 0, 0, hd};
       const PolicyCritic cr = CRT ? PolicyCritic{C->params_dev, (long)C->env_stride, DEEP ? 0 : C->hidden[0],
                                                  p.value_seq_dev ? p.value_seq_dev + k0 * n : nullptr,
                                                  p.next_value_seq_dev ? p.next_value_seq_dev + k0 * n : nullptr}

@@ -522,13 +522,13 @@ class VecMazeEnv:
         widths, act = policy.net_shape(hidden, activation, what)
         return widths, act, bool(np.ndim(hidden) == 0 and act == 0)
 
-    def _policy_params(self, params, hidden, stochastic: bool = False):
+    def _policy_params(self, params, hidden, stochastic: bool = False, log_std: str = "param"):
         """params as a contiguous float32 device tensor [npar] or [N, npar] (stochastic: npar_s = npar + nu, log_std behind the
-        network); returns (tensor, param_env_stride)."""
+        network; log_std="state": the head count, an output layer of 2 nu units); returns (tensor, param_env_stride)."""
         from mujoco_maze_amd import policy
 
         torch = self._torch
-        npar = policy.param_count(self.obs_dim, self.nu, hidden, stochastic)
+        npar = policy.param_count(self.obs_dim, self.nu, hidden, stochastic, log_std)
         p = params if torch.is_tensor(params) else torch.as_tensor(np.asarray(params, dtype=np.float32), device=self.device)
         if p.dtype != torch.float32 or not p.is_contiguous() or p.device != self.device:
             p = p.to(device=self.device, dtype=torch.float32).contiguous()
@@ -604,8 +604,24 @@ class VecMazeEnv:
             step = int(noise_step)
         return C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), C.c_uint64(step & 0xFFFFFFFFFFFFFFFF)
 
+    def _head(self, log_std, log_std_bounds, squashed_logp, squash, mode):
+        """The MzHead of `log_std="state"` (None for "param", where squashed_logp is refused)."""
+        from mujoco_maze_amd import policy
+
+        if not policy._log_std_kind(log_std):
+            if squashed_logp:
+                raise ValueError("squashed_logp needs log_std='state'")
+            return None
+        if mode != _capi.NOISE_PRE_SQUASH:
+            raise ValueError("log_std='state' needs noise='pre_squash'")
+        if squashed_logp and not squash:
+            raise ValueError("squashed_logp needs squash=True: it is the density of action_scale * tanh(z)")
+        lo, hi = policy.head_bounds(log_std_bounds)
+        return _capi.make_head(float(lo), float(hi), bool(squashed_logp))
+
     def policy_sample(self, params, obs=None, hidden=0, squash: bool = False, action_scale: float = 1.0, noise_seed: Optional[int] = None,
-                      noise_step: Optional[int] = None, activation: str = "tanh", noise: str = "pre_squash"):
+                      noise_step: Optional[int] = None, activation: str = "tanh", noise: str = "pre_squash", log_std: str = "param",
+                      log_std_bounds=(-20.0, 2.0), squashed_logp: bool = False):
         """One draw from a diagonal-Gaussian policy on the device (mz_policy_sample): (actions [N, nu], logp [N]).  params: float32
         [npar_s] or [N, npar_s], the vector of `policy_act` followed by log_std [nu] (`policy.pack(..., log_std=)`).  With m the
         network's pre-squash output, a = m + exp(log_std) * eps, or action_scale * tanh(.) of that with `squash`; logp is the density
@@ -620,16 +636,29 @@ class VecMazeEnv:
 
         noise="action" (TD3 / DDPG exploration, mz_net_sample): the noise goes on the action instead of through the squash —
         a = clip(action_scale * tanh(m) + exp(log_std) * eps, +-action_scale) with `squash`; without it the two modes are the same.
-        eps and logp are those of the default "pre_squash" (logp: the density of the unclipped sum around the deterministic action)."""
+        eps and logp are those of the default "pre_squash" (logp: the density of the unclipped sum around the deterministic action).
+
+        log_std="state" (SAC; mz_net_sample_head): the standard deviation is an output of the network.  params: float32 [count_h] or
+        [N, count_h], a network whose output layer has 2 nu units — the means, then the raw log-stds — and no log_std vector
+        (`policy.pack_mlp(.., log_std_head=)`, `policy.param_count(.., log_std="state")`); the raw log-std is clamped to
+        `log_std_bounds` (lo, hi; -inf / inf switch a side off).  squashed_logp (needs `squash`): logp is the density of the squashed
+        action action_scale * tanh(z) — the tanh correction applied on the device in a form that stays finite wherever z is — which
+        is the sample SAC's entropy term takes.  `policy.sample_reference(.., log_std="state")` is the numpy model."""
         mode = _capi.noise_mode(noise)
+        head = self._head(log_std, log_std_bounds, squashed_logp, squash, mode)
         widths, act, legacy = self._net_kind(hidden, activation)
-        p, stride = self._policy_params(params, hidden, stochastic=True)
+        p, stride = self._policy_params(params, hidden, stochastic=True, log_std=log_std)
         o = self._obs if obs is None else self._policy_obs(obs)
         torch = self._torch
         out = torch.empty((self.num_envs, self.nu), dtype=torch.float32, device=self.device)
         logp = torch.empty(self.num_envs, dtype=torch.float32, device=self.device)
         seed, step = self._noise_args(noise_seed, noise_step, 1)
-        if mode != _capi.NOISE_PRE_SQUASH:
+        if head is not None:
+            net = _capi.make_net(_ptr(p), stride, widths, act, squash, action_scale)
+            nz = _capi.make_noise(mode, seed.value, step.value)
+            rc = self._lib.mz_net_sample_head(self._h, C.byref(net), C.byref(head), C.byref(nz), _ptr(o), _ptr(out), _ptr(logp), self._stream())
+            _capi.check(self._lib, self._h, rc, "mz_net_sample_head")
+        elif mode != _capi.NOISE_PRE_SQUASH:
             net = _capi.make_net(_ptr(p), stride, widths, act, squash, action_scale)
             nz = _capi.make_noise(mode, seed.value, step.value)
             rc = self._lib.mz_net_sample(self._h, C.byref(net), C.byref(nz), _ptr(o), _ptr(out), _ptr(logp), self._stream())
@@ -647,7 +676,8 @@ class VecMazeEnv:
     def rollout_policy_sample(self, params, steps: int, hidden=0, squash: bool = False, action_scale: float = 1.0, obs=None,
                               noise_seed: Optional[int] = None, noise_step: Optional[int] = None, return_obs: bool = False,
                               return_actions: bool = False, value_params=None, value_hidden=0, gae=None, activation: str = "tanh",
-                              value_activation: str = "tanh", noise: str = "pre_squash", return_next_obs: bool = False):
+                              value_activation: str = "tanh", noise: str = "pre_squash", return_next_obs: bool = False,
+                              log_std: str = "param", log_std_bounds=(-20.0, 2.0), squashed_logp: bool = False):
         """K = `steps` closed-loop steps with a sampled action each, in one call: exactly what K times (`policy_sample` with
         noise_step + k, `step`) give, state and outputs bit for bit.  Everything as in `rollout_policy`, plus info["logp"] [K, N], the
         log-probabilities of the draws (see `policy_sample`); info["actions"] [K, N, nu] with `return_actions` holds the sampled
@@ -671,9 +701,16 @@ class VecMazeEnv:
 
         noise as in `policy_sample` ("action": TD3 / DDPG exploration), return_next_obs as in `rollout`: either makes the call one
         mz_rollout_ex, which runs the same kernels.  Together they collect an off-policy batch in one call: s = the entry observation
-        followed by "observations"[:-1], a = "actions", r, s' = "next_observations", terminated = dones & 1."""
+        followed by "observations"[:-1], a = "actions", r, s' = "next_observations", terminated = dones & 1.
+
+        log_std="state" / log_std_bounds / squashed_logp as in `policy_sample` (a SAC actor): one mz_rollout_head call — sampled
+        inside the fused rollout kernels of the Point, Swimmer and Reacher (chains of five or six links excepted), a loop of the head
+        kernel and the step's launches inside the call on every other handle —, bit for bit what K times
+        (`policy_sample(log_std="state")`, `step`) give; info["logp"] is then the entropy term's sample.  Critic, return_next_obs, a
+        bound normaliser compose as above."""
         return self._rollout_closed_loop(True, params, steps, hidden, squash, action_scale, obs, noise_seed, noise_step, return_obs,
-                                         return_actions, value_params, value_hidden, gae, activation, value_activation, return_next_obs, noise)
+                                         return_actions, value_params, value_hidden, gae, activation, value_activation, return_next_obs, noise,
+                                         log_std, log_std_bounds, squashed_logp)
 
     def _value_params(self, value_params, hidden):
         """A critic's parameters as a contiguous float32 device tensor [nvpar] or [N, nvpar]; returns (tensor, env_stride)."""
@@ -774,20 +811,22 @@ class VecMazeEnv:
 
     def _rollout_closed_loop(self, sample: bool, params, steps, hidden, squash, action_scale, obs, noise_seed, noise_step, return_obs,
                              return_actions, value_params, value_hidden, gae, activation="tanh", value_activation="tanh",
-                             return_next_obs=False, noise="pre_squash"):
+                             return_next_obs=False, noise="pre_squash", log_std="param", log_std_bounds=(-20.0, 2.0), squashed_logp=False):
         """rollout_policy (sample False) / rollout_policy_sample (sample True): the defining loop where the host has work between
-        steps, else one C call — mz_rollout_ex with return_next_obs or noise="action"; mz_rollout_net where a network, actor or
-        critic, needs mz_net; mz_rollout_actor_critic with a critic; mz_rollout_policy_sample / mz_rollout_policy without one."""
+        steps, else one C call — mz_rollout_head with log_std="state"; mz_rollout_ex with return_next_obs or noise="action";
+        mz_rollout_net where a network, actor or critic, needs mz_net; mz_rollout_actor_critic with a critic; mz_rollout_policy_sample /
+        mz_rollout_policy without one."""
         torch, n = self._torch, self.num_envs
         mode = _capi.noise_mode(noise)
-        extended = return_next_obs or mode != _capi.NOISE_PRE_SQUASH
+        head = self._head(log_std, log_std_bounds, squashed_logp, squash, mode) if sample else None
+        extended = return_next_obs or mode != _capi.NOISE_PRE_SQUASH or head is not None
         with_critic = value_params is not None
         if gae is not None and not with_critic:
             raise ValueError("gae=(gamma, lam) needs a critic: pass value_params")
         if gae is not None:
             gamma, lam = (float(x) for x in gae)
         widths, act, legacy = self._net_kind(hidden, activation)
-        p, stride = self._policy_params(params, hidden, stochastic=sample)
+        p, stride = self._policy_params(params, hidden, stochastic=sample, log_std=log_std if sample else "param")
         if with_critic:
             vwidths, vact, vlegacy = self._net_kind(value_hidden, value_activation, "the critic's hidden")
             vp, vstride = self._value_params(value_params, value_hidden)
@@ -811,7 +850,8 @@ class VecMazeEnv:
                 if with_critic:
                     buf["values"][k] = self.value(vp, None, value_hidden, value_activation)
                 if sample:
-                    a, buf["logp"][k] = self.policy_sample(p, None, hidden, squash, action_scale, seed.value, step.value + k, activation, noise)
+                    a, buf["logp"][k] = self.policy_sample(p, None, hidden, squash, action_scale, seed.value, step.value + k, activation, noise,
+                                                           log_std, log_std_bounds, squashed_logp)
                 else:
                     a = self.policy_act(p, None, hidden, squash, action_scale, activation)
                 o, rew, done, inf = self.step(a)
@@ -839,8 +879,12 @@ class VecMazeEnv:
                                        value_seq_dev=_ptr(buf["values"]) if with_critic else None,
                                        next_value_seq_dev=_ptr(buf["next_values"]) if with_critic else None,
                                        next_obs_seq_dev=_ptr(buf["next_obs_seq"]) if return_next_obs else None)
-            rc = self._lib.mz_rollout_ex(self._h, C.byref(io), self._stream())
-            _capi.check(self._lib, self._h, rc, "mz_rollout_ex")
+            if head is not None:
+                rc = self._lib.mz_rollout_head(self._h, C.byref(io), C.byref(head), self._stream())
+                _capi.check(self._lib, self._h, rc, "mz_rollout_head")
+            else:
+                rc = self._lib.mz_rollout_ex(self._h, C.byref(io), self._stream())
+                _capi.check(self._lib, self._h, rc, "mz_rollout_ex")
         elif not legacy:
             actor = _capi.make_net(_ptr(p), stride, widths, act, squash, action_scale)
             critic = _capi.make_net(_ptr(vp), vstride, vwidths, vact) if with_critic else None

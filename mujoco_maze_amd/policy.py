@@ -45,6 +45,17 @@ Normalised observations (VecMazeEnv.bind_obs_norm, mz_bind_obs_norm): while a no
 on `normalize_reference(obs, mean, inv_std, clip)` — bit-equal to the device — so the model of a bound call is
 `reference(params, normalize_reference(obs, mean, inv_std, clip), ...)`, and likewise for `sample_reference` / `value_reference`.
 `return_scan_reference` is the forward scan of VecMazeEnv.return_scan / mz_return_scan (csrc/mz_returns.h), bit-equal too.
+
+State-dependent log-std heads (`log_std="state"`; mz_net_sample_head / mz_rollout_head; SAC): the output layer has 2 nu units — the
+means, then the raw log-stds — and no log_std vector follows (`param_count(..., log_std="state")`, `pack_mlp(..,
+log_std_head=(W, b))`).  `sample_reference(..., log_std="state", log_std_bounds=(lo, hi), squashed_logp=)`:
+
+    ls_u = lo if r_u < lo else (hi if r_u > hi else r_u)              two selects: NaN passes
+    z_u = m_u + exp(ls_u) * eps_u;  action_u as above;  logp's term t_u as above with ls_u, and with squashed_logp
+    x = -2 z_u;  sp = (x if x > 0 else 0) + log1p(exp(-|x|));  c = 2 * ((0.6931472 - z_u) - sp) + logA;  t_u = t_u - c
+
+float32, every operation rounded separately, logA = log(float32(action_scale)) rounded to float32: the density of the squashed
+action, finite wherever z is.  `mean_actor` cuts the deterministic actor (the means' columns) out of a head vector.
 """
 import numpy as np
 
@@ -71,10 +82,22 @@ def net_shape(hidden=0, activation: str = "tanh", what: str = "hidden"):
     return widths, ACTIVATIONS.index(activation)
 
 
-def param_count(obs_dim: int, nu: int, hidden=0, stochastic: bool = False) -> int:
+LOG_STD_KINDS = ("param", "state")
+
+
+def _log_std_kind(log_std: str) -> bool:
+    """True for a state-dependent head."""
+    if log_std not in LOG_STD_KINDS:
+        raise ValueError(f"log_std must be 'param' or 'state', got {log_std!r}")
+    return log_std == "state"
+
+
+def param_count(obs_dim: int, nu: int, hidden=0, stochastic: bool = False, log_std: str = "param") -> int:
     """Floats of one policy; with `stochastic` the network's count plus log_std [nu].  hidden: an int or a sequence of one or two
-    widths."""
+    widths.  log_std="state": a head actor — an output layer of 2 nu units and nothing behind it (`stochastic` is not read)."""
     obs_dim, nu = int(obs_dim), int(nu)
+    if _log_std_kind(log_std):
+        nu, stochastic = 2 * nu, False
     sizes = (obs_dim,) + net_shape(hidden)[0] + (nu,)
     return sum(a * b + b for a, b in zip(sizes[:-1], sizes[1:])) + (nu if stochastic else 0)
 
@@ -114,11 +137,22 @@ def pack(W1, b1, W2, b2, log_std=None):
     return _with_log_std([W1.T.ravel(), b1, W2.T.ravel(), b2], W2.shape[0], log_std)
 
 
-def pack_mlp(layers, log_std=None):
+def pack_mlp(layers, log_std=None, log_std_head=None):
     """A network of 0, 1 or 2 hidden layers from 1 .. 3 `(W, b)` pairs in nn.Linear orientation, first layer first: W [out, in],
     b [out] -> float32 [count], every layer as W.T then b; with `log_std` [nu] the stochastic policy's vector, nu numbers longer.
-    One pair is `pack_linear`, two pairs are `pack`."""
+    One pair is `pack_linear`, two pairs are `pack`.  `log_std_head=(W [nu, nin], b [nu])`: the second nn.Linear of a SAC actor, whose
+    rows are appended to the last layer's — the head actor's output layer of 2 nu units (not together with `log_std`)."""
     pairs = [(_np(W), _np(b)) for W, b in layers]
+    if log_std_head is not None:
+        if log_std is not None:
+            raise ValueError("log_std and log_std_head exclude each other: a head actor has no log_std vector")
+        if not pairs:
+            raise ValueError(f"layers must hold 1 .. {MAX_HIDDEN_LAYERS + 1} (W, b) pairs, got 0")
+        Wh, bh = _np(log_std_head[0]), _np(log_std_head[1])
+        Wm, bm = pairs[-1]
+        if Wh.shape != Wm.shape or bh.shape != bm.shape:
+            raise ValueError(f"log_std_head: want W {Wm.shape} and b {bm.shape} like the last layer's, got {Wh.shape} and {bh.shape}")
+        pairs[-1] = (np.concatenate([Wm, Wh], axis=0), np.concatenate([bm, bh]))
     if not 1 <= len(pairs) <= MAX_HIDDEN_LAYERS + 1:
         raise ValueError(f"layers must hold 1 .. {MAX_HIDDEN_LAYERS + 1} (W, b) pairs, got {len(pairs)}")
     for k, (W, b) in enumerate(pairs):
@@ -150,6 +184,23 @@ def _pre_squash(x, p, nu, shape):
             return acc
         # hidden units: tanh, or the select of mzp_activate (no rounding, -0.0 and NaN pass)
         h = np.where(acc < 0, np.float32(0.0), acc).astype(np.float32) if act else np.tanh(acc).astype(np.float32)
+
+
+def mean_actor(params, obs_dim: int, nu: int, hidden=0):
+    """The deterministic actor inside a head vector: params [count_h] or [R, count_h] with count_h = param_count(obs_dim, nu, hidden,
+    log_std="state") -> float32 [count] or [R, count], count = param_count(obs_dim, nu, hidden): every hidden layer as it is, the
+    means' columns of the output layer and their biases.  What `rollout_policy` evaluates a trained SAC actor with."""
+    p = np.asarray(_np(params))
+    obs_dim, nu = int(obs_dim), int(nu)
+    ch, widths = param_count(obs_dim, nu, hidden, log_std="state"), net_shape(hidden)[0]
+    if p.shape[-1:] != (ch,) or p.ndim not in (1, 2):
+        raise ValueError(f"params must have shape {(ch,)} or [R, {ch}], got {p.shape}")
+    nin = widths[-1] if widths else obs_dim
+    body = ch - (nin * 2 * nu + 2 * nu)
+    lead = p.shape[:-1]
+    W = p[..., body: body + nin * 2 * nu].reshape(lead + (nin, 2 * nu))[..., :nu].reshape(lead + (nin * nu,))
+    b = p[..., body + nin * 2 * nu: body + nin * 2 * nu + nu]
+    return np.ascontiguousarray(np.concatenate([p[..., :body], W, b], axis=-1), dtype=np.float32)
 
 
 def _squashed(acc, squash, action_scale):
@@ -217,16 +268,26 @@ _eps = noise  # (sample_reference has an argument of that name)
 
 
 def sample_reference(params, obs, nu: int, hidden=0, squash: bool = False, action_scale: float = 1.0, noise_seed: int = 0,
-                     noise_step: int = 0, slots=None, activation: str = "tanh", noise: str = "pre_squash"):
+                     noise_step: int = 0, slots=None, activation: str = "tanh", noise: str = "pre_squash", log_std: str = "param",
+                     log_std_bounds=(-20.0, 2.0), squashed_logp: bool = False):
     """The stochastic policy of csrc/mz_policy.h on rows of observations: obs [R, obs_dim] (or [obs_dim]); params [npar_s] shared by
     the rows or [R, npar_s]; slots: the rows' global env slots, default 0 .. R - 1.  Returns (actions float32 [R, nu], logp float32
     [R]) — or ([nu], scalar) for a single row.
 
     noise="pre_squash" (MZ_NOISE_PRE_SQUASH): z = m + s * eps, a = action_scale * tanh(z) with `squash`.  noise="action"
     (MZ_NOISE_ACTION, TD3 / DDPG exploration): b = action_scale * tanh(m) with `squash` else m, z = b + s * eps, and with `squash`
-    a = z clipped to +-action_scale by two selects (NaN passes).  eps and logp are the same in both modes."""
+    a = z clipped to +-action_scale by two selects (NaN passes).  eps and logp are the same in both modes.
+
+    log_std="state" (mz_net_sample_head): params [count_h] or [R, count_h], count_h = param_count(.., log_std="state"); the raw
+    log-stds are output units nu .. 2 nu - 1, clamped to log_std_bounds by two selects; squashed_logp: logp is the density of the
+    squashed action (needs `squash`; the head of this module).  Needs noise="pre_squash"."""
     if noise not in ("pre_squash", "action"):
         raise ValueError(f"noise must be 'pre_squash' or 'action', got {noise!r}")
+    if _log_std_kind(log_std):
+        return _sample_head_reference(params, obs, nu, hidden, squash, action_scale, noise_seed, noise_step, slots, activation, noise,
+                                      log_std_bounds, squashed_logp)
+    if squashed_logp:
+        raise ValueError("squashed_logp needs log_std='state'")
     x = np.asarray(obs, dtype=np.float32)
     single = x.ndim == 1
     x = np.atleast_2d(x)
@@ -256,6 +317,65 @@ def sample_reference(params, obs, nu: int, hidden=0, squash: bool = False, actio
             t = ((np.float32(-0.5) * q).astype(np.float32) - ls[:, u]).astype(np.float32)
             t = (t - np.float32(0.9189385)).astype(np.float32)
             logp = (logp + t).astype(np.float32)
+    return (act[0], logp[0]) if single else (act, logp)
+
+
+def head_bounds(log_std_bounds):
+    """(lo, hi) of a head's clamp as float32: -inf / +inf allowed, NaN or lo > hi refused."""
+    try:
+        lo, hi = (np.float32(v) for v in log_std_bounds)
+    except (TypeError, ValueError):
+        raise ValueError(f"log_std_bounds must be a pair (lo, hi), got {log_std_bounds!r}") from None
+    if np.isnan(lo) or np.isnan(hi) or lo > hi:
+        raise ValueError(f"log_std_bounds must be (lo, hi) with lo <= hi and no NaN, got {log_std_bounds!r}")
+    return lo, hi
+
+
+def _sample_head_reference(params, obs, nu, hidden, squash, action_scale, noise_seed, noise_step, slots, activation, noise, log_std_bounds,
+                           squashed_logp):
+    if noise != "pre_squash":
+        raise ValueError("log_std='state' needs noise='pre_squash'")
+    if squashed_logp and not squash:
+        raise ValueError("squashed_logp needs squash=True: it is the density of action_scale * tanh(z)")
+    lo, hi = head_bounds(log_std_bounds)
+    x = np.asarray(obs, dtype=np.float32)
+    single = x.ndim == 1
+    x = np.atleast_2d(x)
+    p = np.asarray(params, dtype=np.float32)
+    R, od, nu, shape = x.shape[0], x.shape[1], int(nu), net_shape(hidden, activation)
+    ch = param_count(od, nu, hidden, log_std="state")
+    if p.shape not in ((ch,), (R, ch)):
+        raise ValueError(f"params must have shape {(ch,)} or {(R, ch)} (an output layer of 2 nu units), got {p.shape}")
+    sl = np.arange(R) if slots is None else np.atleast_1d(np.asarray(slots, dtype=object)).ravel()
+    if len(sl) != R:
+        raise ValueError(f"slots must name one global env slot per row ({R}), got {len(sl)}")
+    eps = _eps(noise_seed, noise_step, sl, nu)
+    f = np.float32
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        out = _pre_squash(x, p, 2 * nu, shape)
+        m, r = out[:, :nu], out[:, nu:]
+        ls = np.where(r < lo, lo, np.where(r > hi, hi, r)).astype(f)
+        s = np.exp(ls.astype(np.float64)).astype(f)
+        z = (m + (s * eps).astype(f)).astype(f)
+        act = _squashed(z, squash, action_scale)
+        logA = np.log(np.float64(f(action_scale))).astype(f)
+        logp = np.zeros(R, dtype=f)
+        for u in range(nu):
+            q = (eps[:, u] * eps[:, u]).astype(f)
+            t = ((f(-0.5) * q).astype(f) - ls[:, u]).astype(f)
+            t = (t - f(0.9189385)).astype(f)
+            if squashed_logp:
+                zu = z[:, u]
+                xx = (f(-2.0) * zu).astype(f)
+                e = np.exp(-np.abs(xx).astype(np.float64)).astype(f)
+                l = np.log1p(e.astype(np.float64)).astype(f)
+                sp = (np.where(xx > 0, xx, f(0.0)).astype(f) + l).astype(f)
+                c = (f(0.6931472) - zu).astype(f)
+                c = (c - sp).astype(f)
+                c = (f(2.0) * c).astype(f)
+                c = (c + logA).astype(f)
+                t = (t - c).astype(f)
+            logp = (logp + t).astype(f)
     return (act[0], logp[0]) if single else (act, logp)
 
 

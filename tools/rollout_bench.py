@@ -27,6 +27,11 @@ env.step + torch.where(done, final_observation, obs)) with the rows kept — the
 return_next_obs —; one env.rollout_policy_sample(..., return_obs, return_actions, return_next_obs); and the same call without the next
 rows beside them.  --noise action puts the noise on the action in every leg (TD3 / DDPG exploration; log_std = log(0.1) on every unit).
     python tools/rollout_bench.py --policy 64,64 --activation relu --sample --next-obs --noise action --steps 128 --ids PointUMaze-v0,SwimmerUMaze-v0,AntUMaze-v0
+With --policy H --head state one SAC collection window: the actor's output layer carries the raw log-stds (clamped to (-20, 2); the
+second nn.Linear of a SAC actor, small weights, bias -0.5), squashed actions, and with --squashed-logp the log-probability of the
+squashed action.  K x (env.policy_sample(log_std="state") + env.step + torch.where on the terminal rows) with the rows kept against
+one env.rollout_policy_sample(..., log_std="state", return_obs, return_actions, return_next_obs), and that call without the next rows.
+    python tools/rollout_bench.py --policy 64,64 --activation relu --head state --squashed-logp --steps 128 --ids PointUMaze-v0,SwimmerUMaze-v0,AntUMaze-v0
 Kernel durations come from a run of their own:  rocprofv3 --kernel-trace --stats -d <dir> -- python tools/rollout_bench.py --seconds 0.2"""
 import argparse
 import json
@@ -319,6 +324,78 @@ def bench_transitions(env_id, n, K, H, seconds, repeats, ACT="tanh", obs_norm=Fa
             "flagged_envs": bad, **{name + "_env_steps_per_s": v for name, v in res.items()}}
 
 
+def bench_head(env_id, n, K, H, seconds, repeats, ACT="tanh", obs_norm=False, squashed_logp=False):
+    """One SAC collection window of K steps with a state-dependent log-std head: policy_sample(log_std="state") + step + torch.where
+    on the terminal rows; one rollout_policy_sample(log_std="state") with return_next_obs; the same call without the next rows."""
+    from mujoco_maze_amd import policy
+
+    dev = torch.device("cuda", 0)
+    env = mm.make(env_id, num_envs=n, auto_reset=True, device=dev, force_vec=True)
+    env.reset(seed=20260928)
+    g = torch.Generator(device=dev).manual_seed(1234)
+    bind_norm(env, obs_norm, dev, g)  # (no torch network in this mode)
+
+    def lin(out, fan_in):
+        k = fan_in ** -0.5
+        return (2 * torch.rand((out, fan_in), device=dev, generator=g) - 1) * k, (2 * torch.rand(out, device=dev, generator=g) - 1) * k
+
+    sizes = (env.obs_dim,) + policy.net_shape(H, ACT)[0] + (env.nu,)
+    layers = [lin(o, i) for i, o in zip(sizes[:-1], sizes[1:])]
+    Wh, bh = lin(env.nu, sizes[-2])
+    params = torch.as_tensor(policy.pack_mlp(layers, log_std_head=(0.1 * Wh, torch.full_like(bh, -0.5))), device=dev)
+    kw = dict(hidden=H, activation=ACT, squash=True, log_std="state", squashed_logp=squashed_logp)
+    obs_rows, next_rows = torch.empty((K, n, env.obs_dim), device=dev), torch.empty((K, n, env.obs_dim), device=dev)
+    act_rows, logp_rows = torch.empty((K, n, env.nu), device=dev), torch.empty((K, n), device=dev)
+    rew, done = torch.empty((K, n), device=dev), torch.empty((K, n), dtype=torch.uint8, device=dev)
+
+    def step_where():
+        for k in range(K):
+            a, lp = env.policy_sample(params, **kw)
+            o, r, d, info = env.step(a)
+            act_rows[k], logp_rows[k], obs_rows[k], rew[k], done[k] = a, lp, o, r, d
+            next_rows[k] = torch.where((d != 0).unsqueeze(1), info["final_observation"], o)
+
+    def one_call():
+        env.rollout_policy_sample(params, K, return_obs=True, return_actions=True, return_next_obs=True, **kw)
+
+    def no_next():
+        env.rollout_policy_sample(params, K, return_obs=True, return_actions=True, **kw)
+
+    legs = (("head_step_where", step_where), ("rollout_head_next_obs", one_call), ("rollout_head_no_next_obs", no_next))
+    for _ in range(4):
+        for _, fn in legs:
+            fn()
+    res = {name: [] for name, _ in legs}
+    for _ in range(repeats):
+        for name, fn in legs:
+            w, dt = leg(fn, 4, seconds, dev)
+            res[name].append(n * K * w / dt)
+    bad = int((env.status() & 3).ne(0).sum())
+    fused_flag = env.launch_info()["rollout_fused"]
+    env.close()
+    return {"env": env_id, "envs": n, "steps_per_window": K, "hidden": H, "activation": ACT, "obs_norm": bool(obs_norm), "head": "state",
+            "squashed_logp": bool(squashed_logp), "fused": fused_flag, "flagged_envs": bad, **{name + "_env_steps_per_s": v for name, v in res.items()}}
+
+
+def main_head(args):
+    out = []
+    med = lambda v: sorted(v)[len(v) // 2]
+    print(f"SAC window (s, a, logp, r, s', d), shared squashed actor with a log-std head (hidden {args.policy}, {args.activation} units, logp of the "
+          f"{'action' if args.squashed_logp else 'pre-squash sample'}), {args.steps} steps per window, {args.envs} envs, auto-reset, >= {args.seconds} s per leg, "
+          f"{args.repeats} alternating repeats; M env-steps/s, median (max - min)")
+    print("%-18s %5s %26s %26s %26s" % ("env", "fused", "sample + step + where", "one call, next rows", "one call, no next rows"))
+    for env_id in args.ids.split(","):
+        r = bench_head(env_id, args.envs, args.steps, args.policy, args.seconds, args.repeats, args.activation, args.obs_norm, args.squashed_logp)
+        out.append(r)
+        cell = lambda v: "%10.3f (%6.3f)" % (med(v) / 1e6, (max(v) - min(v)) / 1e6)
+        print("%-18s %5d %26s %26s %26s" % (env_id, r["fused"], cell(r["head_step_where_env_steps_per_s"]), cell(r["rollout_head_next_obs_env_steps_per_s"]),
+                                            cell(r["rollout_head_no_next_obs_env_steps_per_s"])), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            for r in out:
+                f.write(json.dumps(r) + "\n")
+
+
 def main_transitions(args):
     out = []
     med = lambda v: sorted(v)[len(v) // 2]
@@ -406,6 +483,8 @@ def main():
     ap.add_argument("--obs-norm", action="store_true", help="with --policy: bind an observation normaliser (env.bind_obs_norm) in every leg")
     ap.add_argument("--next-obs", action="store_true", help="with --policy H --sample: the off-policy window, with every step's pre-reset row")
     ap.add_argument("--noise", choices=("pre_squash", "action"), default="pre_squash", help="with --next-obs: where the exploration noise goes")
+    ap.add_argument("--head", choices=("state",), default=None, help="with --policy H: a state-dependent log-std head on the actor (the SAC window)")
+    ap.add_argument("--squashed-logp", action="store_true", help="with --head state: the log-probability of the squashed action")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "rollout_bench.py measures on the GPU only"
     if args.sample and args.policy is None:
@@ -420,6 +499,12 @@ def main():
         ap.error("--next-obs goes with --policy H --sample, without --critic")
     if args.noise != "pre_squash" and not args.next_obs:
         ap.error("--noise goes with --next-obs")
+    if args.head is not None and (args.policy is None or args.critic is not None or args.next_obs or args.sample):
+        ap.error("--head goes with --policy H alone (it samples and returns the next rows by itself)")
+    if args.squashed_logp and args.head is None:
+        ap.error("--squashed-logp goes with --head state")
+    if args.head is not None:
+        return main_head(args)
     if args.next_obs:
         return main_transitions(args)
     if args.critic is not None:
