@@ -662,6 +662,60 @@ int32_t mz_net_sample_head(mz_handle* h, const mz_net* actor, const mz_head* hea
                            float* actions_dev, float* logp_dev, void* stream);
 int32_t mz_rollout_head(mz_handle* h, const mz_rollout_io* io, const mz_head* head, void* stream);
 
+/* Context inputs (goal-conditioned actors pi(a | s, g), HIRO's low level pi(a | s, subgoal), skill policies pi(a | s, z), Q(s, a)):
+ * a per-env row c of `dim` fp32 entries that every network of the call reads BEHIND the observation.  Additive entries:
+ * MZ_ABI_VERSION does not change for them; mz_context carries its own size.
+ *
+ * With a context the input row of a network is r = [y | c], obs_dim + dim entries: y the obs_dim entries of the observation (a
+ * top-down view's included), normalised exactly as above while a normaliser is bound, else raw; c the context, never normalised and
+ * never clipped.  Every first-layer unit is the one dot product of above over r in index order — the context terms last — and the
+ * packed vectors are the layouts above with obs_dim + dim in place of obs_dim (count likewise).  Noise, log-prob, head, squash, the
+ * noise mode and the critic — which reads the same r — are unchanged.  A context whose columns carry zero weights returns the bits of
+ * the network without those rows (a sum plus +-0 is the sum); a NaN in env i's context reaches env i's outputs only.
+ *
+ * update == MZ_CTX_HOLD: the context is constant for the whole call.
+ * update == MZ_CTX_RELATIVE (rollouts; HIRO's goal transition h(s, g, s') = s + g - s'), rel_dims = D, 1 <= D <= min(dim, obs_dim):
+ * after step k, for each env with done[k] == 0 and each d < D, in fp32, a sum then a difference, two roundings:
+ *     tmp = c[d] + s[d];   c[d] = tmp - s'[d]
+ * s: the RAW row the actor acted on at step k; s': the RAW row step k produced (next_obs_seq[k]), never normalised.  Where
+ * done[k] != 0 the context is left alone, with or without auto-reset: no transition crosses an episode end.  Entries d >= D hold.
+ * value_seq[k] reads the context of step k; next_value_seq[k] the context after the transition (for an env that finished: the
+ * unchanged context with the terminal row), and so does the value of a new episode's first row.
+ *
+ * ctx_dev [N, dim] is read by the single calls and IN/OUT for a rollout: on return it holds what step n_steps would read, so two
+ * calls in a row equal one call over the joined steps.  ctx_seq_dev [n_steps, N, dim] (nullable; rollouts): the context the networks
+ * read at step k.
+ *
+ * mz_net_eval_ctx: mz_net_act with sample == 0 (noise == NULL), mz_net_sample (noise given) or mz_net_sample_head (head given) on
+ * the rows [obs | ctx].  mz_net_value_ctx: mz_net_value likewise — with the actions as the context it is Q(s, a).
+ * mz_rollout_ctx: mz_rollout_head (head nullable) with the context; the call leaves the handle, every output and ctx_dev as this
+ * loop would, bit for bit:
+ *     for k:  [ctx_seq[k] = ctx]; [mz_net_value_ctx]; mz_net_eval_ctx(noise step + k); mz_step; [the transition];
+ *             [mz_net_value_ctx of the terminal / new row, as in mz_rollout_actor_critic]
+ * Every handle runs that loop inside the call: one copy of the D old columns before the step and one small kernel behind it apply the
+ * transition.  The networks run the kernels of the bound-normaliser path; without a normaliser the staged row holds the raw bits.
+ * ctx == NULL: each entry IS the call it extends — the same launches, the same bits.
+ * MZ_ERR_ARG, with a message that names the argument: a wrong ctx->struct_size; dim outside 1 .. MZ_MAX_CONTEXT; an unknown update;
+ * rel_dims outside 1 .. min(dim, obs_dim) with MZ_CTX_RELATIVE, or non-zero with MZ_CTX_HOLD; MZ_CTX_RELATIVE or ctx_seq_dev in a
+ * single call; reserved != 0; a NULL ctx_dev; an env_stride that is neither 0 nor the count for obs_dim + dim; an open-loop io; and
+ * everything the extended entry refuses.  A refused call leaves the handle as it was. */
+#define MZ_MAX_CONTEXT 32
+#define MZ_CTX_HOLD 0
+#define MZ_CTX_RELATIVE 1
+typedef struct mz_context {
+  uint32_t struct_size;      /* sizeof(mz_context); anything else: MZ_ERR_ARG */
+  int32_t dim;               /* C: 1 .. MZ_MAX_CONTEXT */
+  int32_t update;            /* MZ_CTX_* */
+  int32_t rel_dims;          /* D with MZ_CTX_RELATIVE: 1 .. min(dim, obs_dim); 0 with MZ_CTX_HOLD */
+  int64_t reserved;          /* 0 */
+  float* ctx_dev;            /* [N, dim]; IN/OUT for a rollout */
+  float* ctx_seq_dev;        /* [n_steps, N, dim]  (nullable; rollouts) */
+} mz_context;
+int32_t mz_net_eval_ctx(mz_handle* h, const mz_net* actor, const mz_head* head, const mz_noise* noise, const mz_context* ctx,
+                        const float* obs_dev, float* actions_dev, float* logp_dev, void* stream);
+int32_t mz_net_value_ctx(mz_handle* h, const mz_net* critic, const mz_context* ctx, const float* obs_dev, float* values_dev, void* stream);
+int32_t mz_rollout_ctx(mz_handle* h, const mz_rollout_io* io, const mz_head* head, const mz_context* ctx, void* stream);
+
 /* Normalised observations for the device-side networks (the observation half of VecNormalize; ARS-V2's state normalisation), and the
  * forward return scan that reward scaling and episode logging need.  Additive entries: MZ_ABI_VERSION does not change for them.
  *

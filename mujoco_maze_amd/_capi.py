@@ -28,6 +28,7 @@ SYMBOLS = [
     "mz_bind_obs_norm", "mz_return_scan",
     "mz_net_sample", "mz_rollout_ex",
     "mz_net_sample_head", "mz_rollout_head",
+    "mz_net_eval_ctx", "mz_net_value_ctx", "mz_rollout_ctx",
 ]
 
 
@@ -91,6 +92,46 @@ class MzHead(C.Structure):
 def make_head(log_std_min: float, log_std_max: float, logp_squashed: bool = False) -> MzHead:
     """An MzHead with struct_size and kind set."""
     return MzHead(C.sizeof(MzHead), HEAD_STATE_STD, float(log_std_min), float(log_std_max), 1 if logp_squashed else 0, 0)
+
+
+MAX_CONTEXT = 32  # MZ_MAX_CONTEXT (include/mazestep.h)
+CTX_HOLD, CTX_RELATIVE = 0, 1  # MZ_CTX_*
+CTX_UPDATES = {None: CTX_HOLD, "hold": CTX_HOLD, "relative": CTX_RELATIVE}
+
+
+class MzContext(C.Structure):
+    """`mz_context` of include/mazestep.h: the per-env context rows of one mz_net_eval_ctx / mz_net_value_ctx / mz_rollout_ctx call."""
+    _fields_ = [("struct_size", C.c_uint32), ("dim", C.c_int32), ("update", C.c_int32), ("rel_dims", C.c_int32), ("reserved", C.c_int64),
+                ("ctx_dev", C.c_void_p), ("ctx_seq_dev", C.c_void_p)]
+
+
+def context_args(dim: int, obs_dim: int, context_update=None, context_dims=None, rollout: bool = True):
+    """(MZ_CTX_*, rel_dims) of the `context_update=` / `context_dims=` arguments for a context of `dim` entries, checked as
+    mz_rollout_ctx checks them: ValueError names the argument.  rollout False: a single call, which takes no update."""
+    dim = int(dim)
+    if not 1 <= dim <= MAX_CONTEXT:
+        raise ValueError(f"context must have 1 .. {MAX_CONTEXT} (MZ_MAX_CONTEXT) entries per env, got {dim}")
+    try:
+        update = CTX_UPDATES[context_update]
+    except (KeyError, TypeError):
+        raise ValueError(f"context_update must be None or 'relative', got {context_update!r}") from None
+    if update == CTX_HOLD:
+        if context_dims not in (None, 0):
+            raise ValueError(f"context_dims needs context_update='relative', got context_dims={context_dims!r} with a context that holds")
+        return update, 0
+    if not rollout:
+        raise ValueError("context_update='relative' needs a rollout: a transition needs a step")
+    if context_dims is None:
+        raise ValueError("context_update='relative' needs context_dims=D, 1 <= D <= min(C, obs_dim)")
+    d = int(context_dims)
+    if not 1 <= d <= min(dim, int(obs_dim)):
+        raise ValueError(f"context_dims must be 1 .. min(C, obs_dim) = {min(dim, int(obs_dim))}, got {d}")
+    return update, d
+
+
+def make_context(ctx_ptr, dim: int, update: int = CTX_HOLD, rel_dims: int = 0, ctx_seq_ptr=None) -> MzContext:
+    """An MzContext with struct_size set."""
+    return MzContext(C.sizeof(MzContext), int(dim), int(update), int(rel_dims), 0, ctx_ptr, ctx_seq_ptr)
 
 
 def make_noise(mode: int, seed: int, step: int) -> MzNoise:
@@ -194,6 +235,12 @@ def load():
     lib.mz_net_sample_head.argtypes = [vp, C.POINTER(MzNet), C.POINTER(MzHead), C.POINTER(MzNoise), vp, vp, vp, vp]
     lib.mz_rollout_head.restype = i32
     lib.mz_rollout_head.argtypes = [vp, C.POINTER(MzRolloutIo), C.POINTER(MzHead), vp]
+    lib.mz_net_eval_ctx.restype = i32
+    lib.mz_net_eval_ctx.argtypes = [vp, C.POINTER(MzNet), C.POINTER(MzHead), C.POINTER(MzNoise), C.POINTER(MzContext), vp, vp, vp, vp]
+    lib.mz_net_value_ctx.restype = i32
+    lib.mz_net_value_ctx.argtypes = [vp, C.POINTER(MzNet), C.POINTER(MzContext), vp, vp, vp]
+    lib.mz_rollout_ctx.restype = i32
+    lib.mz_rollout_ctx.argtypes = [vp, C.POINTER(MzRolloutIo), C.POINTER(MzHead), C.POINTER(MzContext), vp]
     lib.mz_bind_obs_norm.restype = i32
     lib.mz_bind_obs_norm.argtypes = [vp, vp, vp, C.c_double, vp]
     lib.mz_return_scan.restype = i32

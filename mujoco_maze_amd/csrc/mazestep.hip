@@ -43,6 +43,20 @@ __global__ __launch_bounds__(256) void next_obs_kernel(int n, int obs_dim, const
   out[idx] = done[idx / obs_dim] ? final_obs[idx] : obs[idx];
 }
 
+// The relative transition of a context behind one step of mz_rollout_ctx (mz_policy.h mzp_ctx_next): one thread per (env, d < D),
+// ctx[i][d] = (ctx[i][d] + s_old[i][d]) - obs[i][d] where done[i] == 0.  s_old [n][D]: the first D columns of the raw row the actor
+// acted on, copied before the step; obs: the rows the step left — for an env that did not finish that IS the row it produced, with or
+// without auto-reset, and an env that finished keeps its context.
+__global__ __launch_bounds__(256) void ctx_transition_kernel(int n, int cdim, int D, int obs_dim, const float* __restrict__ s_old,
+                                                             const float* __restrict__ obs, const uint8_t* __restrict__ done,
+                                                             float* __restrict__ ctx) {
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (size_t)n * D) return;
+  const size_t env = idx / D, d = idx - env * D;
+  if (done[env]) return;
+  ctx[env * cdim + d] = mzp_ctx_next(ctx[env * cdim + d], s_old[idx], obs[env * obs_dim + d]);
+}
+
 // actions[r] = policy(obs[r]) for n rows (mz_policy_act; mz_rollout_policy where it steps launch by launch): the policy of mz_policy.h,
 // one group of MZ_POLICY_LANES adjacent lanes per row — lanes l, l + 16, .. own hidden units, lanes 0 .. nu - 1 the outputs.  Engine-
 // independent.  params: one policy (pstride = 0) or row r's own at params + r * pstride.  Surplus groups shadow the last row (no stores).
@@ -98,6 +112,9 @@ __global__ __launch_bounds__(256) void value_kernel(int n, int obs_dim, int hidd
 // stages the normalised row of mz_policy.h in a third LDS row — lanes l, l + 16, .. own its elements —, hands it over and evaluates
 // the network on it.  obs_dim <= MZ_MAX_OBS + MZ_VIEW_DIM on every handle (mz_create; mz_bind_obs_norm checks it again).  NRM == false
 // compiles the source as it was and never reads `nm`.  mode: MZ_NOISE_* of a sampled action.
+// A context (mz_context: nm.cdim > 0) rides on the NRM instantiations: the row's nm.cdim context floats are staged behind the
+// normalised row — the row has MZ_MAX_CONTEXT floats more for them — and the network runs on obs_dim + nm.cdim inputs; without a
+// bound normaliser nm is the identity (ctx_norm below), which returns the raw bits.  nm.cdim == 0 stages and reads what it did.
 template <bool NRM = false>
 __global__ __launch_bounds__(256) void net_act_kernel(int n, int obs_dim, int nu, mzp_shape s, int squash, float action_scale,
                                                       const float* __restrict__ params, long pstride, int sample, uint64_t key, uint64_t env0,
@@ -109,10 +126,11 @@ __global__ __launch_bounds__(256) void net_act_kernel(int n, int obs_dim, int nu
   const bool live = row < (size_t)n;
   if (!live) row = (size_t)n - 1;
   if constexpr (NRM) {
-    __shared__ float xn[256 / MZ_POLICY_LANES][MZ_MAX_OBS + MZ_VIEW_DIM];
+    __shared__ float xn[256 / MZ_POLICY_LANES][MZ_MAX_OBS + MZ_VIEW_DIM + MZ_MAX_CONTEXT];
     mzp_group_norm(l, MZ_POLICY_LANES, nm, obs_dim, obs + row * obs_dim, xn[grp]);
+    mzp_group_ctx(l, MZ_POLICY_LANES, nm.ctx + row * nm.cdim, nm.cdim, xn[grp] + obs_dim);
     mzp_wave_sync();
-    mzp_group_net_act(l, MZ_POLICY_LANES, params + row * pstride, obs_dim, nu, s, squash, action_scale, sample != 0, key, env0 + row, xn[grp],
+    mzp_group_net_act(l, MZ_POLICY_LANES, params + row * pstride, obs_dim + nm.cdim, nu, s, squash, action_scale, sample != 0, key, env0 + row, xn[grp],
                       hid[grp][0], hid[grp][1], actions + row * nu, live, live && logp ? logp + row : nullptr, mode);
   } else {
     mzp_group_net_act(l, MZ_POLICY_LANES, params + row * pstride, obs_dim, nu, s, squash, action_scale, sample != 0, key, env0 + row,
@@ -134,10 +152,11 @@ __global__ __launch_bounds__(256) void net_sample_head_kernel(int n, int obs_dim
   const bool live = row < (size_t)n;
   if (!live) row = (size_t)n - 1;
   if constexpr (NRM) {
-    __shared__ float xn[256 / MZ_POLICY_LANES][MZ_MAX_OBS + MZ_VIEW_DIM];
+    __shared__ float xn[256 / MZ_POLICY_LANES][MZ_MAX_OBS + MZ_VIEW_DIM + MZ_MAX_CONTEXT];
     mzp_group_norm(l, MZ_POLICY_LANES, nm, obs_dim, obs + row * obs_dim, xn[grp]);
+    mzp_group_ctx(l, MZ_POLICY_LANES, nm.ctx + row * nm.cdim, nm.cdim, xn[grp] + obs_dim);
     mzp_wave_sync();
-    mzp_group_net_sample_head(l, MZ_POLICY_LANES, params + row * pstride, obs_dim, nu, s, squash, action_scale, hd, key, env0 + row, xn[grp],
+    mzp_group_net_sample_head(l, MZ_POLICY_LANES, params + row * pstride, obs_dim + nm.cdim, nu, s, squash, action_scale, hd, key, env0 + row, xn[grp],
                               hid[grp][0], hid[grp][1], actions + row * nu, live, live && logp ? logp + row : nullptr);
   } else {
     mzp_group_net_sample_head(l, MZ_POLICY_LANES, params + row * pstride, obs_dim, nu, s, squash, action_scale, hd, key, env0 + row,
@@ -159,10 +178,11 @@ __global__ __launch_bounds__(256) void net_value_kernel(int n, int obs_dim, mzp_
   const float* x = (done && done[row] ? final_obs : obs) + row * obs_dim;
   float v;
   if constexpr (NRM) {
-    __shared__ float xn[256 / MZ_POLICY_LANES][MZ_MAX_OBS + MZ_VIEW_DIM];
+    __shared__ float xn[256 / MZ_POLICY_LANES][MZ_MAX_OBS + MZ_VIEW_DIM + MZ_MAX_CONTEXT];
     mzp_group_norm(l, MZ_POLICY_LANES, nm, obs_dim, x, xn[grp]);
+    mzp_group_ctx(l, MZ_POLICY_LANES, nm.ctx + row * nm.cdim, nm.cdim, xn[grp] + obs_dim);
     mzp_wave_sync();
-    v = mzp_group_net_value(l, MZ_POLICY_LANES, vparams + row * vstride, obs_dim, s, xn[grp], hid[grp][0], hid[grp][1]);
+    v = mzp_group_net_value(l, MZ_POLICY_LANES, vparams + row * vstride, obs_dim + nm.cdim, s, xn[grp], hid[grp][0], hid[grp][1]);
   } else {
     v = mzp_group_net_value(l, MZ_POLICY_LANES, vparams + row * vstride, obs_dim, s, x, hid[grp][0], hid[grp][1]);
   }
@@ -372,6 +392,8 @@ void mz_destroy(mz_handle* h) {
   if (h->prof) (void)hipFree(h->prof);
   if (h->render_qpos) (void)hipFree(h->render_qpos);
   if (h->policy_act) (void)hipFree(h->policy_act);
+  if (h->ctx_ident) (void)hipFree(h->ctx_ident);
+  if (h->ctx_old) (void)hipFree(h->ctx_old);
   if (h->ev) { for (int i = 0; i < 2 * h->ntime; i++) (void)hipEventDestroy(h->ev[i]); free(h->ev); }
   delete h;
 }
@@ -630,9 +652,10 @@ static mz_net legacy_net(const float* params_dev, int64_t env_stride, int hidden
   return mz_net{(uint32_t)sizeof(mz_net), hidden > 0 ? 1 : 0, {hidden, 0}, MZ_ACT_TANH, squash, action_scale, params_dev, env_stride};
 }
 static void net_act_launch(mz_handle* h, hipStream_t st, const mz_net* actor, int sample, uint64_t noise_seed, uint64_t noise_step,
-                           const float* obs_dev, float* actions_dev, float* logp_dev, int noise_mode = MZ_NOISE_PRE_SQUASH);
+                           const float* obs_dev, float* actions_dev, float* logp_dev, int noise_mode = MZ_NOISE_PRE_SQUASH,
+                           const mz_context* ctx = nullptr);
 static void net_value_launch(mz_handle* h, hipStream_t st, const mz_net* critic, const float* obs_dev, const float* final_obs_dev,
-                             const uint8_t* done_dev, float* values_dev);
+                             const uint8_t* done_dev, float* values_dev, const mz_context* ctx = nullptr);
 
 // the checks the four policy entries share (stochastic: the vector carries log_std[nu] behind the network); MZ_OK or MZ_ERR_ARG with
 // the message set
@@ -742,7 +765,7 @@ int32_t mz_value(mz_handle* h, const float* vparams_dev, int64_t env_stride, int
 // vector carries log_std[nu] behind the network — unless `head`: the output layer is 2 nu units wide and nothing follows it.
 // MZ_OK or MZ_ERR_ARG with the message set.
 static int net_args(mz_handle* h, const char* who, const char* which, const mz_net* net, int nout, bool stochastic, bool is_critic,
-                    bool head = false) {
+                    bool head = false, int cdim = 0) {
   char msg[200];
   auto fail = [&](const char* field, const char* why) {
     snprintf(msg, sizeof(msg), "%s: %s%s %s", who, which, field, why);
@@ -760,11 +783,12 @@ static int net_args(mz_handle* h, const char* who, const char* which, const mz_n
   if (net->squash != 0 && net->squash != 1) return fail("->squash", "must be 0 or 1");
   if (is_critic && net->squash != 0) return fail("->squash", "must be 0: a critic is never squashed");
   if (!net->params_dev) return fail("->params_dev", "is NULL");
-  const int64_t count = (int64_t)mzp_net_param_count(h->model.obs_dim, head ? 2 * nout : nout,
+  const int64_t count = (int64_t)mzp_net_param_count(h->model.obs_dim + cdim, head ? 2 * nout : nout,
                                                      mzp_shape{net->n_hidden, net->hidden[0], net->hidden[1], net->activation}) +
                         (stochastic && !head ? h->model.nu : 0);
   if (net->env_stride != 0 && net->env_stride != count)
-    return fail("->env_stride", head ? "must be 0 (one shared network) or the head count (one per env; an output layer of 2 nu units, no log_std behind it)"
+    return fail("->env_stride", cdim ? "must be 0 (one shared network) or the count for obs_dim + ctx->dim inputs (one per env)"
+                                : head ? "must be 0 (one shared network) or the head count (one per env; an output layer of 2 nu units, no log_std behind it)"
                                 : stochastic ? "must be 0 (one shared network) or count (one per env; log_std[nu] behind the network counts)"
                                            : "must be 0 (one shared network) or count (one per env)");
   return MZ_OK;
@@ -772,26 +796,53 @@ static int net_args(mz_handle* h, const char* who, const char* which, const mz_n
 
 static mzp_shape net_shape(const mz_net* net) { return mzp_shape{net->n_hidden, net->hidden[0], net->hidden[1], net->activation}; }
 
+// The normaliser a network launch gets: the handle's, or — for a call with a context on a handle without one — the identity, which
+// returns the raw bits (mz_policy.h); with the context rows of the launch behind it.  ctx_prepare has allocated the identity.
+static mzp_norm ctx_norm(const mz_handle* h, const mz_context* ctx) {
+  if (!ctx) return mzp_norm{h->nrm_mean, h->nrm_inv_std, h->nrm_clip, 0, nullptr};
+  if (h->nrm_mean) return mzp_norm{h->nrm_mean, h->nrm_inv_std, h->nrm_clip, ctx->dim, ctx->ctx_dev};
+  return mzp_norm{h->ctx_ident, h->ctx_ident + h->model.obs_dim, INFINITY, ctx->dim, ctx->ctx_dev};
+}
+
+// what a checked call with a context needs on the handle before its first launch: the identity normaliser, and for the relative
+// transition the scratch of the old columns.  Synchronous copies on first use only.
+static int ctx_prepare(mz_handle* h, const mz_context* ctx) {
+  const size_t od = (size_t)h->model.obs_dim;
+  if (!h->ctx_ident) {
+    float* host = (float*)malloc(2 * od * sizeof(float));
+    if (!host) return set_err(h, MZ_ERR_HIP, "mz_context: out of memory", hipSuccess);
+    for (size_t i = 0; i < od; i++) { host[i] = 0.0f; host[od + i] = 1.0f; }
+    float* dev = nullptr;
+    hipError_t e = hipMalloc(&dev, 2 * od * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(dev, host, 2 * od * sizeof(float), hipMemcpyHostToDevice);
+    free(host);
+    if (e != hipSuccess) { if (dev) (void)hipFree(dev); return set_err(h, MZ_ERR_HIP, "mz_context: identity normaliser", e); }
+    h->ctx_ident = dev;
+  }
+  if (ctx->update == MZ_CTX_RELATIVE && !h->ctx_old) HIPCHK(h, hipMalloc(&h->ctx_old, (size_t)h->n * MZ_MAX_CONTEXT * sizeof(float)));
+  return MZ_OK;
+}
+
 static void net_act_launch(mz_handle* h, hipStream_t st, const mz_net* actor, int sample, uint64_t noise_seed, uint64_t noise_step,
-                           const float* obs_dev, float* actions_dev, float* logp_dev, int noise_mode) {
+                           const float* obs_dev, float* actions_dev, float* logp_dev, int noise_mode, const mz_context* ctx) {
   const int rows = 256 / MZ_POLICY_LANES;
-  const mzp_norm nm{h->nrm_mean, h->nrm_inv_std, h->nrm_clip};
+  const mzp_norm nm = ctx_norm(h, ctx);
 #define MZ_NET_ACT(NRM)                                                                                                                         \
   hipLaunchKernelGGL(net_act_kernel<NRM>, dim3((unsigned)((h->n + rows - 1) / rows)), dim3(256), 0, st, h->n, h->model.obs_dim, h->model.nu,     \
                      net_shape(actor), actor->squash, (float)actor->action_scale, actor->params_dev, (long)actor->env_stride, sample,           \
                      sample ? mzp_noise_key(noise_seed, noise_step) : 0, h->env0, obs_dev, actions_dev, sample ? logp_dev : NULL, nm, noise_mode)
-  if (h->nrm_mean) MZ_NET_ACT(true); else MZ_NET_ACT(false);
+  if (nm.mean) MZ_NET_ACT(true); else MZ_NET_ACT(false);
 #undef MZ_NET_ACT
 }
 
 static void net_value_launch(mz_handle* h, hipStream_t st, const mz_net* critic, const float* obs_dev, const float* final_obs_dev,
-                             const uint8_t* done_dev, float* values_dev) {
+                             const uint8_t* done_dev, float* values_dev, const mz_context* ctx) {
   const int rows = 256 / MZ_POLICY_LANES;
-  const mzp_norm nm{h->nrm_mean, h->nrm_inv_std, h->nrm_clip};
+  const mzp_norm nm = ctx_norm(h, ctx);
 #define MZ_NET_VALUE(NRM)                                                                                                                        \
   hipLaunchKernelGGL(net_value_kernel<NRM>, dim3((unsigned)((h->n + rows - 1) / rows)), dim3(256), 0, st, h->n, h->model.obs_dim, net_shape(critic), \
                      critic->params_dev, (long)critic->env_stride, obs_dev, final_obs_dev, done_dev, values_dev, nm)
-  if (h->nrm_mean) MZ_NET_VALUE(true); else MZ_NET_VALUE(false);
+  if (nm.mean) MZ_NET_VALUE(true); else MZ_NET_VALUE(false);
 #undef MZ_NET_VALUE
 }
 
@@ -869,15 +920,16 @@ static int head_args(mz_handle* h, const char* who, const mz_head* head, const m
 }
 
 static void net_sample_head_launch(mz_handle* h, hipStream_t st, const mz_net* actor, const mz_head* head, float logA, uint64_t noise_seed,
-                                   uint64_t noise_step, const float* obs_dev, float* actions_dev, float* logp_dev) {
+                                   uint64_t noise_step, const float* obs_dev, float* actions_dev, float* logp_dev,
+                                   const mz_context* ctx = nullptr) {
   const int rows = 256 / MZ_POLICY_LANES;
-  const mzp_norm nm{h->nrm_mean, h->nrm_inv_std, h->nrm_clip};
+  const mzp_norm nm = ctx_norm(h, ctx);
   const mzp_head hd{head->log_std_min, head->log_std_max, head->logp_squashed, logA};
 #define MZ_NET_HEAD(NRM)                                                                                                                          \
   hipLaunchKernelGGL(net_sample_head_kernel<NRM>, dim3((unsigned)((h->n + rows - 1) / rows)), dim3(256), 0, st, h->n, h->model.obs_dim, h->model.nu, \
                      net_shape(actor), actor->squash, (float)actor->action_scale, hd, actor->params_dev, (long)actor->env_stride,                  \
                      mzp_noise_key(noise_seed, noise_step), h->env0, obs_dev, actions_dev, logp_dev, nm)
-  if (h->nrm_mean) MZ_NET_HEAD(true); else MZ_NET_HEAD(false);
+  if (nm.mean) MZ_NET_HEAD(true); else MZ_NET_HEAD(false);
 #undef MZ_NET_HEAD
 }
 
@@ -913,8 +965,8 @@ static hipError_t next_obs_row(mz_handle* h, hipStream_t st, const float* obs_de
 static void rollout_act_launch(mz_handle* h, hipStream_t st, const RolloutPlan& p, bool one_layer, size_t k, float* actions) {
   const mz_net* a = p.actor;
   float* logp = p.logp_seq_dev ? p.logp_seq_dev + k * (size_t)h->n : NULL;
-  if (p.head) net_sample_head_launch(h, st, a, p.head, p.head_logA, p.noise_seed, p.noise_step + k, p.obs_dev, actions, logp);
-  else if (!one_layer) net_act_launch(h, st, a, p.sample, p.noise_seed, p.noise_step + k, p.obs_dev, actions, logp, p.noise_mode);
+  if (p.head) net_sample_head_launch(h, st, a, p.head, p.head_logA, p.noise_seed, p.noise_step + k, p.obs_dev, actions, logp, p.ctx);
+  else if (!one_layer) net_act_launch(h, st, a, p.sample, p.noise_seed, p.noise_step + k, p.obs_dev, actions, logp, p.noise_mode, p.ctx);
   else if (p.sample)
     policy_sample_launch(h, st, a->params_dev, a->env_stride, a->hidden[0], a->squash, (float)a->action_scale, p.noise_seed, p.noise_step + k, p.obs_dev,
                          actions, logp);
@@ -926,7 +978,7 @@ static void rollout_value_launch(mz_handle* h, hipStream_t st, const RolloutPlan
                                  const uint8_t* done_dev, float* values_dev) {
   const mz_net* c = p.critic;
   if (one_layer) value_launch(h, st, c->params_dev, c->env_stride, c->hidden[0], p.obs_dev, final_obs_dev, done_dev, values_dev);
-  else net_value_launch(h, st, c, p.obs_dev, final_obs_dev, done_dev, values_dev);
+  else net_value_launch(h, st, c, p.obs_dev, final_obs_dev, done_dev, values_dev, p.ctx);
 }
 
 // The driver behind every rollout entry: n_steps times [a = the plan's actor on obs, or row k of its action tensor]; step(a) in one
@@ -951,7 +1003,8 @@ static int32_t rollout_run(mz_handle* h, const RolloutPlan& plan, void* stream) 
   const bool six_link_policy = p.actor && h->robot == MZ_ROBOT_SWIMMER && h->swimmer.nlink == 6;
   // A head plan on a five- or six-link chain runs the loop too: their fused kernels compile without the head's branch (planar_kernels.hip).
   const bool long_chain_head = p.head && h->robot == MZ_ROBOT_SWIMMER && h->swimmer.nlink >= 5;
-  if (mzk_planar_rollout_fused(h) && !six_link_policy && !long_chain_head) {
+  // A plan with a context runs the loop on every handle: the fused kernels do not stage one.
+  if (mzk_planar_rollout_fused(h) && !six_link_policy && !long_chain_head && !p.ctx) {
     HIPCHK(h, mzk_planar_rollout(h, st, p));
     if (h->record) {  // the last step's row
       const size_t tot = n * (od + 2), last = (size_t)(p.n_steps - 1) * n;
@@ -959,13 +1012,19 @@ static int32_t rollout_run(mz_handle* h, const RolloutPlan& plan, void* stream) 
       HIPCHK(h, hipGetLastError());
     }
   } else {
-    const bool one_layer = mzk_rollout_kernels(h, p).one_layer;
+    const bool one_layer = !p.ctx && mzk_rollout_kernels(h, p).one_layer;  // a context rides on the net kernels' NRM instantiations
+    const mz_context* cx = p.ctx;
+    const int D = cx && cx->update == MZ_CTX_RELATIVE ? cx->rel_dims : 0;
     if (p.actor && !p.actions_seq_dev && !h->policy_act) HIPCHK(h, hipMalloc(&h->policy_act, n * nu * sizeof(float)));
     for (size_t k = 0; k < (size_t)p.n_steps; k++) {
       uint8_t* done_k = p.done_dev + k * n;
       const float* a;
       if (p.actor) {
         float* out = p.actions_seq_dev ? p.actions_seq_dev + k * n * nu : h->policy_act;
+        if (cx && cx->ctx_seq_dev)  // the context the networks read at step k
+          HIPCHK(h, hipMemcpyAsync(cx->ctx_seq_dev + k * n * cx->dim, cx->ctx_dev, n * cx->dim * sizeof(float), hipMemcpyDeviceToDevice, st));
+        if (D)  // the D old columns of the raw row the actor acts on, which the step overwrites
+          HIPCHK(h, hipMemcpy2DAsync(h->ctx_old, D * sizeof(float), p.obs_dev, od * sizeof(float), D * sizeof(float), n, hipMemcpyDeviceToDevice, st));
         if (p.value_seq_dev) rollout_value_launch(h, st, p, one_layer, NULL, NULL, p.value_seq_dev + k * n);
         rollout_act_launch(h, st, p, one_layer, k, out);
         HIPCHK(h, hipGetLastError());
@@ -976,6 +1035,11 @@ static int32_t rollout_run(mz_handle* h, const RolloutPlan& plan, void* stream) 
       const int rc = step_launches(h, st, a, p.obs_dev, p.reward_dev + k * n, done_k, p.goal_idx_dev ? p.goal_idx_dev + k * n : NULL,
                                    p.info_dev ? p.info_dev + k * n * 4 : NULL);
       if (rc != MZ_OK) return rc;
+      if (D) {  // before the next value, which reads the context after the transition
+        hipLaunchKernelGGL(ctx_transition_kernel, dim3((unsigned)((n * D + 255) / 256)), dim3(256), 0, st, h->n, cx->dim, D, h->model.obs_dim, h->ctx_old,
+                           p.obs_dev, done_k, cx->ctx_dev);
+        HIPCHK(h, hipGetLastError());
+      }
       if (p.next_value_seq_dev) {
         rollout_value_launch(h, st, p, one_layer, h->auto_reset ? h->final_obs : NULL, h->auto_reset ? done_k : NULL, p.next_value_seq_dev + k * n);
         HIPCHK(h, hipGetLastError());
@@ -1024,9 +1088,10 @@ static int net_rollout_args(mz_handle* h, const RolloutPlan& p) {
   if (p.sample != 0 && p.sample != 1) return set_err(h, MZ_ERR_ARG, "mz_rollout_net: sample must be 0 or 1", hipSuccess);
   int rc = rollout_args(h, p);
   if (rc != MZ_OK) return rc;
-  rc = net_args(h, p.who, "actor", p.actor, h->model.nu, p.sample != 0, false, p.head != nullptr);
+  const int cdim = p.ctx ? p.ctx->dim : 0;
+  rc = net_args(h, p.who, "actor", p.actor, h->model.nu, p.sample != 0, false, p.head != nullptr, cdim);
   if (rc != MZ_OK || !p.critic) return rc;
-  rc = net_args(h, p.who, "critic", p.critic, 1, false, true);
+  rc = net_args(h, p.who, "critic", p.critic, 1, false, true, false, cdim);
   if (rc != MZ_OK) return rc;
   if (p.next_value_seq_dev && h->auto_reset && !h->final_obs)
     return set_err(h, MZ_ERR_ARG, "mz_rollout_net: next_value_seq_dev under auto-reset needs a bound final_obs buffer (mz_bind_final_obs): "
@@ -1116,15 +1181,91 @@ int32_t mz_rollout_net(mz_handle* h, int32_t n_steps, const mz_net* actor, int32
 
 // mz_rollout / mz_rollout_net behind one struct, with the per-step pre-reset rows and the noise mode (include/mazestep.h).  The
 // checks here are those the struct adds; everything else is refused as by the entry the call stands for, whose plan it fills.
-static int32_t rollout_ex(mz_handle* h, const mz_rollout_io* io, const mz_head* head, void* stream);
+static int32_t rollout_ex(mz_handle* h, const mz_rollout_io* io, const mz_head* head, void* stream, const mz_context* ctx = nullptr);
 int32_t mz_rollout_ex(mz_handle* h, const mz_rollout_io* io, void* stream) { return rollout_ex(h, io, NULL, stream); }
 // mz_rollout_ex with a state-dependent log-std head on the actor (include/mazestep.h); head == NULL: mz_rollout_ex itself
 int32_t mz_rollout_head(mz_handle* h, const mz_rollout_io* io, const mz_head* head, void* stream) { return rollout_ex(h, io, head, stream); }
 
-static int32_t rollout_ex(mz_handle* h, const mz_rollout_io* io, const mz_head* head, void* stream) {
+// the checks of a context that is not NULL (rollout: MZ_CTX_RELATIVE and ctx_seq_dev are the rollout's); MZ_OK or MZ_ERR_ARG with the
+// message set
+static int ctx_args(mz_handle* h, const char* who, const mz_context* ctx, bool rollout) {
+  char msg[200];
+  const char* why = nullptr;
+  const int dmax = ctx->dim < h->model.obs_dim ? ctx->dim : h->model.obs_dim;
+  if (ctx->struct_size != sizeof(mz_context)) why = "ctx->struct_size must be sizeof(mz_context)";
+  else if (ctx->dim < 1 || ctx->dim > MZ_MAX_CONTEXT) why = "ctx->dim must be 1 .. MZ_MAX_CONTEXT (32)";
+  else if (ctx->update != MZ_CTX_HOLD && ctx->update != MZ_CTX_RELATIVE) why = "ctx->update must be MZ_CTX_HOLD (0) or MZ_CTX_RELATIVE (1)";
+  else if (ctx->update == MZ_CTX_HOLD && ctx->rel_dims != 0) why = "ctx->rel_dims must be 0 with MZ_CTX_HOLD";
+  else if (ctx->update == MZ_CTX_RELATIVE && !rollout) why = "ctx->update must be MZ_CTX_HOLD in a single call: a transition needs a step";
+  else if (ctx->update == MZ_CTX_RELATIVE && (ctx->rel_dims < 1 || ctx->rel_dims > dmax)) why = "ctx->rel_dims must be 1 .. min(ctx->dim, obs_dim) with MZ_CTX_RELATIVE";
+  else if (ctx->reserved != 0) why = "ctx->reserved must be 0";
+  else if (!ctx->ctx_dev) why = "ctx->ctx_dev is NULL";
+  else if (ctx->ctx_seq_dev && !rollout) why = "ctx->ctx_seq_dev must be NULL in a single call";
+  if (!why) return MZ_OK;
+  snprintf(msg, sizeof(msg), "%s: %s", who, why);
+  return set_err(h, MZ_ERR_ARG, msg, hipSuccess);
+}
+
+// mz_net_act / mz_net_sample / mz_net_sample_head on the rows [obs | ctx] (include/mazestep.h); ctx == NULL: those calls themselves
+int32_t mz_net_eval_ctx(mz_handle* h, const mz_net* actor, const mz_head* head, const mz_noise* noise, const mz_context* ctx,
+                        const float* obs_dev, float* actions_dev, float* logp_dev, void* stream) {
+  if (!h) return MZ_ERR_ARG;
+  if (!ctx) {
+    if (head) return mz_net_sample_head(h, actor, head, noise, obs_dev, actions_dev, logp_dev, stream);
+    if (noise) return mz_net_sample(h, actor, noise, obs_dev, actions_dev, logp_dev, stream);
+    return mz_net_act(h, actor, 0, 0, 0, obs_dev, actions_dev, NULL, stream);
+  }
+  const char* who = "mz_net_eval_ctx";
+  if (!obs_dev || !actions_dev) return set_err(h, MZ_ERR_ARG, "mz_net_eval_ctx: null array", hipSuccess);
+  int rc = ctx_args(h, who, ctx, false);
+  if (rc != MZ_OK) return rc;
+  if (head) {
+    rc = head_args(h, who, head, actor, noise, false);
+    if (rc != MZ_OK) return rc;
+  }
+  if (noise) {
+    rc = noise_args(h, who, noise);
+    if (rc != MZ_OK) return rc;
+  }
+  rc = net_args(h, who, "actor", actor, h->model.nu, noise != nullptr, false, head != nullptr, ctx->dim);
+  if (rc != MZ_OK) return rc;
+  DeviceScope scope(h->device);
+  rc = ctx_prepare(h, ctx);
+  if (rc != MZ_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (head) net_sample_head_launch(h, st, actor, head, logf((float)actor->action_scale), noise->seed, noise->step, obs_dev, actions_dev, logp_dev, ctx);
+  else if (noise) net_act_launch(h, st, actor, 1, noise->seed, noise->step, obs_dev, actions_dev, logp_dev, noise->mode, ctx);
+  else net_act_launch(h, st, actor, 0, 0, 0, obs_dev, actions_dev, NULL, MZ_NOISE_PRE_SQUASH, ctx);
+  HIPCHK(h, hipGetLastError());
+  return MZ_OK;
+}
+
+// mz_net_value on the rows [obs | ctx]; ctx == NULL: mz_net_value itself
+int32_t mz_net_value_ctx(mz_handle* h, const mz_net* critic, const mz_context* ctx, const float* obs_dev, float* values_dev, void* stream) {
+  if (!h) return MZ_ERR_ARG;
+  if (!ctx) return mz_net_value(h, critic, obs_dev, values_dev, stream);
+  if (!obs_dev || !values_dev) return set_err(h, MZ_ERR_ARG, "mz_net_value_ctx: null array", hipSuccess);
+  int rc = ctx_args(h, "mz_net_value_ctx", ctx, false);
+  if (rc != MZ_OK) return rc;
+  rc = net_args(h, "mz_net_value_ctx", "critic", critic, 1, false, true, false, ctx->dim);
+  if (rc != MZ_OK) return rc;
+  DeviceScope scope(h->device);
+  rc = ctx_prepare(h, ctx);
+  if (rc != MZ_OK) return rc;
+  net_value_launch(h, (hipStream_t)stream, critic, obs_dev, NULL, NULL, values_dev, ctx);
+  HIPCHK(h, hipGetLastError());
+  return MZ_OK;
+}
+
+// mz_rollout_head with a context (include/mazestep.h); ctx == NULL: mz_rollout_head itself
+int32_t mz_rollout_ctx(mz_handle* h, const mz_rollout_io* io, const mz_head* head, const mz_context* ctx, void* stream) {
+  return rollout_ex(h, io, head, stream, ctx);
+}
+
+static int32_t rollout_ex(mz_handle* h, const mz_rollout_io* io, const mz_head* head, void* stream, const mz_context* ctx) {
   if (!h) return MZ_ERR_ARG;
   // a refusal names the entry the caller used: with a head that is mz_rollout_head, for the io-level checks and for the plan's
-  const char* who = head ? "mz_rollout_head" : "mz_rollout_ex";
+  const char* who = ctx ? "mz_rollout_ctx" : head ? "mz_rollout_head" : "mz_rollout_ex";
   auto fail = [&](const char* why) {
     char msg[224];
     snprintf(msg, sizeof(msg), "%s: %s", who, why);
@@ -1136,6 +1277,11 @@ static int32_t rollout_ex(mz_handle* h, const mz_rollout_io* io, const mz_head* 
   if (!io->actions_dev && !io->actor) return fail("neither io->actions_dev nor io->actor is given: exactly one is the action source");
   if (!io->actor && io->noise) return fail("io->noise without io->actor");
   if (!io->actor && io->critic) return fail("io->critic without io->actor");
+  if (ctx) {
+    if (!io->actor) return fail("a context needs io->actor: an open-loop rollout evaluates no network");
+    const int rc = ctx_args(h, who, ctx, true);
+    if (rc != MZ_OK) return rc;
+  }
   if (head) {
     const int rc = head_args(h, who, head, io->actor, io->noise, true);
     if (rc != MZ_OK) return rc;
@@ -1146,7 +1292,7 @@ static int32_t rollout_ex(mz_handle* h, const mz_rollout_io* io, const mz_head* 
   }
   if (io->next_obs_seq_dev && h->auto_reset && !h->final_obs)
     return fail("next_obs_seq_dev under auto-reset needs a bound final_obs buffer (mz_bind_final_obs): the contract is the same on every handle");
-  RolloutPlan p = rollout_plan(head ? who : (io->actor ? "mz_rollout_net" : "mz_rollout"), io->n_steps, io->obs_dev, io->reward_dev, io->done_dev,
+  RolloutPlan p = rollout_plan(head || ctx ? who : (io->actor ? "mz_rollout_net" : "mz_rollout"), io->n_steps, io->obs_dev, io->reward_dev, io->done_dev,
                                io->goal_idx_dev, io->info_dev, io->obs_seq_dev);
   p.next_obs_seq_dev = io->next_obs_seq_dev;
   if (!io->actor) {
@@ -1157,7 +1303,12 @@ static int32_t rollout_ex(mz_handle* h, const mz_rollout_io* io, const mz_head* 
     if (io->noise) { p.sample = 1; p.noise_seed = io->noise->seed; p.noise_step = io->noise->step; p.noise_mode = io->noise->mode; }
     if (head) { p.head = head; p.head_logA = logf((float)io->actor->action_scale); }
   }
-  const int rc = io->actor ? net_rollout_args(h, p) : open_loop_args(h, p);
+  p.ctx = ctx;
+  int rc = io->actor ? net_rollout_args(h, p) : open_loop_args(h, p);
+  if (rc == MZ_OK && ctx) {
+    DeviceScope scope(h->device);
+    rc = ctx_prepare(h, ctx);
+  }
   return rc != MZ_OK ? rc : rollout_run(h, p, stream);
 }
 

@@ -64,6 +64,10 @@ struct mz_handle {
   const float* nrm_mean;
   const float* nrm_inv_std;
   float nrm_clip;
+  // context inputs (mz_context): the identity normaliser [2][obs_dim] (zeros, then ones) of a call with a context and no bound
+  // normaliser, and the [n][MZ_MAX_CONTEXT] old columns of the relative transition; both allocated on first use, freed by mz_destroy
+  float* ctx_ident;
+  float* ctx_old;
 };
 
 // ---- ant_kernels.hip
@@ -123,6 +127,8 @@ struct RolloutPlan {
   // entry
   const mz_head* head;
   float head_logA;
+  // a context behind the observation (mz_rollout_ctx; NULL: none): such a plan runs the launch-by-launch loop on every handle
+  const mz_context* ctx;
 };
 
 // The kernels a closed-loop plan runs: what every entry launched before there was a plan, and what it must go on launching.

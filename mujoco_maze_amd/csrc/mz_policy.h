@@ -63,6 +63,16 @@
 // that computes an element nor on whether a kernel stages the row (the NRM kernels: a second row in LDS) or computes it again; numpy
 // reproduces it bit for bit (policy.py normalize_reference), so an affine or ReLU network without squash on normalised rows stays
 // bit-reproducible.  The env itself never sees y: observations, the task predicate and info stay raw.
+//
+// Context inputs (mz_context; mzp_input_row, mzp_ctx_next below): a per-env row c of cdim <= MZ_MAX_CONTEXT floats that every network
+// reads BEHIND the observation.  The input row is r = [y | c], obs_dim + cdim entries: y the observation, normalised as above while a
+// normaliser is bound and the raw bits otherwise, c never normalised and never clipped; the unit functions below then run on r with
+// obs_dim + cdim in place of obs_dim, so the context terms are the last terms of every first-layer sum and the packed layouts are
+// those of a wider observation.  The kernels stage r once per group in the row the normaliser already stages (the NRM instantiations,
+// grown by MZ_MAX_CONTEXT floats); without a bound normaliser they run with the identity normaliser — mean 0, inv_std 1, clip +inf —
+// through which every bit pattern passes unchanged: x - 0 = x (-0 stays -0), x * 1 = x, neither select fires, a NaN stays one.
+// HIRO's goal transition of a rollout (MZ_CTX_RELATIVE), element d < D, fp32, two roundings:  tmp = c[d] + s[d];  c[d] = tmp - s'[d]
+// with s, s' the RAW rows before and behind the step; applied where the step did not end the episode.
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -129,6 +139,26 @@ MZP_HD float mzp_norm_elem(float x, float mean, float inv_std, float c) {
 // THE normalised row: y[obs_dim] from x[obs_dim] (the kernels spread the elements over the lanes of a group: mzp_group_norm)
 MZP_HD void mzp_norm_row(const float* x, const float* mean, const float* inv_std, float c, int obs_dim, float* y) {
   for (int i = 0; i < obs_dim; i++) y[i] = mzp_norm_elem(x[i], mean[i], inv_std[i], c);
+}
+
+// ------------------------------------------------------------------ context inputs (the head of this file)
+// THE input row r[obs_dim + cdim] = [y | c]: y = mzp_norm_row of x with a normaliser (mean != NULL), else x; c as it is
+MZP_HD void mzp_input_row(const float* x, int obs_dim, const float* mean, const float* inv_std, float clip, const float* c, int cdim, float* r) {
+  for (int i = 0; i < obs_dim; i++) r[i] = mean ? mzp_norm_elem(x[i], mean[i], inv_std[i], clip) : x[i];
+  for (int i = 0; i < cdim; i++) r[obs_dim + i] = c[i];
+}
+
+// one element of the relative transition: the context that goes with s2 when c went with s
+MZP_HD float mzp_ctx_next(float c, float s, float s2) {
+#pragma clang fp contract(off) reassociate(off)
+  const float tmp = c + s;
+  return tmp - s2;
+}
+
+// THE transition of one row: c[d] for d < rel_dims from the raw rows s (acted on) and s2 (produced), unless the step ended the episode
+MZP_HD void mzp_ctx_transition_row(float* c, int rel_dims, const float* s, const float* s2, int done) {
+  if (done) return;
+  for (int d = 0; d < rel_dims; d++) c[d] = mzp_ctx_next(c[d], s[d], s2[d]);
 }
 
 // ------------------------------------------------------------------ stochastic policies (definitions: the head of this file)
@@ -351,16 +381,25 @@ __device__ __forceinline__ void mzp_wave_sync() {
 }
 
 // the normaliser of one launch (mz_bind_obs_norm): [obs_dim] device arrays shared by all envs, read in stream order
+// and, with a context bound to the call, the context rows: ctx [rows][cdim] (cdim == 0: none), staged behind the normalised row
 struct mzp_norm {
   const float* mean;
   const float* inv_std;
   float clip;
+  int cdim;
+  const float* ctx;
 };
 
 // mzp_norm_row on a group: lanes l, l + G, ... each own the elements i = l, l + G, ... of y (LDS of this group), read from the raw
 // row x.  No lane of the group may still read y on entry, and the caller hands y over (mzp_wave_sync) before a unit reads it.
 __device__ __forceinline__ void mzp_group_norm(int l, int G, mzp_norm nm, int obs_dim, const float* x, float* y) {
   for (int i = l; i < obs_dim; i += G) y[i] = mzp_norm_elem(x[i], nm.mean[i], nm.inv_std[i], nm.clip);
+}
+
+// the context half of mzp_input_row on a group: lanes l, l + G, ... each own the elements i = l, l + G, ... of yc = y + obs_dim, the
+// tail of the staged row, copied from the row's context c; under the hand-offs of mzp_group_norm
+__device__ __forceinline__ void mzp_group_ctx(int l, int G, const float* c, int cdim, float* yc) {
+  for (int i = l; i < cdim; i += G) yc[i] = c[i];
 }
 
 // One row on a group of G adjacent lanes of a wavefront (this lane: l): lanes l, l + G, ... each own one hidden unit, the hidden

@@ -522,20 +522,36 @@ class VecMazeEnv:
         widths, act = policy.net_shape(hidden, activation, what)
         return widths, act, bool(np.ndim(hidden) == 0 and act == 0)
 
-    def _policy_params(self, params, hidden, stochastic: bool = False, log_std: str = "param"):
+    def _policy_params(self, params, hidden, stochastic: bool = False, log_std: str = "param", cdim: int = 0):
         """params as a contiguous float32 device tensor [npar] or [N, npar] (stochastic: npar_s = npar + nu, log_std behind the
         network; log_std="state": the head count, an output layer of 2 nu units); returns (tensor, param_env_stride)."""
         from mujoco_maze_amd import policy
 
         torch = self._torch
-        npar = policy.param_count(self.obs_dim, self.nu, hidden, stochastic, log_std)
+        npar = policy.param_count(self.obs_dim + cdim, self.nu, hidden, stochastic, log_std)
         p = params if torch.is_tensor(params) else torch.as_tensor(np.asarray(params, dtype=np.float32), device=self.device)
         if p.dtype != torch.float32 or not p.is_contiguous() or p.device != self.device:
             p = p.to(device=self.device, dtype=torch.float32).contiguous()
         if tuple(p.shape) not in ((npar,), (self.num_envs, npar)):
-            raise ValueError(f"params must have shape {(npar,)} (one policy) or {(self.num_envs, npar)} (one per env) for obs_dim {self.obs_dim}, "
-                             f"nu {self.nu}, hidden {hidden}, got {tuple(p.shape)}")
+            raise ValueError(f"params must have shape {(npar,)} (one policy) or {(self.num_envs, npar)} (one per env) for obs_dim {self.obs_dim}"
+                             f"{f' + context {cdim}' if cdim else ''}, nu {self.nu}, hidden {hidden}, got {tuple(p.shape)}")
         return p, (npar if p.dim() == 2 else 0)
+
+    def _context(self, context, in_place: bool = False):
+        """context as a contiguous float32 device tensor [N, C], 1 <= C <= MZ_MAX_CONTEXT; in_place (rollouts, which update it): the
+        caller's own tensor or a ValueError."""
+        torch = self._torch
+        if in_place:
+            c = context
+            if not torch.is_tensor(c) or c.dtype != torch.float32 or c.device != self.device or not c.is_contiguous():
+                raise ValueError(f"context must be a contiguous float32 tensor on {self.device}: a rollout updates it in place")
+        else:
+            c = context if torch.is_tensor(context) else torch.as_tensor(np.asarray(context, dtype=np.float32), device=self.device)
+            if c.dtype != torch.float32 or not c.is_contiguous() or c.device != self.device:
+                c = c.to(device=self.device, dtype=torch.float32).contiguous()
+        if c.dim() != 2 or c.shape[0] != self.num_envs or not 1 <= c.shape[1] <= _capi.MAX_CONTEXT:
+            raise ValueError(f"context must have shape ({self.num_envs}, C) with 1 <= C <= {_capi.MAX_CONTEXT} (MZ_MAX_CONTEXT), got {tuple(c.shape)}")
+        return c
 
     def _policy_obs(self, obs):
         torch = self._torch
@@ -546,19 +562,30 @@ class VecMazeEnv:
             o = o.to(device=self.device, dtype=torch.float32).contiguous()
         return o
 
-    def policy_act(self, params, obs=None, hidden=0, squash: bool = False, action_scale: float = 1.0, activation: str = "tanh"):
+    def policy_act(self, params, obs=None, hidden=0, squash: bool = False, action_scale: float = 1.0, activation: str = "tanh", context=None):
         """Actions [N, nu] of a small policy evaluated on the device (mz_policy_act): affine (`hidden=0`) or one tanh hidden layer of
         up to 64 units; `squash` makes the output action_scale * tanh(.).  params: float32 [npar] (one policy for all envs) or
         [N, npar] (one per env), packed by `mujoco_maze_amd.policy.pack` / `pack_linear`; obs: [N, obs_dim], default the env's last
         returned observation.  The actions are not clamped (step() clamps where the reference does).  A new tensor per call.
 
         `hidden` may also be a sequence of one or two widths, e.g. `(64, 64)` (params packed by `policy.pack_mlp`), and
-        `activation="relu"` makes the hidden units ReLU instead of tanh, one choice for both layers (mz_net_act)."""
+        `activation="relu"` makes the hidden units ReLU instead of tanh, one choice for both layers (mz_net_act).
+
+        context: float32 [N, C], 1 <= C <= 32 — a per-env row (a goal, a subgoal, a skill) the network reads BEHIND the observation:
+        its input row is [obs | context], obs normalised as usual while a normaliser is bound, the context never; params are packed
+        for obs_dim + C inputs (`policy.param_count(obs_dim + C, ...)`).  `policy.reference(params, policy.context_row(obs, context), ..)`
+        is the numpy model.  One mz_net_eval_ctx call."""
         widths, act, legacy = self._net_kind(hidden, activation)
-        p, stride = self._policy_params(params, hidden)
+        cx = None if context is None else self._context(context)
+        p, stride = self._policy_params(params, hidden, cdim=0 if cx is None else int(cx.shape[1]))
         o = self._obs if obs is None else self._policy_obs(obs)
         out = self._torch.empty((self.num_envs, self.nu), dtype=self._torch.float32, device=self.device)
-        if legacy:
+        if cx is not None:
+            net = _capi.make_net(_ptr(p), stride, widths, act, squash, action_scale)
+            ctx = _capi.make_context(_ptr(cx), cx.shape[1])
+            rc = self._lib.mz_net_eval_ctx(self._h, C.byref(net), None, None, C.byref(ctx), _ptr(o), _ptr(out), None, self._stream())
+            _capi.check(self._lib, self._h, rc, "mz_net_eval_ctx")
+        elif legacy:
             rc = self._lib.mz_policy_act(self._h, _ptr(p), stride, int(hidden), 1 if squash else 0, float(action_scale), _ptr(o), _ptr(out), self._stream())
             _capi.check(self._lib, self._h, rc, "mz_policy_act")
         else:
@@ -569,7 +596,8 @@ class VecMazeEnv:
 
     def rollout_policy(self, params, steps: int, hidden=0, squash: bool = False, action_scale: float = 1.0, obs=None,
                        return_obs: bool = False, return_actions: bool = False, value_params=None, value_hidden=0, gae=None,
-                       activation: str = "tanh", value_activation: str = "tanh", return_next_obs: bool = False):
+                       activation: str = "tanh", value_activation: str = "tanh", return_next_obs: bool = False, context=None,
+                       context_update=None, context_dims=None, return_contexts: bool = False):
         """K = `steps` closed-loop steps in one call: a = policy(obs); obs, reward, done = step(a) — exactly what K times
         (`policy_act`, `step`) give, state and outputs bit for bit.  params / hidden / squash / action_scale as in `policy_act`.
         The policy acts first on the env's last returned observation (what reset / step / rollout left in the observation buffer),
@@ -589,9 +617,12 @@ class VecMazeEnv:
         ReLU units, actor or critic, makes the call one mz_rollout_net.
 
         return_next_obs: info["next_observations"] [K, N, obs_dim] as in `rollout` (raw rows, whether or not a normaliser is bound);
-        the call is then one mz_rollout_ex."""
+        the call is then one mz_rollout_ex.
+
+        context / context_update / context_dims / return_contexts: see `rollout_policy_sample`."""
         return self._rollout_closed_loop(False, params, steps, hidden, squash, action_scale, obs, None, None, return_obs, return_actions,
-                                         value_params, value_hidden, gae, activation, value_activation, return_next_obs)
+                                         value_params, value_hidden, gae, activation, value_activation, return_next_obs, context=context,
+                                         context_update=context_update, context_dims=context_dims, return_contexts=return_contexts)
 
     def _noise_args(self, noise_seed, noise_step, advance: int):
         """(noise_seed, noise_step) of a draw as uint64: the env's own seed and counter where the caller gives none; the counter
@@ -621,7 +652,7 @@ class VecMazeEnv:
 
     def policy_sample(self, params, obs=None, hidden=0, squash: bool = False, action_scale: float = 1.0, noise_seed: Optional[int] = None,
                       noise_step: Optional[int] = None, activation: str = "tanh", noise: str = "pre_squash", log_std: str = "param",
-                      log_std_bounds=(-20.0, 2.0), squashed_logp: bool = False):
+                      log_std_bounds=(-20.0, 2.0), squashed_logp: bool = False, context=None):
         """One draw from a diagonal-Gaussian policy on the device (mz_policy_sample): (actions [N, nu], logp [N]).  params: float32
         [npar_s] or [N, npar_s], the vector of `policy_act` followed by log_std [nu] (`policy.pack(..., log_std=)`).  With m the
         network's pre-squash output, a = m + exp(log_std) * eps, or action_scale * tanh(.) of that with `squash`; logp is the density
@@ -643,17 +674,27 @@ class VecMazeEnv:
         (`policy.pack_mlp(.., log_std_head=)`, `policy.param_count(.., log_std="state")`); the raw log-std is clamped to
         `log_std_bounds` (lo, hi; -inf / inf switch a side off).  squashed_logp (needs `squash`): logp is the density of the squashed
         action action_scale * tanh(z) — the tanh correction applied on the device in a form that stays finite wherever z is — which
-        is the sample SAC's entropy term takes.  `policy.sample_reference(.., log_std="state")` is the numpy model."""
+        is the sample SAC's entropy term takes.  `policy.sample_reference(.., log_std="state")` is the numpy model.
+
+        context as in `policy_act`: the network reads [obs | context]; noise, logp and the head are unchanged (mz_net_eval_ctx)."""
         mode = _capi.noise_mode(noise)
         head = self._head(log_std, log_std_bounds, squashed_logp, squash, mode)
         widths, act, legacy = self._net_kind(hidden, activation)
-        p, stride = self._policy_params(params, hidden, stochastic=True, log_std=log_std)
+        cx = None if context is None else self._context(context)
+        p, stride = self._policy_params(params, hidden, stochastic=True, log_std=log_std, cdim=0 if cx is None else int(cx.shape[1]))
         o = self._obs if obs is None else self._policy_obs(obs)
         torch = self._torch
         out = torch.empty((self.num_envs, self.nu), dtype=torch.float32, device=self.device)
         logp = torch.empty(self.num_envs, dtype=torch.float32, device=self.device)
         seed, step = self._noise_args(noise_seed, noise_step, 1)
-        if head is not None:
+        if cx is not None:
+            net = _capi.make_net(_ptr(p), stride, widths, act, squash, action_scale)
+            nz = _capi.make_noise(mode, seed.value, step.value)
+            ctx = _capi.make_context(_ptr(cx), cx.shape[1])
+            rc = self._lib.mz_net_eval_ctx(self._h, C.byref(net), C.byref(head) if head is not None else None, C.byref(nz), C.byref(ctx), _ptr(o),
+                                           _ptr(out), _ptr(logp), self._stream())
+            _capi.check(self._lib, self._h, rc, "mz_net_eval_ctx")
+        elif head is not None:
             net = _capi.make_net(_ptr(p), stride, widths, act, squash, action_scale)
             nz = _capi.make_noise(mode, seed.value, step.value)
             rc = self._lib.mz_net_sample_head(self._h, C.byref(net), C.byref(head), C.byref(nz), _ptr(o), _ptr(out), _ptr(logp), self._stream())
@@ -677,7 +718,8 @@ class VecMazeEnv:
                               noise_seed: Optional[int] = None, noise_step: Optional[int] = None, return_obs: bool = False,
                               return_actions: bool = False, value_params=None, value_hidden=0, gae=None, activation: str = "tanh",
                               value_activation: str = "tanh", noise: str = "pre_squash", return_next_obs: bool = False,
-                              log_std: str = "param", log_std_bounds=(-20.0, 2.0), squashed_logp: bool = False):
+                              log_std: str = "param", log_std_bounds=(-20.0, 2.0), squashed_logp: bool = False, context=None,
+                              context_update=None, context_dims=None, return_contexts: bool = False):
         """K = `steps` closed-loop steps with a sampled action each, in one call: exactly what K times (`policy_sample` with
         noise_step + k, `step`) give, state and outputs bit for bit.  Everything as in `rollout_policy`, plus info["logp"] [K, N], the
         log-probabilities of the draws (see `policy_sample`); info["actions"] [K, N, nu] with `return_actions` holds the sampled
@@ -707,37 +749,57 @@ class VecMazeEnv:
         inside the fused rollout kernels of the Point, Swimmer and Reacher (chains of five or six links excepted), a loop of the head
         kernel and the step's launches inside the call on every other handle —, bit for bit what K times
         (`policy_sample(log_std="state")`, `step`) give; info["logp"] is then the entropy term's sample.  Critic, return_next_obs, a
-        bound normaliser compose as above."""
+        bound normaliser compose as above.
+
+        context: a contiguous float32 device tensor [N, C], 1 <= C <= 32, that actor and critic read behind the observation (see
+        `policy_act`; both networks packed for obs_dim + C inputs).  It is IN/OUT: on return it holds what step K would read, so two
+        calls in a row equal one call over the joined steps.  context_update=None holds it for the whole call;
+        context_update="relative" with context_dims=D (1 <= D <= min(C, obs_dim)) applies HIRO's goal transition after every step k, in
+        float32, where dones[k] == 0:  tmp = c[:D] + s[:D];  c[:D] = tmp - s'[:D]  with s the raw row the actor acted on and s' the
+        raw row the step produced ("next_observations"[k]); an env that finished keeps its context, entries d >= D hold.
+        info["values"][k] reads the context of step k, info["next_values"][k] the context after the transition.  return_contexts:
+        info["contexts"] [K, N, C], the context the networks read at step k.  `policy.context_transition_reference` is the numpy
+        model.  One mz_rollout_ctx call, bit for bit what K times (`value`, `policy_sample(context=c, noise_step + k)`, `step`,
+        `value`, the transition in torch) give; where the host has work between steps this method runs that loop itself."""
         return self._rollout_closed_loop(True, params, steps, hidden, squash, action_scale, obs, noise_seed, noise_step, return_obs,
                                          return_actions, value_params, value_hidden, gae, activation, value_activation, return_next_obs, noise,
-                                         log_std, log_std_bounds, squashed_logp)
+                                         log_std, log_std_bounds, squashed_logp, context, context_update, context_dims, return_contexts)
 
-    def _value_params(self, value_params, hidden):
+    def _value_params(self, value_params, hidden, cdim: int = 0):
         """A critic's parameters as a contiguous float32 device tensor [nvpar] or [N, nvpar]; returns (tensor, env_stride)."""
         from mujoco_maze_amd import policy
 
         torch = self._torch
         policy.net_shape(hidden, what="the critic's hidden")
-        npar = policy.param_count(self.obs_dim, 1, hidden)
+        npar = policy.param_count(self.obs_dim + cdim, 1, hidden)
         p = value_params if torch.is_tensor(value_params) else torch.as_tensor(np.asarray(value_params, dtype=np.float32), device=self.device)
         if p.dtype != torch.float32 or not p.is_contiguous() or p.device != self.device:
             p = p.to(device=self.device, dtype=torch.float32).contiguous()
         if tuple(p.shape) not in ((npar,), (self.num_envs, npar)):
             raise ValueError(f"value_params must have shape {(npar,)} (one critic) or {(self.num_envs, npar)} (one per env) for obs_dim "
-                             f"{self.obs_dim}, hidden {hidden}, got {tuple(p.shape)}")
+                             f"{self.obs_dim}{f' + context {cdim}' if cdim else ''}, hidden {hidden}, got {tuple(p.shape)}")
         return p, (npar if p.dim() == 2 else 0)
 
-    def value(self, value_params, obs=None, hidden=0, activation: str = "tanh"):
+    def value(self, value_params, obs=None, hidden=0, activation: str = "tanh", context=None):
         """Values [N] of a small critic evaluated on the device (mz_value): a policy of `policy_act` with one output, never squashed —
         affine (`hidden=0`) or one tanh hidden layer of up to 64 units.  value_params: float32 [nvpar] (one critic for all envs) or
         [N, nvpar] (one per env), nvpar = policy.param_count(obs_dim, 1, hidden), packed by `policy.pack` / `pack_linear` with
         nu = 1; obs: [N, obs_dim], default the env's last returned observation.  A new tensor per call.  `hidden` may also be a
-        sequence of one or two widths (`policy.pack_mlp`), `activation="relu"` makes the hidden units ReLU (mz_net_value)."""
+        sequence of one or two widths (`policy.pack_mlp`), `activation="relu"` makes the hidden units ReLU (mz_net_value).
+
+        context as in `policy_act`: the critic reads [obs | context], value_params packed for obs_dim + C inputs (mz_net_value_ctx).
+        `value(vp, obs=rows, context=actions)` is Q(s, a) on the device."""
         widths, act, legacy = self._net_kind(hidden, activation, "the critic's hidden")
-        p, stride = self._value_params(value_params, hidden)
+        cx = None if context is None else self._context(context)
+        p, stride = self._value_params(value_params, hidden, 0 if cx is None else int(cx.shape[1]))
         o = self._obs if obs is None else self._policy_obs(obs)
         out = self._torch.empty(self.num_envs, dtype=self._torch.float32, device=self.device)
-        if legacy:
+        if cx is not None:
+            net = _capi.make_net(_ptr(p), stride, widths, act)
+            ctx = _capi.make_context(_ptr(cx), cx.shape[1])
+            rc = self._lib.mz_net_value_ctx(self._h, C.byref(net), C.byref(ctx), _ptr(o), _ptr(out), self._stream())
+            _capi.check(self._lib, self._h, rc, "mz_net_value_ctx")
+        elif legacy:
             rc = self._lib.mz_value(self._h, _ptr(p), stride, int(hidden), _ptr(o), _ptr(out), self._stream())
             _capi.check(self._lib, self._h, rc, "mz_value")
         else:
@@ -811,12 +873,21 @@ class VecMazeEnv:
 
     def _rollout_closed_loop(self, sample: bool, params, steps, hidden, squash, action_scale, obs, noise_seed, noise_step, return_obs,
                              return_actions, value_params, value_hidden, gae, activation="tanh", value_activation="tanh",
-                             return_next_obs=False, noise="pre_squash", log_std="param", log_std_bounds=(-20.0, 2.0), squashed_logp=False):
+                             return_next_obs=False, noise="pre_squash", log_std="param", log_std_bounds=(-20.0, 2.0), squashed_logp=False,
+                             context=None, context_update=None, context_dims=None, return_contexts=False):
         """rollout_policy (sample False) / rollout_policy_sample (sample True): the defining loop where the host has work between
         steps, else one C call — mz_rollout_head with log_std="state"; mz_rollout_ex with return_next_obs or noise="action";
         mz_rollout_net where a network, actor or critic, needs mz_net; mz_rollout_actor_critic with a critic; mz_rollout_policy_sample /
-        mz_rollout_policy without one."""
+        mz_rollout_policy without one.  With a context: mz_rollout_ctx, whatever else the call asks for."""
         torch, n = self._torch, self.num_envs
+        if context is None:
+            if context_update is not None or context_dims is not None or return_contexts:
+                raise ValueError("context_update, context_dims and return_contexts need context=")
+            cx, cdim, cupd, D = None, 0, _capi.CTX_HOLD, 0
+        else:
+            cx = self._context(context, in_place=True)
+            cdim = int(cx.shape[1])
+            cupd, D = _capi.context_args(cdim, self.obs_dim, context_update, context_dims)
         mode = _capi.noise_mode(noise)
         head = self._head(log_std, log_std_bounds, squashed_logp, squash, mode) if sample else None
         extended = return_next_obs or mode != _capi.NOISE_PRE_SQUASH or head is not None
@@ -826,10 +897,10 @@ class VecMazeEnv:
         if gae is not None:
             gamma, lam = (float(x) for x in gae)
         widths, act, legacy = self._net_kind(hidden, activation)
-        p, stride = self._policy_params(params, hidden, stochastic=sample, log_std=log_std if sample else "param")
+        p, stride = self._policy_params(params, hidden, stochastic=sample, log_std=log_std if sample else "param", cdim=cdim)
         if with_critic:
             vwidths, vact, vlegacy = self._net_kind(value_hidden, value_activation, "the critic's hidden")
-            vp, vstride = self._value_params(value_params, value_hidden)
+            vp, vstride = self._value_params(value_params, value_hidden, cdim)
             legacy = legacy and vlegacy
         K = int(steps)
         if not 1 <= K <= 65536:
@@ -844,22 +915,32 @@ class VecMazeEnv:
         for key in (("logp",) if sample else ()) + (("values", "next_values") if with_critic else ()) + (("advantages", "returns") if gae is not None else ()):
             if key not in buf:
                 buf[key] = torch.empty((K, n), dtype=torch.float32, device=self.device)
+        if return_contexts and ("contexts" not in buf or buf["contexts"].shape[2] != cdim):
+            buf["contexts"] = torch.empty((K, n, cdim), dtype=torch.float32, device=self.device)
         seed, step = self._noise_args(noise_seed, noise_step, K) if sample else (C.c_uint64(0), C.c_uint64(0))
         if self._host_rewards or (self._env_goals is not None and self._auto_reset):
             for k in range(K):
+                if return_contexts:
+                    buf["contexts"][k] = cx
+                if D:
+                    s_old = self._obs[:, :D].clone()
                 if with_critic:
-                    buf["values"][k] = self.value(vp, None, value_hidden, value_activation)
+                    buf["values"][k] = self.value(vp, None, value_hidden, value_activation, cx)
                 if sample:
                     a, buf["logp"][k] = self.policy_sample(p, None, hidden, squash, action_scale, seed.value, step.value + k, activation, noise,
-                                                           log_std, log_std_bounds, squashed_logp)
+                                                           log_std, log_std_bounds, squashed_logp, cx)
                 else:
-                    a = self.policy_act(p, None, hidden, squash, action_scale, activation)
+                    a = self.policy_act(p, None, hidden, squash, action_scale, activation, cx)
                 o, rew, done, inf = self.step(a)
                 buf["reward"][k], buf["done"][k], buf["goal"][k], buf["info"][k] = rew, done, inf["goal_index"], self._info
+                if D:  # the relative transition where the episode goes on: there `o` is the row the step produced
+                    nxt = cx[:, :D] + s_old
+                    nxt = nxt - o[:, :D]
+                    cx[:, :D] = torch.where((done == 0).unsqueeze(1), nxt, cx[:, :D])
                 if with_critic:
-                    nv = self.value(vp, None, value_hidden, value_activation)
+                    nv = self.value(vp, None, value_hidden, value_activation, cx)
                     if self._auto_reset:  # an env that finished: the value of its terminal row, which `o` no longer holds
-                        nv = torch.where(done != 0, self.value(vp, inf["final_observation"], value_hidden, value_activation), nv)
+                        nv = torch.where(done != 0, self.value(vp, inf["final_observation"], value_hidden, value_activation, cx), nv)
                     buf["next_values"][k] = nv
                 if return_obs:
                     buf["obs_seq"][k] = o
@@ -867,7 +948,7 @@ class VecMazeEnv:
                     buf["next_obs_seq"][k] = self._next_obs_row(o, done, inf)
                 if return_actions:
                     buf["actions"][k] = a
-        elif extended:
+        elif extended or cx is not None:
             io = _capi.make_rollout_io(K, actor=_capi.make_net(_ptr(p), stride, widths, act, squash, action_scale),
                                        noise=_capi.make_noise(mode, seed.value, step.value) if sample else None,
                                        critic=_capi.make_net(_ptr(vp), vstride, vwidths, vact) if with_critic else None,
@@ -879,7 +960,11 @@ class VecMazeEnv:
                                        value_seq_dev=_ptr(buf["values"]) if with_critic else None,
                                        next_value_seq_dev=_ptr(buf["next_values"]) if with_critic else None,
                                        next_obs_seq_dev=_ptr(buf["next_obs_seq"]) if return_next_obs else None)
-            if head is not None:
+            if cx is not None:
+                ctx = _capi.make_context(_ptr(cx), cdim, cupd, D, _ptr(buf["contexts"]) if return_contexts else None)
+                rc = self._lib.mz_rollout_ctx(self._h, C.byref(io), C.byref(head) if head is not None else None, C.byref(ctx), self._stream())
+                _capi.check(self._lib, self._h, rc, "mz_rollout_ctx")
+            elif head is not None:
                 rc = self._lib.mz_rollout_head(self._h, C.byref(io), C.byref(head), self._stream())
                 _capi.check(self._lib, self._h, rc, "mz_rollout_head")
             else:
@@ -914,6 +999,8 @@ class VecMazeEnv:
             per_step["values"], per_step["next_values"] = buf["values"], buf["next_values"]
         if sample:
             per_step["logp"] = buf["logp"]
+        if return_contexts:
+            per_step["contexts"] = buf["contexts"]
         if gae is not None:
             per_step["advantages"], per_step["returns"] = self.gae(buf["reward"], buf["done"], buf["values"], buf["next_values"], gamma, lam,
                                                                    out=(buf["advantages"], buf["returns"]))

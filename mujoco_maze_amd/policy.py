@@ -449,6 +449,38 @@ def normalize_reference(obs, mean, inv_std, clip: float = 10.0):
     return y
 
 
+MAX_CONTEXT = 32  # MZ_MAX_CONTEXT (include/mazestep.h)
+
+
+def context_row(obs, context, mean=None, inv_std=None, clip: float = 10.0):
+    """The input row r = [y | c] of a network with a context (csrc/mz_policy.h mzp_input_row): y = `normalize_reference(obs, ...)`
+    with a normaliser (mean given), else obs; c = context as it is, never normalised.  obs [..., obs_dim], context [..., C] with
+    1 <= C <= MAX_CONTEXT.  The model of a device call with `context=` is `reference(params, context_row(obs, ctx, ...), ...)` (and
+    `sample_reference`, `value_reference` likewise) with params packed for obs_dim + C inputs."""
+    x, c = _np(obs), _np(context)
+    if c.shape[:-1] != x.shape[:-1] or not 1 <= c.shape[-1] <= MAX_CONTEXT:
+        raise ValueError(f"context must be {x.shape[:-1]} + (C,) with 1 <= C <= {MAX_CONTEXT}, got {c.shape}")
+    y = normalize_reference(x, mean, inv_std, clip) if mean is not None else x
+    return np.concatenate([y, c], axis=-1).astype(np.float32)
+
+
+def context_transition_reference(context, obs, next_obs, dones, dims: int):
+    """HIRO's goal transition h(s, g, s') = s + g - s' of `context_update="relative"` (csrc/mz_policy.h mzp_ctx_next) in float32, a
+    sum then a difference, two roundings:  tmp = c[d] + s[d];  c[d] = tmp - s'[d]  for d < dims, where dones == 0; rows with
+    dones != 0 and entries d >= dims hold.  context [N, C]; obs, next_obs [N, obs_dim] the RAW rows before and behind the step (the
+    "next_observations" row, never normalised); dones [N].  Returns a new float32 [N, C]; bit-equal to the device."""
+    c, s, s2 = _np(context).copy(), _np(obs), _np(next_obs)
+    d = int(dims)
+    if c.ndim != 2 or not 1 <= d <= min(c.shape[1], s.shape[-1]):
+        raise ValueError(f"dims must be 1 .. min(C, obs_dim) = {min(c.shape[-1], s.shape[-1])} for a context [N, C], got {d}")
+    go = np.asarray(dones).reshape(-1) == 0
+    with np.errstate(over="ignore", invalid="ignore"):
+        tmp = (c[:, :d] + s[:, :d]).astype(np.float32)
+        new = (tmp - s2[:, :d]).astype(np.float32)
+    c[:, :d] = np.where(go[:, None], new, c[:, :d])
+    return c
+
+
 def return_scan_reference(rewards, dones, gamma: float = 1.0, carry=None, length_carry=None):
     """The forward scan of csrc/mz_returns.h (mz_return_scan) on [K, N] rows, float32, every operation rounded separately, k from 0 up:
 

@@ -32,6 +32,12 @@ second nn.Linear of a SAC actor, small weights, bias -0.5), squashed actions, an
 squashed action.  K x (env.policy_sample(log_std="state") + env.step + torch.where on the terminal rows) with the rows kept against
 one env.rollout_policy_sample(..., log_std="state", return_obs, return_actions, return_next_obs), and that call without the next rows.
     python tools/rollout_bench.py --policy 64,64 --activation relu --head state --squashed-logp --steps 128 --ids PointUMaze-v0,SwimmerUMaze-v0,AntUMaze-v0
+With --policy H --sample --context C [--relative D] one goal-conditioned collection window: a [N, C] context behind the observation
+(both the torch-free legs below read [obs | context]; --relative D applies HIRO's goal transition to the first D entries after every
+step).  K x (env.policy_sample(context=) + env.step + the transition in torch) with the rows kept against one
+env.rollout_policy_sample(..., context=, context_update=, return_next_obs, return_contexts), and the call without a context at the
+same shape (a network on obs_dim inputs) beside them.
+    python tools/rollout_bench.py --policy 64,64 --activation relu --sample --context 15 --relative 3 --steps 10 --ids PointUMaze-v0,SwimmerUMaze-v0,AntUMaze-v0
 Kernel durations come from a run of their own:  rocprofv3 --kernel-trace --stats -d <dir> -- python tools/rollout_bench.py --seconds 0.2"""
 import argparse
 import json
@@ -214,6 +220,63 @@ def bench_sample(env_id, n, K, H, seconds, repeats, ACT="tanh", obs_norm=False):
     env.close()
     return {"env": env_id, "envs": n, "steps_per_window": K, "hidden": H, "activation": ACT, "obs_norm": bool(obs_norm), "sample": True, "fused": fused_flag, "flagged_envs": bad,
             **{name + "_env_steps_per_s": v for name, v in res.items()}}
+
+
+def bench_context(env_id, n, K, H, cdim, rel, seconds, repeats, ACT="tanh", obs_norm=False):
+    """K closed-loop steps of one shared Gaussian policy on [obs | context]: policy_sample(context=) + step + the transition in torch,
+    one rollout_policy_sample(context=); the same call without a context as the yardstick."""
+    dev = torch.device("cuda", 0)
+    env = mm.make(env_id, num_envs=n, auto_reset=True, device=dev, force_vec=True)
+    env.reset(seed=20260928)
+    g = torch.Generator(device=dev).manual_seed(1234)
+    bind_norm(env, obs_norm, dev, g)  # (no torch network in this mode)
+
+    def lin(out, fan_in):
+        k = fan_in ** -0.5
+        return (2 * torch.rand((out, fan_in), device=dev, generator=g) - 1) * k, (2 * torch.rand(out, device=dev, generator=g) - 1) * k
+
+    log_std = torch.full((env.nu,), -0.5)
+    params, _ = build_net(lin, env.obs_dim + cdim, env.nu, H, ACT, dev, log_std=log_std)
+    plain, _ = build_net(lin, env.obs_dim, env.nu, H, ACT, dev, log_std=log_std)
+    ctx0 = torch.randn((n, cdim), device=dev, generator=g).contiguous()
+    ctx = ctx0.clone()
+    upd = dict(context_update="relative", context_dims=rel) if rel else {}
+    rows = torch.empty((K, n, env.obs_dim), device=dev)
+    crow = torch.empty((K, n, cdim), device=dev)
+
+    def sample_step():
+        ctx.copy_(ctx0)
+        for k in range(K):
+            crow[k] = ctx
+            s_old = env._obs[:, :rel].clone() if rel else None
+            obs, _, done, info = env.step(env.policy_sample(params, hidden=H, activation=ACT, context=ctx)[0])
+            nxt = torch.where((done != 0).unsqueeze(1), info["final_observation"], obs)
+            rows[k] = nxt
+            if rel:
+                new = (ctx[:, :rel] + s_old) - nxt[:, :rel]
+                ctx[:, :rel] = torch.where((done != 0).unsqueeze(1), ctx[:, :rel], new)
+
+    def one_call():
+        ctx.copy_(ctx0)
+        env.rollout_policy_sample(params, K, hidden=H, activation=ACT, context=ctx, return_next_obs=True, return_contexts=True, **upd)
+
+    def no_context():
+        env.rollout_policy_sample(plain, K, hidden=H, activation=ACT, return_next_obs=True)
+
+    legs = (("sample_step", sample_step), ("rollout_context", one_call), ("rollout_plain", no_context))
+    for _ in range(4):
+        for _, fn in legs:
+            fn()
+    res = {name: [] for name, _ in legs}
+    for _ in range(repeats):
+        for name, fn in legs:
+            w, dt = leg(fn, 4, seconds, dev)
+            res[name].append(n * K * w / dt)
+    bad = int((env.status() & 3).ne(0).sum())
+    fused_flag = env.launch_info()["rollout_fused"]
+    env.close()
+    return {"env": env_id, "envs": n, "steps_per_window": K, "hidden": H, "activation": ACT, "obs_norm": bool(obs_norm), "context": cdim, "relative": rel,
+            "fused": fused_flag, "flagged_envs": bad, **{name + "_env_steps_per_s": v for name, v in res.items()}}
 
 
 def bench_critic(env_id, n, K, H, HV, seconds, repeats, ACT="tanh", obs_norm=False):
@@ -432,6 +495,25 @@ def main_critic(args):
                 f.write(json.dumps(r) + "\n")
 
 
+def main_context(args):
+    out = []
+    med = lambda v: sorted(v)[len(v) // 2]
+    print(f"goal-conditioned window, one shared Gaussian policy on [obs | context] (hidden {args.policy}, {args.activation} units, context {args.context}, "
+          f"{'relative ' + str(args.relative) if args.relative else 'hold'}), {args.steps} steps per window, {args.envs} envs, auto-reset, >= {args.seconds} s per leg, "
+          f"{args.repeats} alternating repeats; M env-steps/s, median (max - min)")
+    print("%-18s %5s %30s %26s %26s" % ("env", "fused", "policy_sample(context) + step", "rollout(context=)", "rollout without a context"))
+    for env_id in args.ids.split(","):
+        r = bench_context(env_id, args.envs, args.steps, args.policy, args.context, args.relative, args.seconds, args.repeats, args.activation, args.obs_norm)
+        out.append(r)
+        cell = lambda v: "%10.3f (%6.3f)" % (med(v) / 1e6, (max(v) - min(v)) / 1e6)
+        print("%-18s %5d %30s %26s %26s" % (env_id, r["fused"], cell(r["sample_step_env_steps_per_s"]), cell(r["rollout_context_env_steps_per_s"]),
+                                            cell(r["rollout_plain_env_steps_per_s"])), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            for r in out:
+                f.write(json.dumps(r) + "\n")
+
+
 def main_sample(args):
     out = []
     med = lambda v: sorted(v)[len(v) // 2]
@@ -485,6 +567,8 @@ def main():
     ap.add_argument("--noise", choices=("pre_squash", "action"), default="pre_squash", help="with --next-obs: where the exploration noise goes")
     ap.add_argument("--head", choices=("state",), default=None, help="with --policy H: a state-dependent log-std head on the actor (the SAC window)")
     ap.add_argument("--squashed-logp", action="store_true", help="with --head state: the log-probability of the squashed action")
+    ap.add_argument("--context", type=int, default=None, metavar="C", help="with --policy H --sample: a [N, C] context behind the observation (1 .. 32)")
+    ap.add_argument("--relative", type=int, default=0, metavar="D", help="with --context C: HIRO's goal transition on the first D entries after every step")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "rollout_bench.py measures on the GPU only"
     if args.sample and args.policy is None:
@@ -503,6 +587,12 @@ def main():
         ap.error("--head goes with --policy H alone (it samples and returns the next rows by itself)")
     if args.squashed_logp and args.head is None:
         ap.error("--squashed-logp goes with --head state")
+    if args.context is not None and (not args.sample or args.critic is not None or args.next_obs or args.head is not None):
+        ap.error("--context goes with --policy H --sample alone")
+    if args.relative and args.context is None:
+        ap.error("--relative goes with --context C")
+    if args.context is not None:
+        return main_context(args)
     if args.head is not None:
         return main_head(args)
     if args.next_obs:
