@@ -786,24 +786,29 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
   //   jown[C][a]  this lane's own COLUMN of contact C (zero when the contact does not see this dof) — the Hessian folds;
   //   Jf[m][a][k] the ROW a of this lane's own contact over all dofs k (zero outside hub + its leg) — J x as three DPP matvecs.
   // With them a Newton iteration touches no memory at all.
+  // The votes of each_contact's first five guards, taken once per solve: slot k is used by some env of the wave.  A vote at the
+  // call was two vector instructions in front of every guard (the compiler keeps the compare's lane mask across the solve and
+  // votes on it anew: v_cndmask 0 / 1, v_cmp_ne); a wave-uniform flag is one scalar instruction there.
+  const bool use[5] = {cx.any(ncon > 0), NB == 1 || cx.any(ncon > 1), NB == 1 || cx.any(ncon > 2), NB == 1 || cx.any(ncon > 3), cx.any(ncon > 4)};
   auto each_contact = [&](auto&& f) {  // f(C) for the contact slots some env of the wave uses (wave-uniform guards)
     // Slots 0 .. 3 one by one, nested: a wave whose largest count is 2 takes one taken branch per call.  In the settled rollout of
     // the bench the largest count among a wave's four envs is 2 in 59 % of the evaluations, 3 in 32 % and 4 in 2 %, so the block of
     // four ran 1.7 slots per call on zero columns.  Measured (profiles/slot_guards/ab.md, AntUMaze-v0 4096 envs): SQ_INSTS_VALU per
     // launch 7.13e7 -> 6.32e7, the mean wave's cycles -6.8 %, the launch — its slowest wave, more often one that needs three
     // slots — 0.2307 -> 0.2260 ms; 8192 envs (two waves per SIMD) -4.4 %.  Two things measured and left out (same file):
-    //   * the predicates once per solve, in scalar registers: 0.7 % faster still, but with ANY hoisted form the compiler packs and
-    //     contracts four blocks of the forward pass differently — every env's result moves in the last bits.  They stay at the call;
+    //   * the predicates once per solve, in scalar registers: 0.7 % faster still, but with the hoisted forms tried then the compiler
+    //     packed and contracted four blocks of the forward pass differently — every env's result moved in the last bits.  Since the
+    //     set-up of the solve was rearranged the votes can be taken once per solve (`use` above) with equal bits on all five dump
+    //     configurations: profiles/newton_slots/ab.md;
     //   * the same guards for the one-block ant: its waves hold two envs that mostly use the four slots, the three extra votes per
     //     call cost AntPush-v0 0.3 .. 0.5 %.  NB = 1 keeps one guard for the block of four.
     // A skipped slot leaves its jown[C] unwritten, as the slots from 4 up always have: own_col reads it inside each_contact only,
     // behind the same guards (ncon does not change within a solve).
-    auto more = [&](int k) { return NB == 1 || cx.any(ncon > k); };
-    if (cx.any(ncon > 0)) { f(std::integral_constant<int, 0>{});
-    if (more(1)) { f(std::integral_constant<int, 1>{});
-    if (more(2)) { f(std::integral_constant<int, 2>{});
-    if (more(3)) { f(std::integral_constant<int, 3>{});
-      if (cx.any(ncon > 4)) {
+    if (use[0]) { f(std::integral_constant<int, 0>{});
+    if (use[1]) { f(std::integral_constant<int, 1>{});
+    if (use[2]) { f(std::integral_constant<int, 2>{});
+    if (use[3]) { f(std::integral_constant<int, 3>{});
+      if (use[4]) {
         // (slots 4 .. 7 in pairs: the waves a launch waits for are those whose ants lean on a wall — five or six contacts — and two
         // skipped slots are 160 instructions per Newton iteration; measured 0.2971 -> 0.2949 ms)
         f(std::integral_constant<int, 4>{}); f(std::integral_constant<int, 5>{});
@@ -999,7 +1004,20 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
   // env-steps without one solve at the iteration cap, error quantiles against the float64 oracle identical to the search in every
   // iteration — take unit steps, and a CUSTOM task, maze or robot variant, whose stiffness nobody has soaked, runs with
   // ls_fast_iterations = 0 by default (maze_env.py): MuJoCo's line search in every iteration, monotone on any maze.
-  while (cx.any(!done) && it < ant_u(cx, K).max_iter) {
+  // Lane constants of the limit curvature: 1 on the lane that owns hinge position k, 0 elsewhere.  `Hrow[k] += (r == k) ? lact : 0`
+  // was a select and an add per hinge position and iteration; the multiply-add with the constant is one instruction and rounds
+  // once to the same value (1 * lact and 0 * lact are exact).  Opaque, so that they stay eight registers and do not come back as
+  // a select per use; the metric's kernel keeps its 256 + 67 registers and its 36 bytes of scratch, no accumulation-register copy
+  // enters the loop.
+  float onehot[8];
+#pragma unroll
+  for (int k = 0; k < 14; k++)
+    if ((k & 3) < 2) { onehot[2 * (k >> 2) + (k & 1)] = r == k ? 1.f : 0.f; asm("" : "+v"(onehot[2 * (k >> 2) + (k & 1)])); }
+  const AntU U = ant_u(cx, K);  // the solver's settings, unpacked once per solve (in the loop: a v_readfirstlane and bit-field operations per use)
+  // The two marks bracket the loop in the compiled code: tools/newton_slots.py and tests/test_ant_newton_loop_isa.py count the
+  // instructions of one iteration between them.
+  asm volatile("; newton loop begin");
+  while (cx.any(!done) && it < U.max_iter) {
     // ---- contact lanes: gradient block g3 and curvature block W of their contact, in registers; every lane of the row reads
     // them with `row_newbcast:c` (fold_contact<c>): no LDS publish, no hand-off wait
     float mycg[MA][8];
@@ -1087,7 +1105,7 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
     MZ_IF_OWNER(lsign != 0.f) { const float t = lsign * lact * ljar; g += t; ga += fabsf(t); }
 #pragma unroll
     for (int k = 0; k < 14; k++)
-      if ((k & 3) < 2) Hrow[k] += (r == k) ? lact : 0.f;  // hinge positions: the limit row's curvature on its own diagonal
+      if ((k & 3) < 2) Hrow[k] = fmaf(onehot[2 * (k >> 2) + (k & 1)], lact, Hrow[k]);  // hinge positions: the limit row's curvature on its own diagonal
     if (!isdof) { g = 0.f; ga = 0.f; }
     // converged: MuJoCo's scaled-gradient test, or the gradient is at the fp32 cancellation floor.  Not in the first iteration of a
     // solve (round 5): the state has moved since the warm start was a solution, so the test can hardly pass there, and an env
@@ -1097,7 +1115,7 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
     if (it > 0) {
       rsum2_sq(g, ga, gnorm, anorm);
       gnorm = sqrtf(gnorm); anorm = sqrtf(anorm);
-      if (!done && (ant_u(cx, K).inv_scale * gnorm < ant_u(cx, K).tol || gnorm <= ant_u(cx, K).rtol * anorm)) done = true;
+      if (!done && (U.inv_scale * gnorm < U.tol || gnorm <= U.rtol * anorm)) done = true;
     }
     if (!cx.any(!done)) { cx.tick(s, 5); break; }
     cx.tick(s, 5);
@@ -1113,10 +1131,11 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
     for (int m = 0; m < MA; m++)
       if (m == 0 || any2) MZ_IF_OWNER(iscon[m]) {
         const float u0 = u[m][0], u1 = u[m][1], u2 = u[m][2], w0 = u0 + v[m][0], w1 = u1 + v[m][1], w2 = u2 + v[m][2];
-        changed = changed || ((u0 + u1 < 0.f) != (w0 + w1 < 0.f)) || ((u0 - u1 < 0.f) != (w0 - w1 < 0.f)) || ((u0 + u2 < 0.f) != (w0 + w2 < 0.f)) ||
+        // (`|`, not `||`: the short circuit was an exec-mask region around three of the four tests)
+        changed = changed | ((u0 + u1 < 0.f) != (w0 + w1 < 0.f)) | ((u0 - u1 < 0.f) != (w0 - w1 < 0.f)) | ((u0 + u2 < 0.f) != (w0 + w2 < 0.f)) |
                   ((u0 - u2 < 0.f) != (w0 - w2 < 0.f));
       }
-    MZ_IF_OWNER(lsign != 0.f) changed = changed || ((ljar < 0.f) != (ljar + ljv < 0.f));
+    MZ_IF_OWNER(lsign != 0.f) changed = changed | ((ljar < 0.f) != (ljar + ljv < 0.f));
     if constexpr (NB == 1) {
       bdot(bcast<14>(search), bcast<15>(search), bv);
 #pragma unroll
@@ -1142,7 +1161,7 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
       // (AntPush with 50 fast iterations: 2024 of 2048 envs hit the iteration cap within 500 steps; profiles/r05/ls_iters.txt), a
       // few of them (3 .. 8 measure alike on the plain ant, 5 is best on the one-block mazes: ls_k.txt) do not cost an iteration (lock-step iterations per step 55 -> 55) and save the search's matvec + ~3 evaluations, two
       // reductions each: AntUMaze-v0 0.2754 -> 0.2555 ms per step, AntPush-v0 0.5009 -> 0.4551.  `it` is wave-uniform: no divergence.
-      const int ls_max = it < ant_u(cx, K).ls_fast_iters ? ant_u(cx, K).ls_fast : ant_u(cx, K).ls_iter;
+      const int ls_max = it < U.ls_fast_iters ? U.ls_fast : U.ls_iter;
       for (int ls = 0; ls < ls_max; ls++) {
         float d1 = 0.f, d2 = 0.f;
 #pragma unroll
@@ -1256,11 +1275,12 @@ __device__ __forceinline__ float ant_solve_rows_core(const DevCtx<G, PROF>& cx, 
         if (exact && !done) qacc += corr;
       }
     }
-    if (exact && ant_u(cx, K).trust_exact) done = true;
+    if (exact && U.trust_exact) done = true;
     if (changed && alpha * alpha * sn <= MZ_NEWTON_STALL * MZ_NEWTON_STALL * qn) done = true;  // stationary at fp32 resolution (ant_dyn.h ant_solve)
     cx.tick(s, 7);
     it++;
   }
+  asm volatile("; newton loop end");
   if (isdof) s.qacc[ri] = qacc;
   if (cx.l == 0) {
     s.iters = it;
