@@ -273,7 +273,8 @@ int32_t mz_nu(const mz_handle* h);
  * launch — more waves than SIMDs takes the second), "profile_phases" (0/1: instrumented Ant kernel, see
  * mz_read_phase_cycles), "time_kernels" (n > 0: ring of n HIP event pairs around the step kernel, see
  * mz_last_kernel_ms), "time_kernels_stride" (k >= 1, default 1: only every k-th mz_step carries the pair — a pair costs the queue
- * ~5 us per launch, a tenth of a Point or Swimmer step; bench.py samples every 8th). Returns MZ_OK, MZ_ERR_ARG, or MZ_ERR_UNSUPPORTED for an Ant-only key on another robot. */
+ * ~5 us per launch, a tenth of a Point or Swimmer step; bench.py samples every 8th), "wide_nets" (0/1/2: mz_net networks of up to
+ * MZ_NET_MAX_WIDTH units per layer on the tiled kernel, see "Wide networks" below). Returns MZ_OK, MZ_ERR_ARG, or MZ_ERR_UNSUPPORTED for an Ant-only key on another robot. */
 int32_t mz_set_option(mz_handle* h, const char* key, double value);
 
 /* What the next mz_step launches (ABI 8).  The kernel instantiation a handle steps with is chosen from the robot, its maze's
@@ -282,7 +283,8 @@ int32_t mz_set_option(mz_handle* h, const char* key, double value);
  * states give round-off-different trajectories at different num_envs, on shards of unequal size or on devices with another
  * CU count.  Keys: "engine" (0 = the robot family's specialised kernel, 1 = the general engine of mz_model.engine),
  * "lanes_per_env", "waves_per_simd", "device_simds" (4 x compute units), "ls_fast_iterations", "rollout_fused" (1: mz_rollout runs
- * this handle on its fused kernels, 0: it runs the step's launches in a loop).  Returns MZ_OK or MZ_ERR_ARG. */
+ * this handle on its fused kernels, 0: it runs the step's launches in a loop), "wide_nets" (the option's mode).  Returns MZ_OK or
+ * MZ_ERR_ARG. */
 int32_t mz_get_info(const mz_handle* h, const char* key, double* value);
 
 /* Auto-reset observation convention.  With option "auto_reset" = 1 an env whose step ended its episode (done != 0) is
@@ -530,7 +532,26 @@ int32_t mz_gae(mz_handle* h, int32_t n_steps, const float* reward_dev, const uin
  * MZ_ERR_ARG, with a message that names the argument: a NULL net or NULL params_dev, a wrong struct_size, n_hidden outside 0 .. 2, a
  * width outside 1 .. MZ_POLICY_MAX_HIDDEN in a layer in use, a non-zero width in a layer not in use, activation outside
  * {MZ_ACT_TANH, MZ_ACT_RELU}, squash outside {0, 1}, a critic with squash != 0, an env_stride that is neither 0 nor count, sample
- * outside {0, 1}, and everything mz_rollout_actor_critic refuses. */
+ * outside {0, 1}, and everything mz_rollout_actor_critic refuses.
+ *
+ * Wide networks: mz_set_option(h, "wide_nets", v), v = 0, 1 or 2 (anything else: MZ_ERR_ARG, the mode stays), reported by
+ * mz_get_info(h, "wide_nets").  Opt-in per handle; MZ_POLICY_MAX_HIDDEN, MZ_ABI_VERSION and every struct stay as they are.
+ *   0 (default)  as described above: a width above MZ_POLICY_MAX_HIDDEN is refused.
+ *   1            every entry that takes an mz_net — mz_net_act, mz_net_value, mz_net_sample, mz_net_sample_head, mz_net_eval_ctx,
+ *                mz_net_value_ctx, mz_rollout_net, mz_rollout_ex, mz_rollout_head, mz_rollout_ctx — accepts hidden[k] = 1 ..
+ *                MZ_NET_MAX_WIDTH.  A network with a layer wider than MZ_POLICY_MAX_HIDDEN runs the tiled kernel (csrc/mz_net_tile.h:
+ *                a tile of 16 rows per block, each shared weight loaded once per tile); every other network runs what it ran, the
+ *                fused rollout kernels included.
+ *   2            as 1, and every mz_net network of the handle runs the tiled kernel whatever its widths.
+ * The arithmetic does not change — one serial fp32 dot product per unit, in index order, product and sum rounded separately —, so the
+ * two kernel families return the same bits for the same network and policy.py stays the model at every width.  Everything else
+ * about a network is as above: the packed layout, count and both env_stride values, both activations, the squash, both noise modes,
+ * log_std behind the network or a head, a bound normaliser, a context, the final_obs row of a critic under auto-reset.  A rollout
+ * plan in which the actor or the critic runs tiled takes the launch-by-launch loop on every handle, as a plan with a context does,
+ * and each of its networks picks its kernel by its own widths and the mode; "rollout_fused" keeps describing mz_rollout.  The entries
+ * that take an int `hidden` stay at MZ_POLICY_MAX_HIDDEN and on their kernels in every mode.  MZ_ERR_UNSUPPORTED: a tiled network
+ * with more than 128 output units (nu > 128, or a head with nu > 64). */
+#define MZ_NET_MAX_WIDTH 256
 #define MZ_NET_MAX_HIDDEN_LAYERS 2
 #define MZ_ACT_TANH 0
 #define MZ_ACT_RELU 1

@@ -10,6 +10,7 @@
 
 #include "mz_gae.h"
 #include "mz_internal.h"
+#include "mz_net_tile.h"
 #include "mz_policy.h"
 #include "mz_render.h"
 #include "mz_returns.h"
@@ -411,6 +412,11 @@ int32_t mz_set_option(mz_handle* h, const char* key, double value) {
   if (!strcmp(key, "auto_reset")) { h->auto_reset = value != 0; return MZ_OK; }
   if (!strcmp(key, "seed")) { h->seed = (uint64_t)value; return MZ_OK; }
   if (!strcmp(key, "env_index_offset")) { h->env0 = (uint64_t)value; return MZ_OK; }
+  if (!strcmp(key, "wide_nets")) {  // mz_net networks of up to MZ_NET_MAX_WIDTH units per layer on the tiled kernel (include/mazestep.h)
+    if (value != 0.0 && value != 1.0 && value != 2.0) return set_err(h, MZ_ERR_ARG, "wide_nets must be 0, 1 or 2", hipSuccess);
+    h->wide_nets = (int)value;
+    return MZ_OK;
+  }
   if (h->robot == MZ_ROBOT_POINT && !strcmp(key, "ls_fast_iterations")) {  // the Point's float64 solvers: unit steps before the exact search (0 = search in every iteration)
     if (value < 0 || value > 50) return set_err(h, MZ_ERR_ARG, "ls_fast_iterations must be 0 .. 50", hipSuccess);
     h->point.unit_steps = (int)value;
@@ -488,6 +494,7 @@ int32_t mz_get_info(const mz_handle* h, const char* key, double* value) {
   if (!strcmp(key, "device_simds")) { *value = (double)h->simds; return MZ_OK; }
   if (!strcmp(key, "obs_norm")) { *value = h->nrm_mean ? 1.0 : 0.0; return MZ_OK; }  // mz_bind_obs_norm: a normaliser is bound (1) or not (0)
   if (!strcmp(key, "rollout_fused")) { *value = (double)mzk_planar_rollout_fused(h); return MZ_OK; }  // mz_rollout: fused kernels (1) or the step's launches in a loop (0)
+  if (!strcmp(key, "wide_nets")) { *value = (double)h->wide_nets; return MZ_OK; }  // the option's mode
   if (!strcmp(key, "ls_fast_iterations")) {  // Newton iterations of a solve that take unit steps (-1: this handle's kernels have no such phase)
     *value = h->robot == MZ_ROBOT_ANT ? (double)h->ant.ls_fast_iters : (h->robot == MZ_ROBOT_POINT ? (double)h->point.unit_steps : -1.0);
     return MZ_OK;
@@ -764,6 +771,17 @@ int32_t mz_value(mz_handle* h, const float* vparams_dev, int64_t env_stride, int
 // the checks the three mz_net entries share; `which`: the argument's name ("actor" / "critic"), nout: nu or 1, stochastic: the
 // vector carries log_std[nu] behind the network — unless `head`: the output layer is 2 nu units wide and nothing follows it.
 // MZ_OK or MZ_ERR_ARG with the message set.
+// Which kernel family evaluates an mz_net on this handle (option "wide_nets"): the tiled kernel of mz_net_tile.h for a network with a
+// layer wider than MZ_POLICY_MAX_HIDDEN (modes 1 and 2) and for every network in mode 2, the group kernels above otherwise.  The
+// entries that take an int `hidden` never ask: their networks stay on the group kernels in every mode.
+static bool net_tiled(const mz_handle* h, const mz_net* net) {
+  if (h->wide_nets == 2) return true;
+  if (h->wide_nets == 1)
+    for (int k = 0; k < net->n_hidden && k < MZ_NET_MAX_HIDDEN_LAYERS; k++)
+      if (net->hidden[k] > MZ_POLICY_MAX_HIDDEN) return true;
+  return false;
+}
+
 static int net_args(mz_handle* h, const char* who, const char* which, const mz_net* net, int nout, bool stochastic, bool is_critic,
                     bool head = false, int cdim = 0) {
   char msg[200];
@@ -776,7 +794,9 @@ static int net_args(mz_handle* h, const char* who, const char* which, const mz_n
   if (net->n_hidden < 0 || net->n_hidden > MZ_NET_MAX_HIDDEN_LAYERS) return fail("->n_hidden", "must be 0 .. MZ_NET_MAX_HIDDEN_LAYERS (2)");
   for (int k = 0; k < MZ_NET_MAX_HIDDEN_LAYERS; k++) {
     const char* field = k ? "->hidden[1]" : "->hidden[0]";
-    if (k < net->n_hidden && (net->hidden[k] < 1 || net->hidden[k] > MZ_POLICY_MAX_HIDDEN)) return fail(field, "must be 1 .. MZ_POLICY_MAX_HIDDEN (64)");
+    if (k < net->n_hidden && (net->hidden[k] < 1 || net->hidden[k] > (h->wide_nets ? MZ_NET_MAX_WIDTH : MZ_POLICY_MAX_HIDDEN)))
+      return fail(field, h->wide_nets ? "must be 1 .. MZ_NET_MAX_WIDTH (256): option wide_nets is on"
+                                      : "must be 1 .. MZ_POLICY_MAX_HIDDEN (64); option wide_nets = 1 admits up to MZ_NET_MAX_WIDTH (256)");
     if (k >= net->n_hidden && net->hidden[k] != 0) return fail(field, "must be 0: the layer is not in use");
   }
   if (net->activation != MZ_ACT_TANH && net->activation != MZ_ACT_RELU) return fail("->activation", "must be MZ_ACT_TANH (0) or MZ_ACT_RELU (1)");
@@ -791,6 +811,12 @@ static int net_args(mz_handle* h, const char* who, const char* which, const mz_n
                                 : head ? "must be 0 (one shared network) or the head count (one per env; an output layer of 2 nu units, no log_std behind it)"
                                 : stochastic ? "must be 0 (one shared network) or count (one per env; log_std[nu] behind the network counts)"
                                            : "must be 0 (one shared network) or count (one per env)");
+  // the LDS rows of the tiled kernel (mz_net_tile.h)
+  if (net_tiled(h, net) && (h->model.obs_dim + cdim > MZT_IN_MAX || (head ? 2 * nout : nout) > MZT_OUT_MAX)) {
+    snprintf(msg, sizeof(msg), "%s: %s runs the tiled kernel (wide_nets), which takes at most %d inputs and %d output units", who, which, MZT_IN_MAX,
+             MZT_OUT_MAX);
+    return set_err(h, MZ_ERR_UNSUPPORTED, msg, hipSuccess);
+  }
   return MZ_OK;
 }
 
@@ -846,6 +872,53 @@ static void net_value_launch(mz_handle* h, hipStream_t st, const mz_net* critic,
 #undef MZ_NET_VALUE
 }
 
+static void net_sample_head_launch(mz_handle* h, hipStream_t st, const mz_net* actor, const mz_head* head, float logA, uint64_t noise_seed,
+                                   uint64_t noise_step, const float* obs_dev, float* actions_dev, float* logp_dev,
+                                   const mz_context* ctx = nullptr);
+
+// One launch of the tiled kernel (mz_net_tile.h): the rows, the normaliser and the context of the group kernels' launches — ctx_norm,
+// so a context without a bound normaliser goes through the identity here too —, a tile of MZT_ROWS rows per block.
+static mzt_job tile_job(mz_handle* h, int kind, const mz_net* net, const mz_context* ctx, const float* obs_dev) {
+  const mzp_norm nm = ctx_norm(h, ctx);
+  mzt_job J{};
+  J.kind = kind; J.n = h->n; J.obs_dim = h->model.obs_dim; J.cdim = nm.cdim; J.nu = h->model.nu;
+  J.s = net_shape(net); J.squash = net->squash; J.action_scale = (float)net->action_scale; J.mode = MZ_NOISE_PRE_SQUASH;
+  J.params = net->params_dev; J.pstride = (long)net->env_stride; J.env0 = h->env0;
+  J.obs = obs_dev; J.mean = nm.mean; J.inv_std = nm.inv_std; J.clip = nm.clip; J.ctx = nm.ctx;
+  return J;
+}
+static void tile_launch(mz_handle* h, hipStream_t st, const mzt_job& J) {
+  hipLaunchKernelGGL(net_tile_kernel, dim3((unsigned)((h->n + MZT_ROWS - 1) / MZT_ROWS)), dim3(MZT_THREADS), 0, st, J);
+}
+
+// The three launches of an mz_net entry, each on the kernel family net_tiled names for the network: net_act_launch /
+// net_sample_head_launch / net_value_launch with the same arguments, or the tiled kernel.
+static void net_act_run(mz_handle* h, hipStream_t st, const mz_net* actor, int sample, uint64_t noise_seed, uint64_t noise_step,
+                        const float* obs_dev, float* actions_dev, float* logp_dev, int noise_mode = MZ_NOISE_PRE_SQUASH,
+                        const mz_context* ctx = nullptr) {
+  if (!net_tiled(h, actor)) return net_act_launch(h, st, actor, sample, noise_seed, noise_step, obs_dev, actions_dev, logp_dev, noise_mode, ctx);
+  mzt_job J = tile_job(h, sample ? MZT_SAMPLE : MZT_ACT, actor, ctx, obs_dev);
+  J.mode = noise_mode; J.key = sample ? mzp_noise_key(noise_seed, noise_step) : 0;
+  J.actions = actions_dev; J.logp = sample ? logp_dev : NULL;
+  tile_launch(h, st, J);
+}
+static void net_head_run(mz_handle* h, hipStream_t st, const mz_net* actor, const mz_head* head, float logA, uint64_t noise_seed,
+                         uint64_t noise_step, const float* obs_dev, float* actions_dev, float* logp_dev, const mz_context* ctx = nullptr) {
+  if (!net_tiled(h, actor)) return net_sample_head_launch(h, st, actor, head, logA, noise_seed, noise_step, obs_dev, actions_dev, logp_dev, ctx);
+  mzt_job J = tile_job(h, MZT_HEAD, actor, ctx, obs_dev);
+  J.hd = mzp_head{head->log_std_min, head->log_std_max, head->logp_squashed, logA};
+  J.key = mzp_noise_key(noise_seed, noise_step);
+  J.actions = actions_dev; J.logp = logp_dev;
+  tile_launch(h, st, J);
+}
+static void net_value_run(mz_handle* h, hipStream_t st, const mz_net* critic, const float* obs_dev, const float* final_obs_dev,
+                          const uint8_t* done_dev, float* values_dev, const mz_context* ctx = nullptr) {
+  if (!net_tiled(h, critic)) return net_value_launch(h, st, critic, obs_dev, final_obs_dev, done_dev, values_dev, ctx);
+  mzt_job J = tile_job(h, MZT_VALUE, critic, ctx, obs_dev);
+  J.final_obs = final_obs_dev; J.done = done_dev; J.values = values_dev;
+  tile_launch(h, st, J);
+}
+
 int32_t mz_net_act(mz_handle* h, const mz_net* actor, int32_t sample, uint64_t noise_seed, uint64_t noise_step, const float* obs_dev,
                    float* actions_dev, float* logp_dev, void* stream) {
   if (!h) return MZ_ERR_ARG;
@@ -854,7 +927,7 @@ int32_t mz_net_act(mz_handle* h, const mz_net* actor, int32_t sample, uint64_t n
   const int rc = net_args(h, "mz_net_act", "actor", actor, h->model.nu, sample != 0, false);
   if (rc != MZ_OK) return rc;
   DeviceScope scope(h->device);
-  net_act_launch(h, (hipStream_t)stream, actor, sample, noise_seed, noise_step, obs_dev, actions_dev, logp_dev);
+  net_act_run(h, (hipStream_t)stream, actor, sample, noise_seed, noise_step, obs_dev, actions_dev, logp_dev);
   HIPCHK(h, hipGetLastError());
   return MZ_OK;
 }
@@ -865,7 +938,7 @@ int32_t mz_net_value(mz_handle* h, const mz_net* critic, const float* obs_dev, f
   const int rc = net_args(h, "mz_net_value", "critic", critic, 1, false, true);
   if (rc != MZ_OK) return rc;
   DeviceScope scope(h->device);
-  net_value_launch(h, (hipStream_t)stream, critic, obs_dev, NULL, NULL, values_dev);
+  net_value_run(h, (hipStream_t)stream, critic, obs_dev, NULL, NULL, values_dev);
   HIPCHK(h, hipGetLastError());
   return MZ_OK;
 }
@@ -892,7 +965,7 @@ int32_t mz_net_sample(mz_handle* h, const mz_net* actor, const mz_noise* noise, 
   rc = net_args(h, "mz_net_sample", "actor", actor, h->model.nu, true, false);
   if (rc != MZ_OK) return rc;
   DeviceScope scope(h->device);
-  net_act_launch(h, (hipStream_t)stream, actor, 1, noise->seed, noise->step, obs_dev, actions_dev, logp_dev, noise->mode);
+  net_act_run(h, (hipStream_t)stream, actor, 1, noise->seed, noise->step, obs_dev, actions_dev, logp_dev, noise->mode);
   HIPCHK(h, hipGetLastError());
   return MZ_OK;
 }
@@ -920,8 +993,7 @@ static int head_args(mz_handle* h, const char* who, const mz_head* head, const m
 }
 
 static void net_sample_head_launch(mz_handle* h, hipStream_t st, const mz_net* actor, const mz_head* head, float logA, uint64_t noise_seed,
-                                   uint64_t noise_step, const float* obs_dev, float* actions_dev, float* logp_dev,
-                                   const mz_context* ctx = nullptr) {
+                                   uint64_t noise_step, const float* obs_dev, float* actions_dev, float* logp_dev, const mz_context* ctx) {
   const int rows = 256 / MZ_POLICY_LANES;
   const mzp_norm nm = ctx_norm(h, ctx);
   const mzp_head hd{head->log_std_min, head->log_std_max, head->logp_squashed, logA};
@@ -946,7 +1018,7 @@ int32_t mz_net_sample_head(mz_handle* h, const mz_net* actor, const mz_head* hea
   rc = net_args(h, "mz_net_sample_head", "actor", actor, h->model.nu, true, false, true);
   if (rc != MZ_OK) return rc;
   DeviceScope scope(h->device);
-  net_sample_head_launch(h, (hipStream_t)stream, actor, head, logf((float)actor->action_scale), noise->seed, noise->step, obs_dev, actions_dev, logp_dev);
+  net_head_run(h, (hipStream_t)stream, actor, head, logf((float)actor->action_scale), noise->seed, noise->step, obs_dev, actions_dev, logp_dev);
   HIPCHK(h, hipGetLastError());
   return MZ_OK;
 }
@@ -965,8 +1037,10 @@ static hipError_t next_obs_row(mz_handle* h, hipStream_t st, const float* obs_de
 static void rollout_act_launch(mz_handle* h, hipStream_t st, const RolloutPlan& p, bool one_layer, size_t k, float* actions) {
   const mz_net* a = p.actor;
   float* logp = p.logp_seq_dev ? p.logp_seq_dev + k * (size_t)h->n : NULL;
-  if (p.head) net_sample_head_launch(h, st, a, p.head, p.head_logA, p.noise_seed, p.noise_step + k, p.obs_dev, actions, logp, p.ctx);
-  else if (!one_layer) net_act_launch(h, st, a, p.sample, p.noise_seed, p.noise_step + k, p.obs_dev, actions, logp, p.noise_mode, p.ctx);
+  // (a plan of an entry that takes an int `hidden` stays on the group kernels in every mode of "wide_nets")
+  if (p.head) net_head_run(h, st, a, p.head, p.head_logA, p.noise_seed, p.noise_step + k, p.obs_dev, actions, logp, p.ctx);
+  else if (p.legacy && !one_layer) net_act_launch(h, st, a, p.sample, p.noise_seed, p.noise_step + k, p.obs_dev, actions, logp, p.noise_mode, p.ctx);
+  else if (!one_layer) net_act_run(h, st, a, p.sample, p.noise_seed, p.noise_step + k, p.obs_dev, actions, logp, p.noise_mode, p.ctx);
   else if (p.sample)
     policy_sample_launch(h, st, a->params_dev, a->env_stride, a->hidden[0], a->squash, (float)a->action_scale, p.noise_seed, p.noise_step + k, p.obs_dev,
                          actions, logp);
@@ -978,7 +1052,8 @@ static void rollout_value_launch(mz_handle* h, hipStream_t st, const RolloutPlan
                                  const uint8_t* done_dev, float* values_dev) {
   const mz_net* c = p.critic;
   if (one_layer) value_launch(h, st, c->params_dev, c->env_stride, c->hidden[0], p.obs_dev, final_obs_dev, done_dev, values_dev);
-  else net_value_launch(h, st, c, p.obs_dev, final_obs_dev, done_dev, values_dev, p.ctx);
+  else if (p.legacy) net_value_launch(h, st, c, p.obs_dev, final_obs_dev, done_dev, values_dev, p.ctx);
+  else net_value_run(h, st, c, p.obs_dev, final_obs_dev, done_dev, values_dev, p.ctx);
 }
 
 // The driver behind every rollout entry: n_steps times [a = the plan's actor on obs, or row k of its action tensor]; step(a) in one
@@ -1004,7 +1079,9 @@ static int32_t rollout_run(mz_handle* h, const RolloutPlan& plan, void* stream) 
   // A head plan on a five- or six-link chain runs the loop too: their fused kernels compile without the head's branch (planar_kernels.hip).
   const bool long_chain_head = p.head && h->robot == MZ_ROBOT_SWIMMER && h->swimmer.nlink >= 5;
   // A plan with a context runs the loop on every handle: the fused kernels do not stage one.
-  if (mzk_planar_rollout_fused(h) && !six_link_policy && !long_chain_head && !p.ctx) {
+  // So does a plan in which the actor or the critic runs the tiled kernel (option "wide_nets"): the fused kernels hold no wide rows.
+  const bool tiled = !p.legacy && ((p.actor && net_tiled(h, p.actor)) || (p.critic && net_tiled(h, p.critic)));
+  if (mzk_planar_rollout_fused(h) && !six_link_policy && !long_chain_head && !p.ctx && !tiled) {
     HIPCHK(h, mzk_planar_rollout(h, st, p));
     if (h->record) {  // the last step's row
       const size_t tot = n * (od + 2), last = (size_t)(p.n_steps - 1) * n;
@@ -1233,9 +1310,9 @@ int32_t mz_net_eval_ctx(mz_handle* h, const mz_net* actor, const mz_head* head, 
   rc = ctx_prepare(h, ctx);
   if (rc != MZ_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (head) net_sample_head_launch(h, st, actor, head, logf((float)actor->action_scale), noise->seed, noise->step, obs_dev, actions_dev, logp_dev, ctx);
-  else if (noise) net_act_launch(h, st, actor, 1, noise->seed, noise->step, obs_dev, actions_dev, logp_dev, noise->mode, ctx);
-  else net_act_launch(h, st, actor, 0, 0, 0, obs_dev, actions_dev, NULL, MZ_NOISE_PRE_SQUASH, ctx);
+  if (head) net_head_run(h, st, actor, head, logf((float)actor->action_scale), noise->seed, noise->step, obs_dev, actions_dev, logp_dev, ctx);
+  else if (noise) net_act_run(h, st, actor, 1, noise->seed, noise->step, obs_dev, actions_dev, logp_dev, noise->mode, ctx);
+  else net_act_run(h, st, actor, 0, 0, 0, obs_dev, actions_dev, NULL, MZ_NOISE_PRE_SQUASH, ctx);
   HIPCHK(h, hipGetLastError());
   return MZ_OK;
 }
@@ -1252,7 +1329,7 @@ int32_t mz_net_value_ctx(mz_handle* h, const mz_net* critic, const mz_context* c
   DeviceScope scope(h->device);
   rc = ctx_prepare(h, ctx);
   if (rc != MZ_OK) return rc;
-  net_value_launch(h, (hipStream_t)stream, critic, obs_dev, NULL, NULL, values_dev, ctx);
+  net_value_run(h, (hipStream_t)stream, critic, obs_dev, NULL, NULL, values_dev, ctx);
   HIPCHK(h, hipGetLastError());
   return MZ_OK;
 }

@@ -68,6 +68,9 @@ struct mz_handle {
   // normaliser, and the [n][MZ_MAX_CONTEXT] old columns of the relative transition; both allocated on first use, freed by mz_destroy
   float* ctx_ident;
   float* ctx_old;
+  // option "wide_nets" (include/mazestep.h): 0 = widths up to MZ_POLICY_MAX_HIDDEN on the group kernels; 1 = mz_net widths up to
+  // MZ_NET_MAX_WIDTH, a network with a layer wider than 64 on the tiled kernels (mz_net_tile.h); 2 = every mz_net network tiled
+  int wide_nets;
 };
 
 // ---- ant_kernels.hip

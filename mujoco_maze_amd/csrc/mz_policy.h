@@ -73,6 +73,12 @@
 // through which every bit pattern passes unchanged: x - 0 = x (-0 stays -0), x * 1 = x, neither select fires, a NaN stays one.
 // HIRO's goal transition of a rollout (MZ_CTX_RELATIVE), element d < D, fp32, two roundings:  tmp = c[d] + s[d];  c[d] = tmp - s'[d]
 // with s, s' the RAW rows before and behind the step; applied where the step did not end the episode.
+//
+// Wide networks (option "wide_nets"; mz_net_tile.h): a handle that has opted in takes hidden layers of up to MZ_NET_MAX_WIDTH (256)
+// units through the mz_net entries.  Nothing in this file changes for them — MZ_POLICY_MAX_HIDDEN stays the bound of the group
+// functions below and of their LDS rows —: the tiled kernels of mz_net_tile.h evaluate a tile of rows per block, load each shared
+// weight once per tile, and run the SAME serial dot product per (unit, row) and the same unit functions behind it, so they return
+// the bits of the functions here wherever both apply, and policy.py stays the model at every width.
 #pragma once
 #include <math.h>
 #include <stddef.h>

@@ -214,15 +214,26 @@ class VecMazeEnv:
         if key == "auto_reset":
             return self.set_auto_reset(value != 0)
         _capi.check(self._lib, self._h, self._lib.mz_set_option(self._h, key.encode(), float(value)), f"mz_set_option({key})")
+        if key == "wide_nets":  # 0 / 1 / 2 (mz_set_option has refused anything else): what `hidden=` may hold from here on
+            self._wide_nets = int(value)
+
+    def _max_width(self) -> int:
+        """The widest hidden layer this env's networks may have: policy.MAX_WIDTH (256) after `set_option("wide_nets", 1 or 2)`,
+        else policy.MAX_HIDDEN (64)."""
+        from mujoco_maze_amd import policy
+
+        return policy.MAX_WIDTH if getattr(self, "_wide_nets", 0) else policy.MAX_HIDDEN
 
     def launch_info(self) -> dict:
         """What the next step launches (mz_get_info): the engine (0 = the robot family's specialised kernel, 1 = the general engine),
         lanes per env, waves per SIMD, the device's SIMD count, whether rollout() runs this env on fused kernels ("rollout_fused":
-        1) or on the step's launches in a loop (0), and whether an observation normaliser is bound ("obs_norm": `bind_obs_norm`).  The
+        1) or on the step's launches in a loop (0), whether an observation normaliser is bound ("obs_norm": `bind_obs_norm`), and the
+        mode of option "wide_nets" (0: hidden layers of up to 64 units; 1: up to 256, a network wider than 64 on the tiled kernel; 2:
+        every network given as a sequence of widths or with ReLU units on the tiled kernel).  The
         instantiation depends on the batch size and the device; its
         results agree across instantiations to fp32 round-off, not bit for bit (include/mazestep.h)."""
         out = {}
-        for key in ("engine", "lanes_per_env", "waves_per_simd", "device_simds", "ls_fast_iterations", "rollout_fused", "obs_norm"):
+        for key in ("engine", "lanes_per_env", "waves_per_simd", "device_simds", "ls_fast_iterations", "rollout_fused", "obs_norm", "wide_nets"):
             v = C.c_double(0.0)
             _capi.check(self._lib, self._h, self._lib.mz_get_info(self._h, key.encode(), C.byref(v)), f"mz_get_info({key})")
             out[key] = int(v.value)
@@ -513,14 +524,18 @@ class VecMazeEnv:
             info["final_observation"] = self._final_obs
         return info
 
-    @staticmethod
-    def _net_kind(hidden, activation: str, what: str = "hidden"):
+    def _net_kind(self, hidden, activation: str, what: str = "hidden"):
         """(widths, activation index, legacy) of a network given as `hidden` / `activation` (policy.net_shape); legacy: an int
-        `hidden` with tanh, which the entries without mz_net take."""
+        `hidden` with tanh, which the entries without mz_net take.  With option "wide_nets" on, widths go up to 256 and a network
+        wider than 64 is never legacy (the entries with an int `hidden` stay at 64); in mode 2 no network is: the mode puts every
+        network of the env on the tiled kernel, which only the mz_net entries launch."""
         from mujoco_maze_amd import policy
 
-        widths, act = policy.net_shape(hidden, activation, what)
-        return widths, act, bool(np.ndim(hidden) == 0 and act == 0)
+        widths, act = policy.net_shape(hidden, activation, what, max_width=self._max_width())
+        legacy = bool(np.ndim(hidden) == 0 and act == 0)
+        if getattr(self, "_wide_nets", 0) == 2 or any(w > policy.MAX_HIDDEN for w in widths):
+            legacy = False
+        return widths, act, legacy
 
     def _policy_params(self, params, hidden, stochastic: bool = False, log_std: str = "param", cdim: int = 0):
         """params as a contiguous float32 device tensor [npar] or [N, npar] (stochastic: npar_s = npar + nu, log_std behind the
@@ -528,7 +543,7 @@ class VecMazeEnv:
         from mujoco_maze_amd import policy
 
         torch = self._torch
-        npar = policy.param_count(self.obs_dim + cdim, self.nu, hidden, stochastic, log_std)
+        npar = policy.param_count(self.obs_dim + cdim, self.nu, hidden, stochastic, log_std, max_width=self._max_width())
         p = params if torch.is_tensor(params) else torch.as_tensor(np.asarray(params, dtype=np.float32), device=self.device)
         if p.dtype != torch.float32 or not p.is_contiguous() or p.device != self.device:
             p = p.to(device=self.device, dtype=torch.float32).contiguous()
@@ -570,6 +585,12 @@ class VecMazeEnv:
 
         `hidden` may also be a sequence of one or two widths, e.g. `(64, 64)` (params packed by `policy.pack_mlp`), and
         `activation="relu"` makes the hidden units ReLU instead of tanh, one choice for both layers (mz_net_act).
+
+        After `set_option("wide_nets", 1)` a hidden layer may have up to 256 units (SB3's and CleanRL's 256-256 off-policy networks),
+        here and in `policy_sample`, `value`, `rollout_policy` and `rollout_policy_sample`: a network wider than 64 runs the tiled
+        kernel (csrc/mz_net_tile.h), with the same arithmetic and the same numpy model (`policy.reference(.., max_width=256)`), and a
+        rollout with such an actor or critic loops its launches inside the call on every env.  Without the option a width above 64
+        stays a ValueError.
 
         context: float32 [N, C], 1 <= C <= 32 — a per-env row (a goal, a subgoal, a skill) the network reads BEHIND the observation:
         its input row is [obs | context], obs normalised as usual while a normaliser is bound, the context never; params are packed
@@ -770,8 +791,8 @@ class VecMazeEnv:
         from mujoco_maze_amd import policy
 
         torch = self._torch
-        policy.net_shape(hidden, what="the critic's hidden")
-        npar = policy.param_count(self.obs_dim + cdim, 1, hidden)
+        policy.net_shape(hidden, what="the critic's hidden", max_width=self._max_width())
+        npar = policy.param_count(self.obs_dim + cdim, 1, hidden, max_width=self._max_width())
         p = value_params if torch.is_tensor(value_params) else torch.as_tensor(np.asarray(value_params, dtype=np.float32), device=self.device)
         if p.dtype != torch.float32 or not p.is_contiguous() or p.device != self.device:
             p = p.to(device=self.device, dtype=torch.float32).contiguous()

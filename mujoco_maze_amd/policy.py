@@ -56,30 +56,45 @@ log_std_head=(W, b))`).  `sample_reference(..., log_std="state", log_std_bounds=
 
 float32, every operation rounded separately, logA = log(float32(action_scale)) rounded to float32: the density of the squashed
 action, finite wherever z is.  `mean_actor` cuts the deterministic actor (the means' columns) out of a head vector.
+
+Wide networks (`VecMazeEnv.set_option("wide_nets", 1)`, option "wide_nets" of include/mazestep.h): hidden layers of up to MAX_WIDTH =
+256 units, evaluated by the tiled kernel of csrc/mz_net_tile.h with the same arithmetic, so everything above holds at every width.
+`net_shape`, `param_count`, `pack_mlp`, `mean_actor`, `reference`, `sample_reference` and `value_reference` take `max_width=`
+(default MAX_HIDDEN = 64, which refuses 65 as ever): pass `max_width=MAX_WIDTH` for such a network.
 """
 import numpy as np
 
 MAX_HIDDEN = 64  # MZ_POLICY_MAX_HIDDEN (include/mazestep.h)
+MAX_WIDTH = 256  # MZ_NET_MAX_WIDTH: the widest hidden layer of an mz_net network on a handle with option "wide_nets" on
 MAX_HIDDEN_LAYERS = 2  # MZ_NET_MAX_HIDDEN_LAYERS
 ACTIVATIONS = ("tanh", "relu")  # index: MZ_ACT_TANH, MZ_ACT_RELU
 
 
-def net_shape(hidden=0, activation: str = "tanh", what: str = "hidden"):
-    """(widths, activation index) of a network: `hidden` an int (0: affine) or a sequence of one or two widths 1 .. 64, `activation`
-    "tanh" or "relu".  `what` names the argument in the errors."""
+def net_shape(hidden=0, activation: str = "tanh", what: str = "hidden", max_width: int = MAX_HIDDEN):
+    """(widths, activation index) of a network: `hidden` an int (0: affine) or a sequence of one or two widths 1 .. max_width,
+    `activation` "tanh" or "relu".  `what` names the argument in the errors.  max_width: MAX_HIDDEN (64) by default, up to MAX_WIDTH
+    (256) for a network of a handle with `set_option("wide_nets", 1)`; every function here that takes it passes it down."""
+    max_width = int(max_width)
+    if not MAX_HIDDEN <= max_width <= MAX_WIDTH:
+        raise ValueError(f"max_width must be {MAX_HIDDEN} .. {MAX_WIDTH}, got {max_width}")
     if activation not in ACTIVATIONS:
         raise ValueError(f"activation must be 'tanh' or 'relu', got {activation!r}")
     if np.ndim(hidden) == 0:
         h = int(hidden)
-        if not 0 <= h <= MAX_HIDDEN:
-            raise ValueError(f"{what} must be 0 .. {MAX_HIDDEN}, got {h}")
+        if not 0 <= h <= max_width:
+            raise ValueError(f"{what} must be 0 .. {max_width}, got {h}" + _WIDE_HINT * (max_width < MAX_WIDTH and h <= MAX_WIDTH))
         return ((h,) if h else ()), ACTIVATIONS.index(activation)
     widths = tuple(int(w) for w in hidden)
     if not 1 <= len(widths) <= MAX_HIDDEN_LAYERS:
         raise ValueError(f"{what} must be an int or a sequence of one or two widths, got {len(widths)} hidden layers")
-    if any(not 1 <= w <= MAX_HIDDEN for w in widths):
-        raise ValueError(f"{what}: a hidden layer has 1 .. {MAX_HIDDEN} units, got {widths}")
+    if any(not 1 <= w <= max_width for w in widths):
+        raise ValueError(f"{what}: a hidden layer has 1 .. {max_width} units, got {widths}"
+                         + _WIDE_HINT * (max_width < MAX_WIDTH and all(1 <= w <= MAX_WIDTH for w in widths)))
     return widths, ACTIVATIONS.index(activation)
+
+
+# what a refusal of a width 65 .. 256 adds
+_WIDE_HINT = f" (up to {MAX_WIDTH} on an env with set_option('wide_nets', 1), and with max_width={MAX_WIDTH} here)"
 
 
 LOG_STD_KINDS = ("param", "state")
@@ -92,13 +107,13 @@ def _log_std_kind(log_std: str) -> bool:
     return log_std == "state"
 
 
-def param_count(obs_dim: int, nu: int, hidden=0, stochastic: bool = False, log_std: str = "param") -> int:
+def param_count(obs_dim: int, nu: int, hidden=0, stochastic: bool = False, log_std: str = "param", max_width: int = MAX_HIDDEN) -> int:
     """Floats of one policy; with `stochastic` the network's count plus log_std [nu].  hidden: an int or a sequence of one or two
     widths.  log_std="state": a head actor — an output layer of 2 nu units and nothing behind it (`stochastic` is not read)."""
     obs_dim, nu = int(obs_dim), int(nu)
     if _log_std_kind(log_std):
         nu, stochastic = 2 * nu, False
-    sizes = (obs_dim,) + net_shape(hidden)[0] + (nu,)
+    sizes = (obs_dim,) + net_shape(hidden, max_width=max_width)[0] + (nu,)
     return sum(a * b + b for a, b in zip(sizes[:-1], sizes[1:])) + (nu if stochastic else 0)
 
 
@@ -137,7 +152,7 @@ def pack(W1, b1, W2, b2, log_std=None):
     return _with_log_std([W1.T.ravel(), b1, W2.T.ravel(), b2], W2.shape[0], log_std)
 
 
-def pack_mlp(layers, log_std=None, log_std_head=None):
+def pack_mlp(layers, log_std=None, log_std_head=None, max_width: int = MAX_HIDDEN):
     """A network of 0, 1 or 2 hidden layers from 1 .. 3 `(W, b)` pairs in nn.Linear orientation, first layer first: W [out, in],
     b [out] -> float32 [count], every layer as W.T then b; with `log_std` [nu] the stochastic policy's vector, nu numbers longer.
     One pair is `pack_linear`, two pairs are `pack`.  `log_std_head=(W [nu, nin], b [nu])`: the second nn.Linear of a SAC actor, whose
@@ -158,8 +173,10 @@ def pack_mlp(layers, log_std=None, log_std_head=None):
     for k, (W, b) in enumerate(pairs):
         if W.ndim != 2 or b.shape != (W.shape[0],) or (k and W.shape[1] != pairs[k - 1][0].shape[0]):
             raise ValueError(f"layers[{k}]: want W [out, in] and b [out] with in = the width of the layer before, got {W.shape} and {b.shape}")
-        if k < len(pairs) - 1 and not 1 <= W.shape[0] <= MAX_HIDDEN:
-            raise ValueError(f"layers[{k}]: a hidden layer has 1 .. {MAX_HIDDEN} units, got {W.shape[0]}")
+        if k < len(pairs) - 1 and not 1 <= W.shape[0] <= int(max_width):
+            raise ValueError(f"layers[{k}]: a hidden layer has 1 .. {int(max_width)} units, got {W.shape[0]}"
+                             + _WIDE_HINT * (int(max_width) < MAX_WIDTH and 1 <= W.shape[0] <= MAX_WIDTH))
+    net_shape(0, max_width=max_width)  # (refuses a max_width outside MAX_HIDDEN .. MAX_WIDTH)
     return _with_log_std([a for W, b in pairs for a in (W.T.ravel(), b)], pairs[-1][0].shape[0], log_std)
 
 
@@ -186,13 +203,13 @@ def _pre_squash(x, p, nu, shape):
         h = np.where(acc < 0, np.float32(0.0), acc).astype(np.float32) if act else np.tanh(acc).astype(np.float32)
 
 
-def mean_actor(params, obs_dim: int, nu: int, hidden=0):
+def mean_actor(params, obs_dim: int, nu: int, hidden=0, max_width: int = MAX_HIDDEN):
     """The deterministic actor inside a head vector: params [count_h] or [R, count_h] with count_h = param_count(obs_dim, nu, hidden,
     log_std="state") -> float32 [count] or [R, count], count = param_count(obs_dim, nu, hidden): every hidden layer as it is, the
     means' columns of the output layer and their biases.  What `rollout_policy` evaluates a trained SAC actor with."""
     p = np.asarray(_np(params))
     obs_dim, nu = int(obs_dim), int(nu)
-    ch, widths = param_count(obs_dim, nu, hidden, log_std="state"), net_shape(hidden)[0]
+    ch, widths = param_count(obs_dim, nu, hidden, log_std="state", max_width=max_width), net_shape(hidden, max_width=max_width)[0]
     if p.shape[-1:] != (ch,) or p.ndim not in (1, 2):
         raise ValueError(f"params must have shape {(ch,)} or [R, {ch}], got {p.shape}")
     nin = widths[-1] if widths else obs_dim
@@ -207,15 +224,16 @@ def _squashed(acc, squash, action_scale):
     return (np.float32(action_scale) * np.tanh(acc).astype(np.float32)).astype(np.float32) if squash else acc
 
 
-def reference(params, obs, nu: int, hidden=0, squash: bool = False, action_scale: float = 1.0, activation: str = "tanh"):
+def reference(params, obs, nu: int, hidden=0, squash: bool = False, action_scale: float = 1.0, activation: str = "tanh",
+              max_width: int = MAX_HIDDEN):
     """The policy of csrc/mz_policy.h on rows of observations: obs [R, obs_dim] (or [obs_dim]); params [npar] shared by the rows or
     [R, npar], one policy per row; hidden / activation as in `net_shape`.  Returns float32 [R, nu] (or [nu])."""
     x = np.asarray(obs, dtype=np.float32)
     single = x.ndim == 1
     x = np.atleast_2d(x)
     p = np.asarray(params, dtype=np.float32)
-    R, od, nu, shape = x.shape[0], x.shape[1], int(nu), net_shape(hidden, activation)
-    npar = param_count(od, nu, hidden)
+    R, od, nu, shape = x.shape[0], x.shape[1], int(nu), net_shape(hidden, activation, max_width=max_width)
+    npar = param_count(od, nu, hidden, max_width=max_width)
     if p.shape not in ((npar,), (R, npar)):
         raise ValueError(f"params must have shape {(npar,)} or {(R, npar)}, got {p.shape}")
     out = _squashed(_pre_squash(x, p, nu, shape), squash, action_scale)
@@ -269,7 +287,7 @@ _eps = noise  # (sample_reference has an argument of that name)
 
 def sample_reference(params, obs, nu: int, hidden=0, squash: bool = False, action_scale: float = 1.0, noise_seed: int = 0,
                      noise_step: int = 0, slots=None, activation: str = "tanh", noise: str = "pre_squash", log_std: str = "param",
-                     log_std_bounds=(-20.0, 2.0), squashed_logp: bool = False):
+                     log_std_bounds=(-20.0, 2.0), squashed_logp: bool = False, max_width: int = MAX_HIDDEN):
     """The stochastic policy of csrc/mz_policy.h on rows of observations: obs [R, obs_dim] (or [obs_dim]); params [npar_s] shared by
     the rows or [R, npar_s]; slots: the rows' global env slots, default 0 .. R - 1.  Returns (actions float32 [R, nu], logp float32
     [R]) — or ([nu], scalar) for a single row.
@@ -285,15 +303,15 @@ def sample_reference(params, obs, nu: int, hidden=0, squash: bool = False, actio
         raise ValueError(f"noise must be 'pre_squash' or 'action', got {noise!r}")
     if _log_std_kind(log_std):
         return _sample_head_reference(params, obs, nu, hidden, squash, action_scale, noise_seed, noise_step, slots, activation, noise,
-                                      log_std_bounds, squashed_logp)
+                                      log_std_bounds, squashed_logp, max_width)
     if squashed_logp:
         raise ValueError("squashed_logp needs log_std='state'")
     x = np.asarray(obs, dtype=np.float32)
     single = x.ndim == 1
     x = np.atleast_2d(x)
     p = np.asarray(params, dtype=np.float32)
-    R, od, nu, shape = x.shape[0], x.shape[1], int(nu), net_shape(hidden, activation)
-    npar = param_count(od, nu, hidden)
+    R, od, nu, shape = x.shape[0], x.shape[1], int(nu), net_shape(hidden, activation, max_width=max_width)
+    npar = param_count(od, nu, hidden, max_width=max_width)
     if p.shape not in ((npar + nu,), (R, npar + nu)):
         raise ValueError(f"params must have shape {(npar + nu,)} or {(R, npar + nu)} (the network, then log_std [nu]), got {p.shape}")
     sl = np.arange(R) if slots is None else np.atleast_1d(np.asarray(slots, dtype=object)).ravel()
@@ -332,7 +350,7 @@ def head_bounds(log_std_bounds):
 
 
 def _sample_head_reference(params, obs, nu, hidden, squash, action_scale, noise_seed, noise_step, slots, activation, noise, log_std_bounds,
-                           squashed_logp):
+                           squashed_logp, max_width=MAX_HIDDEN):
     if noise != "pre_squash":
         raise ValueError("log_std='state' needs noise='pre_squash'")
     if squashed_logp and not squash:
@@ -342,8 +360,8 @@ def _sample_head_reference(params, obs, nu, hidden, squash, action_scale, noise_
     single = x.ndim == 1
     x = np.atleast_2d(x)
     p = np.asarray(params, dtype=np.float32)
-    R, od, nu, shape = x.shape[0], x.shape[1], int(nu), net_shape(hidden, activation)
-    ch = param_count(od, nu, hidden, log_std="state")
+    R, od, nu, shape = x.shape[0], x.shape[1], int(nu), net_shape(hidden, activation, max_width=max_width)
+    ch = param_count(od, nu, hidden, log_std="state", max_width=max_width)
     if p.shape not in ((ch,), (R, ch)):
         raise ValueError(f"params must have shape {(ch,)} or {(R, ch)} (an output layer of 2 nu units), got {p.shape}")
     sl = np.arange(R) if slots is None else np.atleast_1d(np.asarray(slots, dtype=object)).ravel()
@@ -379,7 +397,7 @@ def _sample_head_reference(params, obs, nu, hidden, squash, action_scale, noise_
     return (act[0], logp[0]) if single else (act, logp)
 
 
-def value_reference(value_params, obs, hidden=0, activation: str = "tanh"):
+def value_reference(value_params, obs, hidden=0, activation: str = "tanh", max_width: int = MAX_HIDDEN):
     """The critic of csrc/mz_policy.h (mzp_value_row) on rows of observations: a policy with nu = 1, never squashed, whose value is
     the pre-squash sum of its one output unit.  obs [R, obs_dim] (or [obs_dim]); value_params [nvpar] shared by the rows or
     [R, nvpar], nvpar = param_count(obs_dim, 1, hidden).  Returns float32 [R] (or a scalar); bit-equal to the device for hidden == 0."""
@@ -387,8 +405,8 @@ def value_reference(value_params, obs, hidden=0, activation: str = "tanh"):
     single = x.ndim == 1
     x = np.atleast_2d(x)
     p = np.asarray(value_params, dtype=np.float32)
-    R, od, shape = x.shape[0], x.shape[1], net_shape(hidden, activation)
-    npar = param_count(od, 1, hidden)
+    R, od, shape = x.shape[0], x.shape[1], net_shape(hidden, activation, max_width=max_width)
+    npar = param_count(od, 1, hidden, max_width=max_width)
     if p.shape not in ((npar,), (R, npar)):
         raise ValueError(f"value_params must have shape {(npar,)} or {(R, npar)}, got {p.shape}")
     with np.errstate(over="ignore", invalid="ignore"):

@@ -38,6 +38,13 @@ step).  K x (env.policy_sample(context=) + env.step + the transition in torch) w
 env.rollout_policy_sample(..., context=, context_update=, return_next_obs, return_contexts), and the call without a context at the
 same shape (a network on obs_dim inputs) beside them.
     python tools/rollout_bench.py --policy 64,64 --activation relu --sample --context 15 --relative 3 --steps 10 --ids PointUMaze-v0,SwimmerUMaze-v0,AntUMaze-v0
+With --policy H --head state --critic HV one SAC-style window with a critic: K x (torch actor with its head + torch critic + env.step) —
+the loop a user runs without the device networks — against one rollout_policy_sample(log_std="state", value_params=) call, and the cost
+of one actor evaluation, one critic evaluation and one env.step.  Widths above 64 (`256,256`) set option "wide_nets" = 1 on every env
+by themselves; --wide-nets 2 puts narrower networks on the tiled kernel as well (the A/B of the two kernel families); --per-env gives
+every env its own network:
+    python tools/rollout_bench.py --policy 256,256 --activation relu --head state --critic 256,256 --ids AntUMaze-v0,PointUMaze-v0
+    python tools/rollout_bench.py --policy 64,64 --activation relu --head state --critic 64,64 --wide-nets 2 [--per-env] --ids AntUMaze-v0
 Kernel durations come from a run of their own:  rocprofv3 --kernel-trace --stats -d <dir> -- python tools/rollout_bench.py --seconds 0.2"""
 import argparse
 import json
@@ -68,6 +75,22 @@ def leg(fn, windows_min, seconds, dev):
             return done, dt
 
 
+WIDE_NETS = 0  # option "wide_nets" of every env of this run (main: from the widths and --wide-nets)
+
+
+def make_env(env_id, n, dev):
+    env = mm.make(env_id, num_envs=n, auto_reset=True, device=dev, force_vec=True)
+    if WIDE_NETS:
+        env.set_option("wide_nets", WIDE_NETS)
+    return env
+
+
+def max_width():
+    from mujoco_maze_amd import policy
+
+    return policy.MAX_WIDTH if WIDE_NETS else policy.MAX_HIDDEN
+
+
 def hidden_arg(text):
     """`32` -> 32, `64,64` -> (64, 64)"""
     w = tuple(int(x) for x in text.split(","))
@@ -79,9 +102,9 @@ def build_net(lin, obs_dim, nout, hidden, activation, dev, log_std=None):
     draws one layer's (W, b), first layer first."""
     from mujoco_maze_amd import policy
 
-    sizes = (obs_dim,) + policy.net_shape(hidden, activation)[0] + (nout,)
+    sizes = (obs_dim,) + policy.net_shape(hidden, activation, max_width=max_width())[0] + (nout,)
     layers = [lin(o, i) for i, o in zip(sizes[:-1], sizes[1:])]
-    params = torch.as_tensor(policy.pack_mlp(layers, log_std=log_std), device=dev)
+    params = torch.as_tensor(policy.pack_mlp(layers, log_std=log_std, max_width=max_width()), device=dev)
     wts = [(W.T.contiguous(), b) for W, b in layers]
     f = torch.tanh if activation == "tanh" else torch.relu
 
@@ -109,7 +132,7 @@ def bind_norm(env, on, dev, g):
 
 def bench(env_id, n, K, seconds, repeats):
     dev = torch.device("cuda", 0)
-    env = mm.make(env_id, num_envs=n, auto_reset=True, device=dev, force_vec=True)
+    env = make_env(env_id, n, dev)
     env.reset(seed=20260928)
     g = torch.Generator(device=dev).manual_seed(1234)
     lo, hi = torch.as_tensor(env.action_space.low, device=dev), torch.as_tensor(env.action_space.high, device=dev)
@@ -140,7 +163,7 @@ def bench(env_id, n, K, seconds, repeats):
 def bench_policy(env_id, n, K, H, seconds, repeats, ACT="tanh", obs_norm=False):
     """K closed-loop steps of one shared policy, three ways: torch policy + step, policy_act + step, one rollout_policy."""
     dev = torch.device("cuda", 0)
-    env = mm.make(env_id, num_envs=n, auto_reset=True, device=dev, force_vec=True)
+    env = make_env(env_id, n, dev)
     env.reset(seed=20260928)
     g = torch.Generator(device=dev).manual_seed(1234)
     nrm = bind_norm(env, obs_norm, dev, g)
@@ -183,7 +206,7 @@ def bench_sample(env_id, n, K, H, seconds, repeats, ACT="tanh", obs_norm=False):
     """K closed-loop steps of one shared Gaussian policy: policy_sample + step, one rollout_policy_sample; the deterministic
     rollout_policy of the same network as the yardstick."""
     dev = torch.device("cuda", 0)
-    env = mm.make(env_id, num_envs=n, auto_reset=True, device=dev, force_vec=True)
+    env = make_env(env_id, n, dev)
     env.reset(seed=20260928)
     g = torch.Generator(device=dev).manual_seed(1234)
     bind_norm(env, obs_norm, dev, g)  # (no torch network in this mode)
@@ -226,7 +249,7 @@ def bench_context(env_id, n, K, H, cdim, rel, seconds, repeats, ACT="tanh", obs_
     """K closed-loop steps of one shared Gaussian policy on [obs | context]: policy_sample(context=) + step + the transition in torch,
     one rollout_policy_sample(context=); the same call without a context as the yardstick."""
     dev = torch.device("cuda", 0)
-    env = mm.make(env_id, num_envs=n, auto_reset=True, device=dev, force_vec=True)
+    env = make_env(env_id, n, dev)
     env.reset(seed=20260928)
     g = torch.Generator(device=dev).manual_seed(1234)
     bind_norm(env, obs_norm, dev, g)  # (no torch network in this mode)
@@ -283,7 +306,7 @@ def bench_critic(env_id, n, K, H, HV, seconds, repeats, ACT="tanh", obs_norm=Fal
     """One actor-critic collection window of K steps: policy_sample + step + torch critic + torch GAE loop; one
     rollout_policy_sample with value_params and gae; the same call without a critic."""
     dev = torch.device("cuda", 0)
-    env = mm.make(env_id, num_envs=n, auto_reset=True, device=dev, force_vec=True)
+    env = make_env(env_id, n, dev)
     env.reset(seed=20260928)
     g = torch.Generator(device=dev).manual_seed(1234)
     nrm = bind_norm(env, obs_norm, dev, g)
@@ -342,7 +365,7 @@ def bench_transitions(env_id, n, K, H, seconds, repeats, ACT="tanh", obs_norm=Fa
     import math
 
     dev = torch.device("cuda", 0)
-    env = mm.make(env_id, num_envs=n, auto_reset=True, device=dev, force_vec=True)
+    env = make_env(env_id, n, dev)
     env.reset(seed=20260928)
     g = torch.Generator(device=dev).manual_seed(1234)
     bind_norm(env, obs_norm, dev, g)  # (no torch network in this mode)
@@ -393,7 +416,7 @@ def bench_head(env_id, n, K, H, seconds, repeats, ACT="tanh", obs_norm=False, sq
     from mujoco_maze_amd import policy
 
     dev = torch.device("cuda", 0)
-    env = mm.make(env_id, num_envs=n, auto_reset=True, device=dev, force_vec=True)
+    env = make_env(env_id, n, dev)
     env.reset(seed=20260928)
     g = torch.Generator(device=dev).manual_seed(1234)
     bind_norm(env, obs_norm, dev, g)  # (no torch network in this mode)
@@ -402,10 +425,10 @@ def bench_head(env_id, n, K, H, seconds, repeats, ACT="tanh", obs_norm=False, sq
         k = fan_in ** -0.5
         return (2 * torch.rand((out, fan_in), device=dev, generator=g) - 1) * k, (2 * torch.rand(out, device=dev, generator=g) - 1) * k
 
-    sizes = (env.obs_dim,) + policy.net_shape(H, ACT)[0] + (env.nu,)
+    sizes = (env.obs_dim,) + policy.net_shape(H, ACT, max_width=max_width())[0] + (env.nu,)
     layers = [lin(o, i) for i, o in zip(sizes[:-1], sizes[1:])]
     Wh, bh = lin(env.nu, sizes[-2])
-    params = torch.as_tensor(policy.pack_mlp(layers, log_std_head=(0.1 * Wh, torch.full_like(bh, -0.5))), device=dev)
+    params = torch.as_tensor(policy.pack_mlp(layers, log_std_head=(0.1 * Wh, torch.full_like(bh, -0.5)), max_width=max_width()), device=dev)
     kw = dict(hidden=H, activation=ACT, squash=True, log_std="state", squashed_logp=squashed_logp)
     obs_rows, next_rows = torch.empty((K, n, env.obs_dim), device=dev), torch.empty((K, n, env.obs_dim), device=dev)
     act_rows, logp_rows = torch.empty((K, n, env.nu), device=dev), torch.empty((K, n), device=dev)
@@ -438,6 +461,103 @@ def bench_head(env_id, n, K, H, seconds, repeats, ACT="tanh", obs_norm=False, sq
     env.close()
     return {"env": env_id, "envs": n, "steps_per_window": K, "hidden": H, "activation": ACT, "obs_norm": bool(obs_norm), "head": "state",
             "squashed_logp": bool(squashed_logp), "fused": fused_flag, "flagged_envs": bad, **{name + "_env_steps_per_s": v for name, v in res.items()}}
+
+
+def bench_head_critic(env_id, n, K, H, HV, seconds, repeats, ACT="tanh", per_env=False):
+    """One SAC-style window of K steps with a head actor and a critic (the 256-256 networks of SB3 / CleanRL with `--policy 256,256
+    --critic 256,256`): what a user runs without the device networks — K x (torch actor with its head and sampling, torch critic,
+    env.step) —, against one rollout_policy_sample(log_std="state", value_params=) call; and, one launch each, an actor evaluation
+    (policy_sample), a critic evaluation (value) and an env.step.  per_env: one network per env ([N, count] parameters; no torch leg)."""
+    from mujoco_maze_amd import policy
+
+    dev = torch.device("cuda", 0)
+    env = make_env(env_id, n, dev)
+    env.reset(seed=20260928)
+    g = torch.Generator(device=dev).manual_seed(1234)
+
+    def lin(out, fan_in):
+        k = fan_in ** -0.5
+        return (2 * torch.rand((out, fan_in), device=dev, generator=g) - 1) * k, (2 * torch.rand(out, device=dev, generator=g) - 1) * k
+
+    sizes = (env.obs_dim,) + policy.net_shape(H, ACT, max_width=max_width())[0] + (env.nu,)
+    layers = [lin(o, i) for i, o in zip(sizes[:-1], sizes[1:])]
+    Wh, bh = lin(env.nu, sizes[-2])
+    Wh, bh = 0.1 * Wh, torch.full_like(bh, -0.5)
+    params = torch.as_tensor(policy.pack_mlp(layers, log_std_head=(Wh, bh), max_width=max_width()), device=dev)
+    vparams, torch_critic = build_net(lin, env.obs_dim, 1, HV, ACT, dev)
+    if per_env:
+        params, vparams = params.repeat(n, 1).contiguous(), vparams.repeat(n, 1).contiguous()
+    f = torch.tanh if ACT == "tanh" else torch.relu
+    body = [(W.T.contiguous(), b) for W, b in layers[:-1]]
+    Wm, bm, Ws, bs = layers[-1][0].T.contiguous(), layers[-1][1], Wh.T.contiguous(), bh
+    kw = dict(hidden=H, activation=ACT, squash=True, log_std="state", squashed_logp=True)
+    vals = torch.empty((K, n), device=dev)
+
+    def torch_loop():
+        obs = env._obs
+        for k in range(K):
+            x = obs
+            for Wt, b in body:
+                x = f(torch.addmm(b, x, Wt))
+            m, ls = torch.addmm(bm, x, Wm), torch.clamp(torch.addmm(bs, x, Ws), -20.0, 2.0)
+            z = m + ls.exp() * torch.randn(m.shape, device=dev, generator=g)
+            vals[k] = torch_critic(obs).squeeze(1)
+            obs = env.step(torch.tanh(z))[0]
+
+    def one_call():
+        env.rollout_policy_sample(params, K, value_params=vparams, value_hidden=HV, value_activation=ACT, **kw)
+
+    def actor_eval():
+        for _ in range(K):
+            env.policy_sample(params, **kw)
+
+    def critic_eval():
+        for _ in range(K):
+            env.value(vparams, hidden=HV, activation=ACT)
+
+    zero = torch.zeros((n, env.nu), device=dev)
+
+    def step_only():
+        for _ in range(K):
+            env.step(zero)
+
+    legs = (() if per_env else (("torch_loop", torch_loop),)) + (("rollout_head_critic", one_call), ("actor_eval", actor_eval),
+                                                                 ("critic_eval", critic_eval), ("step", step_only))
+    for _ in range(4):
+        for _, fn in legs:
+            fn()
+    res = {name: [] for name, _ in legs}
+    for _ in range(repeats):
+        for name, fn in legs:
+            w, dt = leg(fn, 2, seconds, dev)
+            res[name].append(n * K * w / dt)
+    bad = int((env.status() & 3).ne(0).sum())
+    info = env.launch_info()
+    env.close()
+    return {"env": env_id, "envs": n, "steps_per_window": K, "hidden": H, "critic_hidden": HV, "activation": ACT, "head": "state", "per_env": bool(per_env),
+            "wide_nets": info["wide_nets"], "fused": info["rollout_fused"], "flagged_envs": bad, **{name + "_env_steps_per_s": v for name, v in res.items()}}
+
+
+def main_head_critic(args):
+    out = []
+    med = lambda v: sorted(v)[len(v) // 2]
+    print(f"SAC-style window with a critic: head actor (hidden {args.policy}) and critic (hidden {args.critic}), {args.activation} units, "
+          f"{'one network per env' if args.per_env else 'shared networks'}, wide_nets = {WIDE_NETS}, {args.steps} steps per window, {args.envs} envs, "
+          f"auto-reset, >= {args.seconds} s per leg, {args.repeats} alternating repeats; M env-steps/s, median (max - min); the last three "
+          "columns: ms per launch of one actor evaluation, one critic evaluation, one env.step (median)")
+    print("%-16s %26s %26s %10s %10s %10s" % ("env", "torch nets + step, K x", "one call", "actor ms", "critic ms", "step ms"))
+    for env_id in args.ids.split(","):
+        r = bench_head_critic(env_id, args.envs, args.steps, args.policy, args.critic, args.seconds, args.repeats, args.activation, args.per_env)
+        out.append(r)
+        cell = lambda v: "%10.3f (%6.3f)" % (med(v) / 1e6, (max(v) - min(v)) / 1e6)
+        ms = lambda v: 1e3 * args.envs / med(v)
+        print("%-16s %26s %26s %10.4f %10.4f %10.4f" % (env_id, cell(r["torch_loop_env_steps_per_s"]) if "torch_loop_env_steps_per_s" in r else "-",
+                                                        cell(r["rollout_head_critic_env_steps_per_s"]), ms(r["actor_eval_env_steps_per_s"]),
+                                                        ms(r["critic_eval_env_steps_per_s"]), ms(r["step_env_steps_per_s"])), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            for r in out:
+                f.write(json.dumps(r) + "\n")
 
 
 def main_head(args):
@@ -568,13 +688,21 @@ def main():
     ap.add_argument("--head", choices=("state",), default=None, help="with --policy H: a state-dependent log-std head on the actor (the SAC window)")
     ap.add_argument("--squashed-logp", action="store_true", help="with --head state: the log-probability of the squashed action")
     ap.add_argument("--context", type=int, default=None, metavar="C", help="with --policy H --sample: a [N, C] context behind the observation (1 .. 32)")
+    ap.add_argument("--wide-nets", type=int, choices=(0, 1, 2), default=None, help="option wide_nets of every env (default: 1 where --policy or "
+                    "--critic is wider than 64, else 0; 2 puts narrower networks on the tiled kernel too)")
+    ap.add_argument("--per-env", action="store_true", help="with --policy H --head state --critic HV: one network per env")
     ap.add_argument("--relative", type=int, default=0, metavar="D", help="with --context C: HIRO's goal transition on the first D entries after every step")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "rollout_bench.py measures on the GPU only"
     if args.sample and args.policy is None:
         ap.error("--sample goes with --policy H")
-    if args.critic is not None and not args.sample:
-        ap.error("--critic goes with --policy H --sample")
+    if args.critic is not None and not args.sample and args.head is None:
+        ap.error("--critic goes with --policy H --sample, or with --policy H --head state")
+    global WIDE_NETS
+    widths = [w for h in (args.policy, args.critic) if h is not None for w in (h if isinstance(h, tuple) else (h,))]
+    WIDE_NETS = args.wide_nets if args.wide_nets is not None else int(any(w > 64 for w in widths))
+    if args.per_env and (args.head is None or args.critic is None):
+        ap.error("--per-env goes with --policy H --head state --critic HV")
     if args.obs_norm and args.policy is None:
         ap.error("--obs-norm goes with --policy H")
     if args.obs_norm:
@@ -583,8 +711,8 @@ def main():
         ap.error("--next-obs goes with --policy H --sample, without --critic")
     if args.noise != "pre_squash" and not args.next_obs:
         ap.error("--noise goes with --next-obs")
-    if args.head is not None and (args.policy is None or args.critic is not None or args.next_obs or args.sample):
-        ap.error("--head goes with --policy H alone (it samples and returns the next rows by itself)")
+    if args.head is not None and (args.policy is None or args.next_obs or args.sample):
+        ap.error("--head goes with --policy H alone (it samples and returns the next rows by itself), or with --critic HV as well")
     if args.squashed_logp and args.head is None:
         ap.error("--squashed-logp goes with --head state")
     if args.context is not None and (not args.sample or args.critic is not None or args.next_obs or args.head is not None):
@@ -593,6 +721,8 @@ def main():
         ap.error("--relative goes with --context C")
     if args.context is not None:
         return main_context(args)
+    if args.head is not None and args.critic is not None:
+        return main_head_critic(args)
     if args.head is not None:
         return main_head(args)
     if args.next_obs:
